@@ -38,8 +38,15 @@
   checks   : every resident batch carries ONE history with a planted impossible read (2 % in, a value inside the
              batch's domain): verdicts are compared element-wise -- that one INVALID, every other one VALID, the CPU
              sample history by history, the planted one's failing op against the oracle's
+  --full   : a plain run measures the headline only: it sets up, warms up, times the K steps, checks the resident batches'
+             verdicts and prints the line.  cpu_baseline, extra.one_batch_at_a_time, extra.fresh_input, the time-to-verdict,
+             the same batch one history per wavefront, the bad read in the middle, the tiers, the other workloads and set-full
+             (with the CPU oracle's cross-checks that go with them) run only with --full
+  --dump-outputs DIR : after the timed steps, what the last step handed back (one row per history of the batch it ran
+             over: verdict, failing op, counters) as DIR/<field>.npy, float64; the inputs are seeded, so two builds run
+             with the same arguments can be compared array by array
 
-Usage: python bench.py --gpus N --steps K --warmup W   (N>1 via torch.distributed.run)
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N>1 via torch.distributed.run)
 """
 import argparse
 import json
@@ -445,6 +452,29 @@ def emit(line):
     print(small, flush=True)
 
 
+DUMP_FIELDS = ("valid", "cause", "analyzer", "fail_op", "prev_ok_op", "final_state", "search_width",
+               "steps", "visited", "probes", "backtracks", "max_depth")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(batch, out_dir):
+    """--dump-outputs: the per-history results the batch's last run handed back (tbc_result, as core.Batch.results() gives them; no
+    witness is asked for, and the device timings are left out) -> out_dir/<field>.npy, float64, history i in row i.  fail_op /
+    prev_ok_op are -1 where there is none; out_dir/history_index.npy says which history each row is.  A batch too big for
+    DUMP_MAX_BYTES is sampled: a fixed, seeded set of rows."""
+    import numpy as np
+    res = batch.results(copy_witness=False)
+    rows = np.arange(len(res))
+    cap = DUMP_MAX_BYTES // (8 * (len(DUMP_FIELDS) + 1))
+    if len(rows) > cap:
+        rows = np.sort(np.random.default_rng(0).choice(len(rows), cap, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for f in DUMP_FIELDS:
+        col = np.array([-1 if res[i][f] is None else res[i][f] for i in rows], np.float64)
+        np.save(os.path.join(out_dir, f"{f}.npy"), col)
+    np.save(os.path.join(out_dir, "history_index.npy"), rows.astype(np.float64))
+
+
 LEGS = {"tiers": leg_tiers, "set_full": leg_set_full,
         "workload_2": lambda a, d: leg_workload(a, d, "workload_2"), "workload_3": lambda a, d: leg_workload(a, d, "workload_3"),
         "workload_crashed": lambda a, d: leg_workload(a, d, "workload_crashed")}
@@ -525,6 +555,11 @@ def main():
     ap.add_argument("--sharded-ttv", action="store_true",
                     help="N > 1 only: also time ONE history swept by all N GPUs (shard.check_sharded: wavefronts dealt to the ranks, "
                          "one RCCL all-gather of the relation tables); off by default -- it adds a collective to the run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline (CPU baselines, one batch at a time, fresh inputs, time-to-verdict, the other "
+                         "workloads, tiers, set-full); a plain run times the headline's steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (per history: verdict, failing op, counters) as DIR/<field>.npy")
     ap.add_argument("--leg", default=None, help="(internal) run this one extra leg and print its result: see run_leg")
     args = ap.parse_args()
     if args.leg is not None:
@@ -535,6 +570,8 @@ def main():
         torch.cuda.set_device(lr)
         print(json.dumps({"leg": args.leg, "result": LEGS[args.leg](args, lr)}), flush=True)
         return
+    if not args.full:
+        args.only_headline = True
     if args.only_headline:
         args.no_cpu = args.no_tiers = args.no_set_full = True
         args.busy2 = args.busy3 = args.info4 = 0.0
@@ -591,7 +628,11 @@ def main():
     F = max(1, args.in_flight)
     t_gen = time.time()
     seeds = shard.shard_indices(F * B * world, rank, world)      # history i of the job lives on rank i % world
-    hists_all = [synth.register_ops_many(seeds[k * B:(k + 1) * B], n_ops=args.ops, n_procs=args.procs, busy=args.busy, info=args.info) for k in range(F)]
+    # (the generator's thread pool sized to the CPUs this process may use: more threads than the quota only slow it down; the histories are
+    # the seeds', whatever the pool)
+    gen_workers = usable_cores()[0]
+    hists_all = [synth.register_ops_many(seeds[k * B:(k + 1) * B], workers=gen_workers, n_ops=args.ops, n_procs=args.procs, busy=args.busy, info=args.info)
+                 for k in range(F)]
     # every resident batch carries ONE history with a planted bad read (its last): a verdict mix-up cannot hide behind "all valid".
     # In the headline the read is planted 2 % into the history, as in rounds 3 and 4 (the workload is VALID histories; the guard should not
     # be what is measured): an INVALID verdict means exhausting the configs up to the failing completion, nine times a valid history's
@@ -652,6 +693,9 @@ def main():
     search_ns, pack_ns, init_ns, retry_ns = ([tm[k] for tm in tms] for k in ("search", "pack", "init", "retries"))
     wait_ns = [tm["turn_wait"] for tm in tms]
     leg("timed region done")
+    if args.dump_outputs is not None and rank == 0:
+        # before anything else runs a batch: the fresh-input leg (--full) puts other histories into them
+        dump_outputs(batches[(args.steps - 1) % F], args.dump_outputs)      # (step i was a pass over batch i % F)
     # the same passes with nothing else in flight: one batch, one pass after the other (never `value` unless --in-flight 1)
     alone = None
     if F > 1 and not args.only_headline:
@@ -896,7 +940,7 @@ def main():
             assert out_mid["with_handover"]["fail_op"] == out_mid["without_handover"]["fail_op"]
             line["extra"]["bad_read_in_the_middle"] = out_mid
         leg("time to verdict (one history through tbc_check)")
-        if on_gpu:      # (one history through tbc_check: needs the device)
+        if on_gpu and not args.only_headline:      # (one history through tbc_check: needs the device)
             ttv, ttv_dfs, analyzers = [], [], []
             o_sweep = core.make_opts(device=local_rank, want_witness=False, algorithm=N.ALG_COMPETITION)
             o_dfs = core.make_opts(device=local_rank, want_witness=True, algorithm=N.ALG_COMPETITION, search_width=args.width)

@@ -2,12 +2,10 @@
 machine without a JVM CAN check, it checks: the file reads as Clojure forms (balanced brackets, strings, comments), its `abi` table
 -- every struct size, field offset and enum code the shim uses -- equals the library's ctypes binding (which tests/test_abi.py pins to
 include/tbcheck.h with gcc), every (o :struct :field) in the code names an entry of that table, no .getX / .setX takes a bare numeric
-offset, the entry points it invokes are exported by libtbcheck.so, and the call-site patches apply to the reference where it is on disk."""
+offset, the entry points it invokes are exported by libtbcheck.so, and the call-site patches are well-formed and call what the shim defines."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
@@ -15,7 +13,6 @@ from jepsen_tigerbeetle_amd.jepsen import edn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "clj", "src", "tigerbeetle", "checker", "gpu_linear.clj")
-REF = "/root/reference"
 
 
 def top_level_forms(src):
@@ -157,18 +154,42 @@ def test_integration_md_points_at_the_files():
         assert path in doc and os.path.exists(os.path.join(ROOT, path)), path
 
 
-@pytest.mark.skipif(not os.path.isdir(REF) or shutil.which("patch") is None, reason="the reference is only on disk in the build container")
-def test_call_site_patches_apply_to_the_reference(tmp_path):
-    work = tmp_path / "ref"
-    for rel in ("project.clj", "src/tigerbeetle/workloads/set_full.clj", "src/tigerbeetle/tests/ledger.clj"):
-        os.makedirs(os.path.dirname(work / rel), exist_ok=True)
-        shutil.copy(os.path.join(REF, rel), work / rel)
-    for p in ("project", "set_full", "ledger"):
-        subprocess.check_call(["patch", "-p1", "-s", "-i", os.path.join(ROOT, "clj", "patches", p + ".patch")], cwd=work)
-    for rel in ("project.clj", "src/tigerbeetle/workloads/set_full.clj", "src/tigerbeetle/tests/ledger.clj"):
-        top_level_forms(open(work / rel).read())          # still balanced after the patch
-    assert "gpu-linear/linearizable" in open(work / "src/tigerbeetle/workloads/set_full.clj").read()
-    assert "net.java.dev.jna/jna" in open(work / "project.clj").read()
+def test_call_site_patches_are_well_formed_and_call_the_shim(shim):
+    """The call-site patches as the repository holds them (the files they patch belong to the Jepsen test, not to this repository):
+    each targets its one file, every hunk's header counts its lines and the hunks' offsets follow from each other -- what `patch -p1`
+    needs to apply them --, and every gpu-linear/<name> they add is defined by the shim."""
+    src, _ = shim
+    defined = set(re.findall(r"^\(defn\s+(?:\^\S+\s+)?([^\s\]\[()]+)", src, re.M))
+    targets = {"project": "project.clj", "set_full": "src/tigerbeetle/workloads/set_full.clj", "ledger": "src/tigerbeetle/tests/ledger.clj"}
+    added = {}
+    for p, rel in targets.items():
+        lines = open(os.path.join(ROOT, "clj", "patches", p + ".patch")).read().split("\n")
+        assert lines[0] == f"--- a/{rel}" and lines[1] == f"+++ b/{rel}", p
+        i, delta, last_end, plus = 2, 0, 0, []
+        while i < len(lines) and lines[i]:
+            m = re.match(r"@@ -(\d+),(\d+) \+(\d+),(\d+) @@", lines[i])
+            assert m, (p, i, lines[i])
+            o0, on, n0, nn = map(int, m.groups())
+            assert o0 > last_end and n0 == o0 + delta, (p, lines[i])
+            i += 1
+            old = new = 0
+            while i < len(lines) and (old < on or new < nn):
+                tag = lines[i][:1]
+                assert tag in (" ", "-", "+"), (p, i, lines[i])
+                old += tag != "+"
+                new += tag != "-"
+                if tag == "+":
+                    plus.append(lines[i][1:])
+                i += 1
+            assert (old, new) == (on, nn), (p, o0)
+            delta, last_end = delta + nn - on, o0 + on - 1
+        assert i == len(lines) - 1 and lines[i] == "", (p, "text after the last hunk")
+        added[p] = "\n".join(plus)
+    assert "net.java.dev.jna/jna" in added["project"]
+    for p in ("set_full", "ledger"):
+        assert "gpu-linear/linearizable" in added[p], p
+        for name in re.findall(r"gpu-linear/([a-z!?-]+)", added[p]):
+            assert name in defined, (p, name)
 
 
 def test_the_crosscheck_recipe_still_covers_every_golden_file():

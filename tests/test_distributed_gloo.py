@@ -197,6 +197,10 @@ class StandInBatch:
     def verdicts(self):
         return self._v
 
+    def results(self, copy_witness=True):
+        return [{"valid": int(v), "cause": 0, "analyzer": 0, "fail_op": None if v else 7, "prev_ok_op": None if v else 6, "final_state": 0,
+                 "search_width": 1, "steps": 10, "visited": 8, "probes": 10, "backtracks": 0, "max_depth": 1} for v in self._v]
+
     def timing_ns(self):
         return {"init": 1000, "pack": 2000, "search": 3000, "retries": 0, "turn_wait": 0}
 
@@ -238,6 +242,43 @@ def test_bench_n_gt_1_plumbing_over_gloo(native):
     # whole-job aggregate: 2 ranks x 6 histories per step; verdicts summed over the ranks' resident batches (one planted INVALID each)
     assert abs(line["value"] - 2 * 6 * 4 / (line["ms_per_step"] * 4 / 1e3)) < 0.01 * line["value"]      # (ms_per_step is rounded to a microsecond)
     assert line["extra"]["valid"] == 2 * 2 * 5 and line["extra"]["unknown"] == 0
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(native, tmp_path):
+    """A plain `bench.py --steps K --warmup W --dump-outputs DIR` (one process, the stand-in batch): the line holds the headline's fields
+    with steps = K, and DIR holds the last step's per-history results as float64 arrays, one row per history of the batch."""
+    import json
+    import subprocess
+    env = dict(os.environ, TBC_BENCH_BACKEND="gloo", TBC_BENCH_BATCH_CLASS="test_distributed_gloo:StandInBatch",
+               PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "tests"), ROOT, os.environ.get("PYTHONPATH", "")]))
+    out_dir = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--batch", "6", "--ops", "300",
+           "--procs", "8", "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 5 and line["n_gpus"] == 1 and line["ms_per_step"] > 0 and "cpu_baseline" not in line
+    v = np.load(out_dir / "valid.npy")
+    assert v.dtype == np.float64 and v.tolist() == [1, 1, 1, 1, 1, 0]          # the planted history is the batch's last
+    assert np.load(out_dir / "fail_op.npy").tolist() == [-1] * 5 + [7]
+    assert np.load(out_dir / "history_index.npy").tolist() == list(range(6))
+    assert sum(f.stat().st_size for f in out_dir.iterdir()) <= 64 << 20
+
+
+def test_bench_dump_samples_a_big_batch(monkeypatch, tmp_path):
+    """A batch whose results would pass the dump's size limit is written as a fixed, seeded sample of its rows."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * (len(bench.DUMP_FIELDS) + 1) * 100)
+    b = StandInBatch([np.zeros(3)] * 1000, None, None)
+    bench.dump_outputs(b, str(tmp_path / "a"))
+    bench.dump_outputs(b, str(tmp_path / "b"))
+    idx = np.load(tmp_path / "a" / "history_index.npy")
+    assert len(idx) == 100 and np.array_equal(idx, np.load(tmp_path / "b" / "history_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "valid.npy"), (idx != 999).astype(np.float64))
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES      # (128 B: each .npy header)
 
 
 def test_bench_extra_legs_run_in_their_own_process(monkeypatch):
