@@ -673,6 +673,32 @@ tbc_status tbc_setfull_create_rows(const tbc_setfull_rows* in, tbc_setfull** han
 tbc_status tbc_setfull_run(tbc_setfull* handle, tbc_setfull_out* out);
 void tbc_setfull_destroy(tbc_setfull* handle);
 
+/* Many keys of one independent history (jepsen.independent, set_full.clj:155) in ONE object: every key in the compact form of
+ * tbc_setfull_rows, the arrays of all keys laid end to end, key after key.  Element and read numbers stay LOCAL to their key (top,
+ * exc and each key's orders exactly as tbc_setfull_rows); exc_off runs over the whole input (exc_off[0] = 0, ascending).  Each call
+ * does a fixed number of launches and copies whatever n_keys is.  Every rule is checked on the host before any device work; an error
+ * names the key (and the read).  Keys with no element or no read are allowed (no read: known = the add's :ok, nothing seen). */
+typedef struct tbc_setfull_keys_in {
+  uint32_t n_keys, device;
+  const uint32_t* n_elements;    /* [n_keys] */
+  const uint32_t* n_reads;       /* [n_keys] */
+  const uint32_t* add_invoke;    /* [sum n_elements], key after key; per key as tbc_setfull_rows */
+  const uint32_t* add_ok;
+  const uint32_t* read_invoke;   /* [sum n_reads], key after key */
+  const uint32_t* read_ok;
+  const uint32_t* top;           /* [sum n_reads], element numbers local to the row's key */
+  const uint64_t* exc_off;       /* [sum n_reads + 1], offsets into exc over the whole input */
+  const uint32_t* exc;           /* element numbers local to the row's key */
+} tbc_setfull_keys_in;
+typedef struct tbc_setfull_keys_out {          /* [sum n_elements] each, key after key; TBC_NO_OP = none */
+  uint32_t *known, *last_present, *last_absent;
+  uint64_t ns_scan, bytes_scanned, bytes_matrix;
+} tbc_setfull_keys_out;
+typedef struct tbc_setfull_keys tbc_setfull_keys;
+tbc_status tbc_setfull_keys_create(const tbc_setfull_keys_in* in, tbc_setfull_keys** handle);
+tbc_status tbc_setfull_keys_run(tbc_setfull_keys* handle, tbc_setfull_keys_out* out);
+void tbc_setfull_keys_destroy(tbc_setfull_keys* handle);
+
 /* ------------------------------------------------------------------- misc */
 uint32_t tbc_version(void);             /* TBC_ABI_VERSION                       */
 const char* tbc_strerror(int status);

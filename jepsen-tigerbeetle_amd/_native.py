@@ -142,6 +142,18 @@ class SetFullOut(C.Structure):
                 ("ns_scan", C.c_uint64), ("bytes_scanned", C.c_uint64), ("bytes_matrix", C.c_uint64)]
 
 
+class SetFullKeysIn(C.Structure):
+    _fields_ = [("n_keys", C.c_uint32), ("device", C.c_uint32), ("n_elements", C.POINTER(C.c_uint32)), ("n_reads", C.POINTER(C.c_uint32)),
+                ("add_invoke", C.POINTER(C.c_uint32)), ("add_ok", C.POINTER(C.c_uint32)), ("read_invoke", C.POINTER(C.c_uint32)),
+                ("read_ok", C.POINTER(C.c_uint32)), ("top", C.POINTER(C.c_uint32)), ("exc_off", C.POINTER(C.c_uint64)),
+                ("exc", C.POINTER(C.c_uint32))]
+
+
+class SetFullKeysOut(C.Structure):
+    _fields_ = [("known", C.POINTER(C.c_uint32)), ("last_present", C.POINTER(C.c_uint32)), ("last_absent", C.POINTER(C.c_uint32)),
+                ("ns_scan", C.c_uint64), ("bytes_scanned", C.c_uint64), ("bytes_matrix", C.c_uint64)]
+
+
 class BatchInput(C.Structure):
     """tbc_batch_input: pointers into one pinned slot of a batch (tbc_batch_map_input)."""
     _fields_ = [("n_hist_cap", C.c_uint32), ("reserved0", C.c_uint32), ("ops_cap", C.c_uint64),
@@ -204,6 +216,9 @@ SYMBOLS = {
     "tbc_setfull_create_rows": (C.c_int, [C.POINTER(SetFullRows), C.POINTER(C.c_void_p)]),
     "tbc_setfull_run": (C.c_int, [C.c_void_p, C.POINTER(SetFullOut)]),
     "tbc_setfull_destroy": (None, [C.c_void_p]),
+    "tbc_setfull_keys_create": (C.c_int, [C.POINTER(SetFullKeysIn), C.POINTER(C.c_void_p)]),
+    "tbc_setfull_keys_run": (C.c_int, [C.c_void_p, C.POINTER(SetFullKeysOut)]),
+    "tbc_setfull_keys_destroy": (None, [C.c_void_p]),
     "tbc_batch_destroy": (None, [C.c_void_p]),
     "tbc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "tbc_comm_init": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),

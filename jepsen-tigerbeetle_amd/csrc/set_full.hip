@@ -42,9 +42,11 @@ constexpr uint32_t kSetFullRows = 2048;      // rows per chunk at most (their me
 constexpr uint32_t kWordCounters = 256;      // the words-loaded statistic: a wavefront adds to counter (its workgroup mod 256), 128 B apart -- thousands of
                                              // atomics on ONE address queue up in one L2 channel; the host adds the counters up
 
-__global__ __launch_bounds__(256) void setfull_prefix_kernel(const uint32_t* add_invoke, const uint32_t* read_ok, uint32_t E, uint32_t R,
-                                                             uint32_t rows_per_chunk, uint32_t chunks, uint32_t* P, uint32_t* pmax) {
-  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+// The kernel bodies below are written once, as inline functions of one key's arrays and of the workgroup's place in that key's grid
+// (bx, by, gx, gy where a kernel read blockIdx / gridDim): the single-key kernels (tbc_setfull_*) pass their own launch's, the keyed
+// ones (tbc_setfull_keys_*, further down) find their key in the plan table first.
+__device__ __forceinline__ void setfull_prefix_row(const uint32_t* add_invoke, const uint32_t* read_ok, uint32_t E, uint32_t R,
+                                                   uint32_t rows_per_chunk, uint32_t chunks, uint32_t* P, uint32_t* pmax, uint32_t r) {
   if (r >= R) return;
   const uint32_t t = read_ok[r];
   uint32_t lo = 0, hi = E;                       // first element whose add was invoked at or after this read's completion
@@ -54,6 +56,11 @@ __global__ __launch_bounds__(256) void setfull_prefix_kernel(const uint32_t* add
   atomicMin(&pmax[chunks + r / rows_per_chunk], lo);         // (the minima lie behind the maxima)
 }
 
+__global__ __launch_bounds__(256) void setfull_prefix_kernel(const uint32_t* add_invoke, const uint32_t* read_ok, uint32_t E, uint32_t R,
+                                                             uint32_t rows_per_chunk, uint32_t chunks, uint32_t* P, uint32_t* pmax) {
+  setfull_prefix_row(add_invoke, read_ok, E, R, rows_per_chunk, chunks, P, pmax, blockIdx.x * 256u + threadIdx.x);
+}
+
 __device__ __forceinline__ uint32_t prefix_mask(uint32_t p, uint32_t w) {       // bits of word w below element number p
   return p >= 32u * w + 32u ? 0xFFFFFFFFu : (p <= 32u * w ? 0u : (1u << (p - 32u * w)) - 1u);
 }
@@ -61,21 +68,39 @@ __device__ __forceinline__ uint32_t prefix_mask(uint32_t p, uint32_t w) {       
 // ---- the membership matrix from the reads' compact form (tbc_setfull_create_rows): one workgroup per read writes its row --
 // ones below top[r], zeros above (a coalesced stream: the matrix is written once, at HBM's write rate) -- and then flips the
 // listed exceptions in it.  No row ever exists on the host.
+__device__ __forceinline__ void setfull_build_row(uint32_t* __restrict__ row, uint32_t t, unsigned long long e0, unsigned long long e1,
+                                                  const uint32_t* __restrict__ exc, uint32_t WPR) {
+  for (uint32_t w = threadIdx.x; w < WPR; w += 256u) row[w] = prefix_mask(t, w);
+  __syncthreads();
+  for (unsigned long long i = e0 + threadIdx.x; i < e1; i += 256u) {
+    const uint32_t e = exc[i];
+    atomicXor(&row[e >> 5], 1u << (e & 31u));
+  }
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(256) void setfull_rows_kernel(const uint32_t* __restrict__ top, const unsigned long long* __restrict__ exc_off,
                                                            const uint32_t* __restrict__ exc, uint32_t R, uint32_t WPR, uint32_t PITCH, uint32_t* __restrict__ M) {
-  for (uint32_t r = blockIdx.x; r < R; r += gridDim.x) {
-    uint32_t* row = M + (uint64_t)r * PITCH;
-    const uint32_t t = top[r];
-    for (uint32_t w = threadIdx.x; w < WPR; w += 256u) row[w] = prefix_mask(t, w);
-    __syncthreads();
-    const unsigned long long e0 = exc_off[r], e1 = exc_off[r + 1];
-    for (unsigned long long i = e0 + threadIdx.x; i < e1; i += 256u) {
-      const uint32_t e = exc[i];
-      atomicXor(&row[e >> 5], 1u << (e & 31u));
-    }
-    __syncthreads();
-  }
+  for (uint32_t r = blockIdx.x; r < R; r += gridDim.x) setfull_build_row(M + (uint64_t)r * PITCH, top[r], exc_off[r], exc_off[r + 1], exc, WPR);
 }
+
+// A workgroup's place in its key's grid: the launch's own (single key) ...
+struct LaunchGrid {
+  __device__ uint32_t bx() const { return blockIdx.x; }
+  __device__ uint32_t by() const { return blockIdx.y; }
+  __device__ uint32_t gx() const { return gridDim.x; }
+  __device__ uint32_t gy() const { return gridDim.y; }
+  __device__ uint32_t ctr() const { return blockIdx.x + blockIdx.y * gridDim.x; }     // which words-loaded counter
+};
+// ... or one found in the plan table (keyed: one flat grid over all keys' tiles)
+struct KeyGrid {
+  uint32_t x, y, nx, ny, flat;
+  __device__ uint32_t bx() const { return x; }
+  __device__ uint32_t by() const { return y; }
+  __device__ uint32_t gx() const { return nx; }
+  __device__ uint32_t gy() const { return ny; }
+  __device__ uint32_t ctr() const { return flat; }
+};
 
 // ---- pass 1: per (word column, chunk of rows) -- is any bit of the column present / absent in the chunk?  The streaming
 // pass.  VEC = 4: a lane takes FOUR consecutive word columns (16 B loads, a wavefront 1 KB of a row; rows of a multiple of four
@@ -107,11 +132,12 @@ __device__ __forceinline__ void store_summary(uint32_t* __restrict__ any_p, uint
   }
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256) void setfull_any_kernel(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
-                                                          const uint32_t* __restrict__ pmax, uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH,
-                                                          uint32_t rows_per_chunk, uint32_t SP, uint32_t* __restrict__ any_p,
-                                                          uint32_t* __restrict__ any_a, unsigned long long* words_loaded) {
+template <int VEC, class Grid>
+__device__ __forceinline__ void setfull_any_tile(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
+                                                 const uint32_t* __restrict__ pmax, uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH,
+                                                 uint32_t rows_per_chunk, uint32_t SP, uint32_t* __restrict__ any_p,
+                                                 uint32_t* __restrict__ any_a, unsigned long long* words_loaded,
+                                                 const Grid& g) {
   constexpr uint32_t U = 8u;                            // rows in flight per lane (16 B each at VEC = 4)
   // grid = (chunks, column blocks), the CHUNK in x.  Workgroup b runs on XCD b % 8 (observed, MI355X_MICROARCH.md "Workgroup dispatch"),
   // and the work is a triangle: column block j counts in the chunks above j / n of the rows only.  With the column block in x (rounds
@@ -121,8 +147,8 @@ __global__ __launch_bounds__(256) void setfull_any_kernel(const uint32_t* __rest
   // The order the workgroups are handed out in (x fastest, then y): the LAST column block first, and in every column block the chunks
   // from its diagonal on -- the tiles on the diagonal decide per row (the general path below: the longest workgroups) and start first,
   // the tiles below the diagonal, which return at once, come last.
-  const uint32_t cb = gridDim.y - 1u - blockIdx.y;
-  const uint32_t c = (blockIdx.x + (uint32_t)((uint64_t)cb * gridDim.x / gridDim.y)) % gridDim.x;
+  const uint32_t cb = g.gy() - 1u - g.by();
+  const uint32_t c = (g.bx() + (uint32_t)((uint64_t)cb * g.gx() / g.gy())) % g.gx();
   const uint32_t w0 = (cb * 256u + threadIdx.x) * (uint32_t)VEC;
   uint32_t loaded = 0;
   __shared__ uint32_t s_P[kSetFullRows];
@@ -135,7 +161,7 @@ __global__ __launch_bounds__(256) void setfull_any_kernel(const uint32_t* __rest
   // a word -- the fold of the general path below costs ~50 vector instructions a row and wavefront, 43 us of a SIMD's time per launch
   // beside 88 us of streaming (scripts/exp/strip_read.hip: this very access pattern, bare, reads at 6.1 TB/s, 6.7 non-temporal).
   const uint32_t tile_hi = 32u * ((cb + 1u) * 256u * (uint32_t)VEC);
-  if (pmax[gridDim.x + c] >= (tile_hi < E ? tile_hi : E)) {
+  if (pmax[g.gx() + c] >= (tile_hi < E ? tile_hi : E)) {
     if (w0 < WPR) {
       typedef uint32_t wvec __attribute__((ext_vector_type(VEC)));
       uint32_t po[VEC], na[VEC];
@@ -170,7 +196,7 @@ __global__ __launch_bounds__(256) void setfull_any_kernel(const uint32_t* __rest
     }
     unsigned long long tot = loaded;
     for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
-    if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * ((blockIdx.x + blockIdx.y * gridDim.x) % kWordCounters), tot);
+    if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (g.ctr() % kWordCounters), tot);
     return;
   }
   for (uint32_t i = threadIdx.x; i < r1 - r0; i += 256u) s_P[i] = P[r0 + i];
@@ -232,7 +258,15 @@ __global__ __launch_bounds__(256) void setfull_any_kernel(const uint32_t* __rest
   }
   unsigned long long tot = loaded;
   for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
-  if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * ((blockIdx.x + blockIdx.y * gridDim.x) % kWordCounters), tot);
+  if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (g.ctr() % kWordCounters), tot);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void setfull_any_kernel(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
+                                                          const uint32_t* __restrict__ pmax, uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH,
+                                                          uint32_t rows_per_chunk, uint32_t SP, uint32_t* __restrict__ any_p,
+                                                          uint32_t* __restrict__ any_a, unsigned long long* words_loaded) {
+  setfull_any_tile<VEC>(M, P, pmax, E, R, WPR, PITCH, rows_per_chunk, SP, any_p, any_a, words_loaded, LaunchGrid{});
 }
 
 // ---- pass 2: one WAVEFRONT per word column resolves its 32 elements.  The chunk summaries say WHICH chunk holds an
@@ -307,17 +341,18 @@ __device__ __forceinline__ uint32_t setfull_last_in_chunk(const uint32_t* __rest
 #ifndef SF_RESOLVE_MIN_WAVES
 #define SF_RESOLVE_MIN_WAVES 8          /* 41 registers: every one of the 8,192 wavefronts of 262,144 elements resident at once */
 #endif
-__global__ __launch_bounds__(256, SF_RESOLVE_MIN_WAVES) void setfull_resolve_kernel(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
-                                                              const uint32_t* __restrict__ read_invoke, const uint32_t* __restrict__ read_ok,
-                                                              const uint32_t* __restrict__ any_p, const uint32_t* __restrict__ any_a,
-                                                              uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH, uint32_t rows_per_chunk, uint32_t chunks, uint32_t SP,
-                                                              const uint32_t* __restrict__ add_ok, uint32_t* lp, uint32_t* la, uint32_t* known,
-                                                              unsigned long long* words_loaded) {
+template <class Grid>
+__device__ __forceinline__ void setfull_resolve_columns(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
+                                                      const uint32_t* __restrict__ read_invoke, const uint32_t* __restrict__ read_ok,
+                                                      const uint32_t* __restrict__ any_p, const uint32_t* __restrict__ any_a,
+                                                      uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH, uint32_t rows_per_chunk, uint32_t chunks, uint32_t SP,
+                                                      const uint32_t* __restrict__ add_ok, uint32_t* lp, uint32_t* la, uint32_t* known,
+                                                      unsigned long long* words_loaded, const Grid& g) {
   const uint32_t lane = threadIdx.x & 63u;
   // workgroup b runs on XCD b % 8 (observed): the eight XCDs take eight contiguous ranges of the columns, so that the lines four
   // neighbouring workgroups read 16 B each of -- the summaries' and the matrix rows' -- are fetched into ONE L2 instead of eight
-  const uint32_t nb = gridDim.x;
-  const uint32_t bb = nb % 8u == 0u ? (blockIdx.x % 8u) * (nb / 8u) + blockIdx.x / 8u : blockIdx.x;
+  const uint32_t nb = g.gx();
+  const uint32_t bb = nb % 8u == 0u ? (g.bx() % 8u) * (nb / 8u) + g.bx() / 8u : g.bx();
   const uint32_t wv_ = threadIdx.x >> 6;
   const uint32_t w = __builtin_amdgcn_readfirstlane(bb * 4u + wv_);
   uint32_t loaded = 0;
@@ -456,7 +491,17 @@ __global__ __launch_bounds__(256, SF_RESOLVE_MIN_WAVES) void setfull_resolve_ker
   }
   unsigned long long tot = loaded;
   for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
-  if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (blockIdx.x % kWordCounters), tot);
+  if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (g.ctr() % kWordCounters), tot);
+}
+
+__global__ __launch_bounds__(256, SF_RESOLVE_MIN_WAVES) void setfull_resolve_kernel(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
+                                                              const uint32_t* __restrict__ read_invoke, const uint32_t* __restrict__ read_ok,
+                                                              const uint32_t* __restrict__ any_p, const uint32_t* __restrict__ any_a,
+                                                              uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH, uint32_t rows_per_chunk, uint32_t chunks, uint32_t SP,
+                                                              const uint32_t* __restrict__ add_ok, uint32_t* lp, uint32_t* la, uint32_t* known,
+                                                              unsigned long long* words_loaded) {
+  setfull_resolve_columns(M, P, read_invoke, read_ok, any_p, any_a, E, R, WPR, PITCH, rows_per_chunk, chunks, SP, add_ok, lp, la, known, words_loaded,
+                          LaunchGrid{});
 }
 
 __global__ __launch_bounds__(256) void setfull_finish_kernel(uint32_t* lp1, uint32_t* la1, uint32_t* known, const uint32_t* add_ok, uint32_t E) {
@@ -674,6 +719,322 @@ tbc_status tbc_setfull_create_rows(const tbc_setfull_rows* in, tbc_setfull** han
 }
 
 void tbc_setfull_destroy(tbc_setfull* S) {
+  if (!S) return;
+  (void)hipSetDevice(S->device);
+  delete S;
+}
+
+}  // extern "C"
+
+// ================================================================ many keys in one object (tbc_setfull_keys_*)
+// jepsen.independent splits the reference's set-full history into keys (set_full.clj:155) and checks each on its own; at real sizes a
+// key's matrix is a few MB and one object per key costs its fixed price (allocation, stream, copies, synchronisation) once per key while
+// its scan fills a sliver of the GPU.  Here every key lives in ONE arena, and each pass is ONE launch over the tiles of all keys: the plan
+// table (built on the host at create) gives each key its arrays' offsets, its chunking and the first tile of each grid; a workgroup finds
+// its key by a binary search over those first tiles (uniform across the workgroup: scalar loads) and then runs the single-key body on it.
+// Each key's pitch is a multiple of four words, so the scan always takes the 16 B path; the bits at or above a key's E never count (the
+// bodies mask them, and the rows kernel writes the padding words as zeros).
+namespace {
+
+struct SfKeyPlan {                 // one key (device table; offsets in 32-bit words)
+  uint32_t E, R, WPR, PITCH, rows_per_chunk, chunks, elem_base, row_base;
+  uint32_t pmax_off, out_off, any_gy, reserved;
+  unsigned long long m_off, sum_off;
+};
+enum { kFirstRows = 0, kFirstPrefix, kFirstAny, kFirstResolve, kFirstGather, kFirsts };   // first[g * (n_keys + 1) + k]: key k's first tile in grid g
+
+// the last key whose first tile (row) is <= b: keys with no tile share their successor's first and are never picked for a tile of theirs
+__device__ __forceinline__ uint32_t sf_find_key(const uint32_t* __restrict__ first, uint32_t n_keys, uint32_t b) {
+  uint32_t lo = 0, hi = n_keys;
+  while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (first[mid] <= b) lo = mid; else hi = mid; }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void setfull_keys_rows_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
+                                                                uint32_t R_all, const uint32_t* __restrict__ top, const unsigned long long* __restrict__ exc_off,
+                                                                const uint32_t* __restrict__ exc, uint32_t* __restrict__ M) {
+  for (uint32_t r = blockIdx.x; r < R_all; r += gridDim.x) {
+    const SfKeyPlan& p = plan[sf_find_key(first + kFirstRows * (n_keys + 1u), n_keys, r)];
+    // the whole pitch is written (zeros past E: top <= E), so no word of the arena the scan loads is left unset
+    setfull_build_row(M + p.m_off + (uint64_t)(r - p.row_base) * p.PITCH, top[r], exc_off[r], exc_off[r + 1], exc, p.PITCH);
+  }
+}
+
+__global__ __launch_bounds__(256) void setfull_keys_prefix_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
+                                                                  const uint32_t* add_invoke, const uint32_t* read_ok, uint32_t* P, uint32_t* pmax) {
+  const uint32_t* f = first + kFirstPrefix * (n_keys + 1u);
+  const uint32_t k = sf_find_key(f, n_keys, blockIdx.x);
+  const SfKeyPlan& p = plan[k];
+  setfull_prefix_row(add_invoke + p.elem_base, read_ok + p.row_base, p.E, p.R, p.rows_per_chunk, p.chunks, P + p.row_base, pmax + p.pmax_off,
+                     (blockIdx.x - f[k]) * 256u + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void setfull_keys_any_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
+                                                               const uint32_t* __restrict__ M, const uint32_t* __restrict__ P, const uint32_t* __restrict__ pmax,
+                                                               uint32_t* __restrict__ any_p, uint32_t* __restrict__ any_a, unsigned long long* words_loaded) {
+  const uint32_t* f = first + kFirstAny * (n_keys + 1u);
+  const uint32_t k = sf_find_key(f, n_keys, blockIdx.x);
+  const SfKeyPlan& p = plan[k];
+  const uint32_t t = blockIdx.x - f[k];
+  // (chunk, column block) = (t % chunks, t / chunks): the order a 2-D launch hands them out in
+  const KeyGrid g{t % p.chunks, t / p.chunks, p.chunks, p.any_gy, blockIdx.x};
+  setfull_any_tile<4>(M + p.m_off, P + p.row_base, pmax + p.pmax_off, p.E, p.R, p.WPR, p.PITCH, p.rows_per_chunk, p.PITCH,
+                      any_p + p.sum_off, any_a + p.sum_off, words_loaded, g);
+}
+
+__global__ __launch_bounds__(256, SF_RESOLVE_MIN_WAVES) void setfull_keys_resolve_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first,
+                                                                  uint32_t n_keys, const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
+                                                                  const uint32_t* __restrict__ read_invoke, const uint32_t* __restrict__ read_ok,
+                                                                  const uint32_t* __restrict__ any_p, const uint32_t* __restrict__ any_a,
+                                                                  const uint32_t* __restrict__ add_ok, uint32_t* lp, uint32_t* la, uint32_t* known,
+                                                                  unsigned long long* words_loaded) {
+  const uint32_t* f = first + kFirstResolve * (n_keys + 1u);
+  const uint32_t k = sf_find_key(f, n_keys, blockIdx.x);
+  const SfKeyPlan& p = plan[k];
+  const uint32_t nb = (p.WPR + 3u) / 4u, bx = blockIdx.x - f[k];
+  // (a key of a multiple of eight workgroups starts on a multiple of eight -- the body's XCD-contiguous order holds -- and the tiles
+  // skipped to get there belong to the key before, past its last workgroup)
+  if (bx >= nb) return;
+  setfull_resolve_columns(M + p.m_off, P + p.row_base, read_invoke + p.row_base, read_ok + p.row_base, any_p + p.sum_off, any_a + p.sum_off,
+                          p.E, p.R, p.WPR, p.PITCH, p.rows_per_chunk, p.chunks, p.PITCH, add_ok + p.elem_base, lp + p.out_off, la + p.out_off,
+                          known + p.out_off, words_loaded, KeyGrid{bx, 0u, nb, 1u, blockIdx.x});
+}
+
+// the padded per-key results into the caller's layout (key after key, n_elements each); a key without reads takes the answer
+// setfull_finish_kernel gives one: nothing seen, known = the add's ack
+__global__ __launch_bounds__(256) void setfull_keys_gather_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
+                                                                  const uint32_t* __restrict__ add_ok, const uint32_t* __restrict__ lp_pad,
+                                                                  const uint32_t* __restrict__ la_pad, const uint32_t* __restrict__ known_pad,
+                                                                  uint32_t* __restrict__ known, uint32_t* __restrict__ lp, uint32_t* __restrict__ la) {
+  const uint32_t* f = first + kFirstGather * (n_keys + 1u);
+  const uint32_t k = sf_find_key(f, n_keys, blockIdx.x);
+  const SfKeyPlan& p = plan[k];
+  const uint32_t e = (blockIdx.x - f[k]) * 256u + threadIdx.x;
+  if (e >= p.E) return;
+  const uint32_t o = p.elem_base + e;
+  if (p.R == 0u) {
+    lp[o] = kNoneU; la[o] = kNoneU; known[o] = add_ok[o];
+  } else {
+    lp[o] = lp_pad[p.out_off + e]; la[o] = la_pad[p.out_off + e]; known[o] = known_pad[p.out_off + e];
+  }
+}
+
+}  // namespace
+
+struct tbc_setfull_keys {
+  int device = 0;
+  uint32_t n_keys = 0, sumE = 0, sumR = 0;
+  uint32_t tiles_rows = 0, tiles_prefix = 0, tiles_any = 0, tiles_resolve = 0, tiles_gather = 0;
+  uint64_t bytes_matrix = 0;
+  SfKeyPlan* d_plan = nullptr;
+  uint32_t *d_first = nullptr, *d_add_ok = nullptr, *d_read_invoke = nullptr, *d_read_ok = nullptr, *d_M = nullptr, *d_P = nullptr;
+  uint32_t *d_pmax = nullptr, *d_anyp = nullptr, *d_anya = nullptr, *d_pad = nullptr, *d_out = nullptr;     // d_pad: lp | la | known padded; d_out: known | lp | la, then the counters
+  unsigned long long* d_words = nullptr;
+  size_t out_bytes = 0, pad_words = 0;                       // the one D2H of a run: d_out .. the end of the counters
+  std::vector<unsigned char> h_out;
+  void* arena = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~tbc_setfull_keys() {
+    if (arena) (void)hipFree(arena);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+// every rule of tbc_setfull_create_rows, key by key, on the host; nothing has touched a device yet
+static tbc_status setfull_keys_validate(const tbc_setfull_keys_in* in, uint64_t& sumE, uint64_t& sumR) {
+  const char* fn = "tbc_setfull_keys_create";
+  if (in->n_keys == 0) { set_error("%s: n_keys is 0", fn); return TBC_ERR_INVALID_ARG; }
+  if (!in->n_elements || !in->n_reads || !in->exc_off) { set_error("%s: null argument", fn); return TBC_ERR_INVALID_ARG; }
+  sumE = 0; sumR = 0;
+  for (uint32_t k = 0; k < in->n_keys; k++) { sumE += in->n_elements[k]; sumR += in->n_reads[k]; }
+  if (sumE >= 0xFFFFFFFFull || sumR >= 0xFFFFFFFFull) { set_error("%s: more than 2^32 - 2 elements or reads in one object", fn); return TBC_ERR_INVALID_ARG; }
+  if ((sumE && (!in->add_invoke || !in->add_ok)) || (sumR && (!in->read_invoke || !in->read_ok || !in->top)) || (in->exc_off[sumR] && !in->exc)) {
+    set_error("%s: null argument", fn);
+    return TBC_ERR_INVALID_ARG;
+  }
+  if (in->exc_off[0] != 0) { set_error("%s: exc_off[0] must be 0", fn); return TBC_ERR_INVALID_ARG; }
+  std::vector<uint32_t> tmp;
+  uint64_t e0 = 0, r0 = 0;
+  for (uint32_t k = 0; k < in->n_keys; e0 += in->n_elements[k], r0 += in->n_reads[k], k++) {
+    const uint32_t E = in->n_elements[k], R = in->n_reads[k];
+    for (uint32_t e = 1; e < E; e++)
+      if (in->add_invoke[e0 + e] <= in->add_invoke[e0 + e - 1]) { set_error("%s: key %u: add_invoke must be strictly ascending (element %u)", fn, k, e); return TBC_ERR_INVALID_ARG; }
+    for (uint32_t r = 0; r < R; r++) {
+      const uint64_t g = r0 + r;
+      if (r && in->read_invoke[g] <= in->read_invoke[g - 1]) { set_error("%s: key %u: read_invoke must be strictly ascending (read %u)", fn, k, r); return TBC_ERR_INVALID_ARG; }
+      if (in->top[g] > E || in->exc_off[g + 1] < in->exc_off[g]) { set_error("%s: key %u read %u: bad top / exc_off (top %u, n_elements %u)", fn, k, r, in->top[g], E); return TBC_ERR_INVALID_ARG; }
+      bool ascending = true;
+      for (uint64_t i = in->exc_off[g]; i < in->exc_off[g + 1]; i++) {
+        if (in->exc[i] >= E) { set_error("%s: key %u read %u: exception names element %u of %u", fn, k, r, in->exc[i], E); return TBC_ERR_INVALID_ARG; }
+        if (i > in->exc_off[g] && in->exc[i] <= in->exc[i - 1]) ascending = false;
+      }
+      if (ascending) continue;        // (strictly ascending: no element twice; any other order is sorted aside, as tbc_setfull_create_rows does)
+      tmp.assign(in->exc + in->exc_off[g], in->exc + in->exc_off[g + 1]);
+      std::sort(tmp.begin(), tmp.end());
+      for (size_t i = 1; i < tmp.size(); i++)
+        if (tmp[i] == tmp[i - 1]) { set_error("%s: key %u read %u lists element %u twice (each element at most once per read)", fn, k, r, tmp[i]); return TBC_ERR_INVALID_ARG; }
+    }
+  }
+  return TBC_OK;
+}
+
+static tbc_status setfull_keys_create_impl(const tbc_setfull_keys_in* in, tbc_setfull_keys* S, uint32_t sumE, uint32_t sumR) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || (int)in->device >= ndev) {
+    set_error("no usable HIP device; libtbcheck has no CPU fallback");
+    return TBC_ERR_NO_DEVICE;
+  }
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, (int)in->device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+    set_error("device %u is not a gfx950 (MI355X) device", in->device);
+    return TBC_ERR_NO_DEVICE;
+  }
+  const uint32_t n = in->n_keys;
+  S->device = (int)in->device; S->n_keys = n; S->sumE = sumE; S->sumR = sumR;
+  // ---- the plan: per key its chunking (tbc_setfull_create's rule: a key of a few reads is one chunk, a large key is chunked as a single
+  // key is) and its place in the arena's regions; per grid the first tile of every key
+  std::vector<SfKeyPlan> plan(n);
+  std::vector<uint32_t> first((size_t)kFirsts * (n + 1), 0u);
+  uint64_t m_words = 0, sum_words = 0, pmax_words = 0, pad_words = 0, tiles[kFirsts] = {};
+  const auto up = [](uint64_t x, uint64_t a) { return (x + a - 1) / a * a; };
+  uint32_t eb = 0, rb = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    SfKeyPlan& p = plan[k];
+    p = SfKeyPlan{};
+    p.E = in->n_elements[k]; p.R = in->n_reads[k]; p.elem_base = eb; p.row_base = rb;
+    p.WPR = (p.E + 31u) / 32u; p.PITCH = (p.WPR + 3u) / 4u * 4u;
+    const bool scan = p.E && p.R;
+    uint32_t chunks = 1;
+    if (scan) {
+      const uint32_t col_blocks = (p.WPR + 255) / 256;
+      chunks = std::max(1u, std::min(256u, 8192u / std::max(1u, col_blocks)));
+      while (chunks > 1 && p.R / chunks < 64) chunks >>= 1;
+      while ((p.R + chunks - 1) / chunks > kSetFullRows) chunks <<= 1;
+    }
+    p.chunks = chunks; p.rows_per_chunk = std::max(1u, (p.R + chunks - 1) / chunks);
+    p.any_gy = (p.PITCH / 4u + 255u) / 256u;
+    m_words = up(m_words, 64); p.m_off = m_words; m_words += (uint64_t)p.R * p.PITCH;
+    sum_words = up(sum_words, 64); p.sum_off = sum_words; sum_words += scan ? (uint64_t)p.chunks * p.PITCH : 0;
+    p.pmax_off = (uint32_t)pmax_words; pmax_words += 2ull * p.chunks;
+    p.out_off = (uint32_t)pad_words; pad_words += 32ull * p.WPR;
+    const uint32_t nb = (p.WPR + 3u) / 4u;
+    first[kFirstRows * (n + 1) + k] = rb;
+    first[kFirstPrefix * (n + 1) + k] = (uint32_t)tiles[kFirstPrefix]; tiles[kFirstPrefix] += scan ? (p.R + 255u) / 256u : 0u;
+    first[kFirstAny * (n + 1) + k] = (uint32_t)tiles[kFirstAny]; tiles[kFirstAny] += scan ? (uint64_t)p.chunks * p.any_gy : 0u;
+    if (scan && nb % 8u == 0u) tiles[kFirstResolve] = up(tiles[kFirstResolve], 8);
+    first[kFirstResolve * (n + 1) + k] = (uint32_t)tiles[kFirstResolve]; tiles[kFirstResolve] += scan ? nb : 0u;
+    first[kFirstGather * (n + 1) + k] = (uint32_t)tiles[kFirstGather]; tiles[kFirstGather] += (p.E + 255u) / 256u;
+    S->bytes_matrix += (uint64_t)p.R * p.WPR * 4;
+    eb += p.E; rb += p.R;
+  }
+  first[kFirstRows * (n + 1) + n] = rb;
+  for (int g = kFirstPrefix; g < kFirsts; g++) first[(size_t)g * (n + 1) + n] = (uint32_t)tiles[g];
+  if (pad_words >= 0xFFFFFFFFull || pmax_words >= 0xFFFFFFFFull || tiles[kFirstAny] >= 0x7FFFFFFFull || tiles[kFirstResolve] >= 0x7FFFFFFFull) {
+    set_error("tbc_setfull_keys_create: too many elements for one object"); return TBC_ERR_INVALID_ARG;
+  }
+  S->tiles_rows = std::min<uint32_t>(sumR, 16384u); S->tiles_prefix = (uint32_t)tiles[kFirstPrefix]; S->tiles_any = (uint32_t)tiles[kFirstAny];
+  S->tiles_resolve = (uint32_t)tiles[kFirstResolve]; S->tiles_gather = (uint32_t)tiles[kFirstGather]; S->pad_words = pad_words;
+  // ---- one arena: the inputs first (ONE H2D from a host image of the same layout), then what the device makes
+  const uint64_t ne = in->exc_off[sumR];
+  size_t cursor = 0;
+  const auto take = [&](size_t bytes) { const size_t at = cursor; cursor += (bytes + 255) & ~(size_t)255; return at; };
+  const size_t o_plan = take(sizeof(SfKeyPlan) * n), o_first = take(first.size() * 4), o_ai = take((size_t)sumE * 4), o_ao = take((size_t)sumE * 4),
+               o_ri = take((size_t)sumR * 4), o_ro = take((size_t)sumR * 4), o_top = take((size_t)sumR * 4), o_off = take(((size_t)sumR + 1) * 8),
+               o_exc = take(ne * 4), o_pm = take(pmax_words * 4);
+  const size_t in_bytes = cursor;
+  const size_t o_M = take(m_words * 4), o_P = take((size_t)sumR * 4), o_any = take(sum_words * 8), o_pad = take(pad_words * 12);
+  const size_t o_out = take((size_t)sumE * 12), o_w = take((size_t)kWordCounters * 128);
+  S->out_bytes = o_w + (size_t)kWordCounters * 128 - o_out;
+  std::vector<unsigned char> img;
+  try { img.assign(in_bytes, 0); S->h_out.assign(S->out_bytes, 0); } catch (const std::bad_alloc&) { set_error("tbc_setfull_keys_create: host memory"); return TBC_ERR_OOM; }
+  const auto put = [&](size_t at, const void* src, size_t bytes) { if (bytes) std::memcpy(img.data() + at, src, bytes); };
+  put(o_plan, plan.data(), sizeof(SfKeyPlan) * n); put(o_first, first.data(), first.size() * 4);
+  put(o_ai, in->add_invoke, (size_t)sumE * 4); put(o_ao, in->add_ok, (size_t)sumE * 4);
+  put(o_ri, in->read_invoke, (size_t)sumR * 4); put(o_ro, in->read_ok, (size_t)sumR * 4); put(o_top, in->top, (size_t)sumR * 4);
+  put(o_off, in->exc_off, ((size_t)sumR + 1) * 8); put(o_exc, in->exc, ne * 4);
+  for (uint32_t k = 0; k < n; k++)        // the chunks' greatest prefixes start at 0, their least at ~0 (the minima lie behind the maxima)
+    std::memset(img.data() + o_pm + ((size_t)plan[k].pmax_off + plan[k].chunks) * 4, 0xFF, (size_t)plan[k].chunks * 4);
+  SF_TRY(hipSetDevice(S->device));
+  SF_TRY(hipMalloc(&S->arena, std::max<size_t>(cursor, 256)));
+  char* const A0 = static_cast<char*>(S->arena);
+  S->d_plan = (SfKeyPlan*)(A0 + o_plan); S->d_first = (uint32_t*)(A0 + o_first); S->d_add_ok = (uint32_t*)(A0 + o_ao);
+  S->d_read_invoke = (uint32_t*)(A0 + o_ri); S->d_read_ok = (uint32_t*)(A0 + o_ro); S->d_M = (uint32_t*)(A0 + o_M); S->d_P = (uint32_t*)(A0 + o_P);
+  S->d_anyp = (uint32_t*)(A0 + o_any); S->d_anya = S->d_anyp + sum_words; S->d_pad = (uint32_t*)(A0 + o_pad);
+  S->d_out = (uint32_t*)(A0 + o_out); S->d_words = (unsigned long long*)(A0 + o_w); S->d_pmax = (uint32_t*)(A0 + o_pm);
+  SF_TRY(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
+  SF_TRY(hipEventCreate(&S->ev0)); SF_TRY(hipEventCreate(&S->ev1));
+  SF_TRY(hipMemcpyAsync(A0, img.data(), in_bytes, hipMemcpyHostToDevice, S->stream));
+  if (sum_words) SF_TRY(hipMemsetAsync(S->d_anyp, 0, sum_words * 8, S->stream));     // (the tiles below the diagonal never write theirs)
+  if (S->tiles_rows)
+    hipLaunchKernelGGL(setfull_keys_rows_kernel, dim3(S->tiles_rows), dim3(256), 0, S->stream, S->d_plan, S->d_first, n, sumR,
+                       (const uint32_t*)(A0 + o_top), (const unsigned long long*)(A0 + o_off), (const uint32_t*)(A0 + o_exc), S->d_M);
+  if (S->tiles_prefix)
+    hipLaunchKernelGGL(setfull_keys_prefix_kernel, dim3(S->tiles_prefix), dim3(256), 0, S->stream, S->d_plan, S->d_first, n,
+                       (const uint32_t*)(A0 + o_ai), S->d_read_ok, S->d_P, S->d_pmax);
+  SF_TRY(hipGetLastError());
+  SF_TRY(hipStreamSynchronize(S->stream));
+  return TBC_OK;
+}
+
+extern "C" {
+
+tbc_status tbc_setfull_keys_create(const tbc_setfull_keys_in* in, tbc_setfull_keys** handle) {
+  if (!in || !handle) { set_error("tbc_setfull_keys_create: null argument"); return TBC_ERR_INVALID_ARG; }
+  uint64_t sumE = 0, sumR = 0;
+  tbc_status st = setfull_keys_validate(in, sumE, sumR);
+  if (st != TBC_OK) return st;
+  tbc_setfull_keys* S = new (std::nothrow) tbc_setfull_keys();
+  if (!S) return TBC_ERR_OOM;
+  st = setfull_keys_create_impl(in, S, (uint32_t)sumE, (uint32_t)sumR);
+  if (st != TBC_OK) { delete S; return st; }
+  *handle = S;
+  return TBC_OK;
+}
+
+tbc_status tbc_setfull_keys_run(tbc_setfull_keys* S, tbc_setfull_keys_out* out) {
+  if (!S || !out || (S->sumE && (!out->known || !out->last_present || !out->last_absent))) { set_error("tbc_setfull_keys_run: null argument"); return TBC_ERR_INVALID_ARG; }
+  SF_TRY(hipSetDevice(S->device));
+  hipStream_t s = S->stream;
+  const uint32_t n = S->n_keys;
+  uint32_t* const lp_pad = S->d_pad; uint32_t* const la_pad = S->d_pad + S->pad_words; uint32_t* const kn_pad = S->d_pad + 2 * S->pad_words;
+  uint32_t* const known = S->d_out; uint32_t* const lp = S->d_out + S->sumE; uint32_t* const la = S->d_out + 2ull * S->sumE;
+  SF_TRY(hipMemsetAsync(S->d_words, 0, (size_t)kWordCounters * 128, s));
+  SF_TRY(hipEventRecord(S->ev0, s));
+  // three launches whatever n_keys is (the resolve pass writes every padded result of a key that has reads; the gather every result)
+  if (S->tiles_any)
+    hipLaunchKernelGGL(setfull_keys_any_kernel, dim3(S->tiles_any), dim3(256), 0, s, S->d_plan, S->d_first, n, S->d_M, S->d_P, S->d_pmax,
+                       S->d_anyp, S->d_anya, S->d_words);
+  if (S->tiles_resolve)
+    hipLaunchKernelGGL(setfull_keys_resolve_kernel, dim3(S->tiles_resolve), dim3(256), 0, s, S->d_plan, S->d_first, n, S->d_M, S->d_P, S->d_read_invoke,
+                       S->d_read_ok, S->d_anyp, S->d_anya, S->d_add_ok, lp_pad, la_pad, kn_pad, S->d_words);
+  if (S->tiles_gather)
+    hipLaunchKernelGGL(setfull_keys_gather_kernel, dim3(S->tiles_gather), dim3(256), 0, s, S->d_plan, S->d_first, n, S->d_add_ok, lp_pad, la_pad, kn_pad,
+                       known, lp, la);
+  SF_TRY(hipGetLastError());
+  SF_TRY(hipEventRecord(S->ev1, s));
+  SF_TRY(hipMemcpyAsync(S->h_out.data(), S->d_out, S->out_bytes, hipMemcpyDeviceToHost, s));        // results and counters: one copy
+  SF_TRY(hipStreamSynchronize(s));
+  float ms = 0;
+  SF_TRY(hipEventElapsedTime(&ms, S->ev0, S->ev1));
+  const unsigned char* h = S->h_out.data();
+  if (S->sumE) {
+    std::memcpy(out->known, h, (size_t)S->sumE * 4);
+    std::memcpy(out->last_present, h + (size_t)S->sumE * 4, (size_t)S->sumE * 4);
+    std::memcpy(out->last_absent, h + (size_t)S->sumE * 8, (size_t)S->sumE * 4);
+  }
+  const unsigned long long* counters = reinterpret_cast<const unsigned long long*>(h + ((char*)S->d_words - (char*)S->d_out));
+  unsigned long long words = 0;
+  for (uint32_t k = 0; k < kWordCounters; k++) words += counters[16u * k];
+  out->ns_scan = (uint64_t)(ms * 1e6);
+  out->bytes_scanned = (uint64_t)words * 4;
+  out->bytes_matrix = S->bytes_matrix;
+  return TBC_OK;
+}
+
+void tbc_setfull_keys_destroy(tbc_setfull_keys* S) {
   if (!S) return;
   (void)hipSetDevice(S->device);
   delete S;

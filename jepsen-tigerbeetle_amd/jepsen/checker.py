@@ -66,6 +66,20 @@ def set_full(opts=None):
     return SetFull(opts)
 
 
+class ReadAllInvokedAdds(Checker):
+    """The reference's own `read-all-invoked-adds` (workloads/set_full.clj:51-75), composed beside set-full at :155-158: every :ok
+    read with :final? must hold every value some :add was invoked with.  A host scan of the history (jepsen/set_full.py); under
+    independent/checker the keyed set-full path answers it from the encoding it already built."""
+
+    def check(self, test, history, opts=None):
+        from . import set_full as sf
+        return sf.read_all_invoked_adds(history)
+
+
+def read_all_invoked_adds():
+    return ReadAllInvokedAdds()
+
+
 class Compose(Checker):
     def __init__(self, checkers):
         self.checkers = dict(checkers)

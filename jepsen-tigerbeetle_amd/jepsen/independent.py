@@ -57,20 +57,78 @@ def subhistory(k, history):
     return out
 
 
+def split(history):
+    """(keys in order of first appearance, {k: subhistory(k, history)}) in ONE walk of the history: the same ops in the same order
+    per key -- a tuple op as a copy with the tuple stripped, every non-tuple op (the same dict) in every key's sub-history, those
+    before the key's first op included."""
+    keys, subs, shared = [], {}, []
+    for op in history:
+        v = op.get("value")
+        if tuple_p(v):
+            sub = subs.get(v.key)
+            if sub is None:
+                sub = subs[v.key] = list(shared)
+                keys.append(v.key)
+            sub.append(dict(op, value=v.value))
+        else:
+            shared.append(op)
+            for sub in subs.values():
+                sub.append(op)
+    return keys, subs
+
+
+def _set_full_members(inner):
+    """{name: checker} when `inner` is what the keyed set-full path answers (set-full, or a compose of set-full, read-all-invoked-adds
+    and linearizable members), else None.  A bare SetFull is {None: it}."""
+    if isinstance(inner, jc.SetFull):
+        return {None: inner}
+    if isinstance(inner, jc.Compose) and inner.checkers and any(isinstance(c, jc.SetFull) for c in inner.checkers.values()) and all(
+            isinstance(c, (jc.SetFull, jc.ReadAllInvokedAdds, jc.Linearizable)) for c in inner.checkers.values()):
+        return dict(inner.checkers)
+    return None
+
+
 class IndependentChecker(jc.Checker):
     def __init__(self, inner):
         self.inner = inner
 
     def check(self, test, history, opts=None):
-        keys = history_keys(history)
-        subs = {k: subhistory(k, history) for k in keys}
+        keys, subs = split(history)
+        members = _set_full_members(self.inner)
         if isinstance(self.inner, jc.Linearizable) and keys:
             results = self._check_batched(keys, subs)
+        elif members is not None and keys:
+            results = self._check_set_full(keys, subs, members, opts)
         else:
             results = {k: self.inner.check(test, subs[k], opts) for k in keys}
         failures = [k for k in keys if results[k].get("valid?") is False]
         return {"valid?": jc.merge_valid(r.get("valid?") for r in results.values()),
                 "results": results, "failures": failures}
+
+    def _check_set_full(self, keys, subs, members, opts):
+        """set-full (alone or composed, set_full.clj:155-158) over all keys: every key encoded once, every key's matrix scanned in one
+        device pass (jepsen/set_full.py scan_keys), each set-full member's result map from the same scan, read-all-invoked-adds from
+        the same encoding, linearizable members as one batch.  Per key what Compose.check / SetFull.check give on its sub-history."""
+        from . import set_full as sf
+        encs = {k: sf.Encoded(subs[k]) for k in keys}
+        sts = sf.scan_keys(encs, device=(opts or {}).get("device", 0))
+        lin = {name: IndependentChecker(c)._check_batched(keys, subs) for name, c in members.items() if isinstance(c, jc.Linearizable)}
+        out = {}
+        for k in keys:
+            res = {}
+            for name, c in members.items():
+                if isinstance(c, jc.SetFull):
+                    res[name] = sf.result_map(encs[k], sts[k], c.linearizable)
+                elif isinstance(c, jc.ReadAllInvokedAdds):
+                    res[name] = sf.read_all_invoked_adds(subs[k], encs[k])
+                else:
+                    res[name] = lin[name][k]
+            if None in res:                                 # a bare set-full, not a compose
+                out[k] = res[None]
+                continue
+            res["valid?"] = jc.merge_valid(r.get("valid?") for r in res.values() if isinstance(r, dict))
+            out[k] = res
+        return out
 
     def _check_batched(self, keys, subs):
         lin = self.inner

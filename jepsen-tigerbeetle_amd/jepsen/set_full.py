@@ -241,3 +241,136 @@ def check(history, linearizable=False, device=0):
     with Scan(enc, device) as s:
         st = s.run()
     return result_map(enc, st, linearizable)
+
+
+# ---------------------------------------------------------------------------------------------------- many keys, one device pass
+# The matrix bytes one keyed object may hold (the sum over its keys of reads x padded row): check_keys splits a larger independent
+# history into several calls of at most this much each, one key never split.  (Tests lower it to force the split.)
+KEYS_BUDGET_BYTES = 2 << 30
+
+
+def _matrix_bytes(enc):
+    return int(enc.R) * ((int(enc.wpr) + 3) // 4 * 4) * 4 if enc.E else 0
+
+
+class KeyedScan:
+    """tbc_setfull_keys_*: the compact reads of MANY keys (each an `Encoded`) resident in one object; `run()` scans all of them in one
+    fixed sequence of launches and returns each key's known / last-present / last-absent, in the order the encodings were given."""
+
+    def __init__(self, encs, device=0):
+        encs = list(encs)
+        self.Es = np.array([e.E for e in encs], np.uint32)
+        self.Rs = np.array([e.R for e in encs], np.uint32)
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate([np.asarray(x, dt) for x in parts] + [np.zeros(0, dt)]), dt)
+        n_exc = [int(e.exc_off[e.R]) for e in encs]
+        base = np.concatenate([[0], np.cumsum(n_exc, dtype=np.int64)]).astype(np.uint64)
+        a = dict(add_invoke=cat([e.add_invoke for e in encs], np.uint32), add_ok=cat([e.add_ok for e in encs], np.uint32),
+                 read_invoke=cat([e.read_invoke for e in encs], np.uint32), read_ok=cat([e.read_ok for e in encs], np.uint32),
+                 top=cat([e.top[:e.R] for e in encs], np.uint32),
+                 exc_off=cat([np.zeros(1, np.uint64)] + [np.asarray(e.exc_off[1:e.R + 1], np.uint64) + b for e, b in zip(encs, base)], np.uint64),
+                 exc=cat([e.exc[:n] for e, n in zip(encs, n_exc)], np.uint32))
+        self._keep = a = {k: (v if len(v) else np.zeros(1, v.dtype)) for k, v in a.items()}      # (a valid pointer for every array)
+        s = N.SetFullKeysIn()
+        s.n_keys, s.device = len(encs), device
+        s.n_elements, s.n_reads = _p(self.Es, C.c_uint32), _p(self.Rs, C.c_uint32)
+        for f in ("add_invoke", "add_ok", "read_invoke", "read_ok", "top", "exc"):
+            setattr(s, f, _p(a[f], C.c_uint32))
+        s.exc_off = _p(a["exc_off"], C.c_uint64)
+        self._h = C.c_void_p()
+        N.check_status(N.lib().tbc_setfull_keys_create(C.byref(s), C.byref(self._h)))
+
+    def run(self):
+        """-> ([per key {"known", "last_present", "last_absent"}], {"ns_scan", "bytes_scanned", "bytes_matrix"} of the whole object)"""
+        n = max(1, int(self.Es.sum()))
+        known, lp, la = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        o = N.SetFullKeysOut()
+        o.known, o.last_present, o.last_absent = _p(known, C.c_uint32), _p(lp, C.c_uint32), _p(la, C.c_uint32)
+        N.check_status(N.lib().tbc_setfull_keys_run(self._h, C.byref(o)))
+        cut = np.concatenate([[0], np.cumsum(self.Es, dtype=np.int64)])
+        per = [{"known": known[a:b], "last_present": lp[a:b], "last_absent": la[a:b]} for a, b in zip(cut[:-1], cut[1:])]
+        return per, {"ns_scan": o.ns_scan, "bytes_scanned": o.bytes_scanned, "bytes_matrix": o.bytes_matrix}
+
+    def close(self):
+        if self._h:
+            N.lib().tbc_setfull_keys_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def groups_within_budget(encs, budget=None):
+    """The keys (a list of (key, Encoded)) in order, cut into runs of at most `budget` matrix bytes each (a larger key alone)."""
+    budget = KEYS_BUDGET_BYTES if budget is None else budget
+    out, cur, size = [], [], 0
+    for k, e in encs:
+        b = _matrix_bytes(e)
+        if cur and size + b > budget:
+            out.append(cur)
+            cur, size = [], 0
+        cur.append((k, e))
+        size += b
+    if cur:
+        out.append(cur)
+    return out
+
+
+def scan_keys(encs, device=0):
+    """{k: Encoded} -> {k: the three indices per element}: one keyed object per budget group (csrc/set_full.hip tbc_setfull_keys_*)."""
+    out = {}
+    for grp in groups_within_budget(list(encs.items())):
+        with KeyedScan([e for _, e in grp], device) as ks:
+            per, _ = ks.run()
+        out.update({k: st for (k, _), st in zip(grp, per)})
+    return out
+
+
+def check_keys(histories, linearizable=False, device=0):
+    """{k: history} -> {k: set-full result}: each key encoded as `check` encodes it, all keys scanned in one device pass per budget
+    group; per key exactly what `check(history, linearizable)` gives."""
+    if not histories:
+        return {}
+    encs = {k: Encoded(h) for k, h in histories.items()}
+    sts = scan_keys(encs, device)
+    return {k: result_map(encs[k], sts[k], linearizable) for k in encs}
+
+
+# ---------------------------------------------------------------------------------------------------- read-all-invoked-adds
+def read_all_invoked_adds(history, enc=None):
+    """The reference's `read-all-invoked-adds` (workloads/set_full.clj:51-75): did every :ok read with :final? see every value some
+    :add was invoked with (crashed adds included)?  A nil value reads as empty; values read but never added do not count.
+    -> {"valid?": True} or {"valid?": False, "suspect-final-reads": [[index, missing values sorted], ...]} in history order,
+    index as the set-full result numbers ops (H.index over this history).
+
+    With `enc` (this history's `Encoded`), a final read the encoding holds is answered from its compact row -- the missing values are
+    the row's exceptions below top and the columns from top on that are not exceptions; any other final read (nil value, unmatched
+    invoke) directly.  No device work either way."""
+    hist = H.index(list(history))
+    invoked = {}                                        # value -> (its last add invocation, the value): the encoding's column order
+    for op in hist:
+        if op.get("f") == "add" and op.get("type") == "invoke":
+            invoked[_freeze(op.get("value"))] = (op["index"], op.get("value"))
+    finals = [op for op in hist if op.get("f") == "read" and op.get("type") == "ok" and op.get("final?")]
+    if not finals:
+        return {"valid?": True}
+    in_order = [v for _, v in sorted(invoked.values(), key=lambda iv: iv[0])]
+    row_of = {}
+    if enc is not None and len(enc.elements) == len(invoked) and all(_freeze(v) in invoked for v in enc.elements):
+        row_of = {int(i): r for r, i in enumerate(enc.read_ok)}
+    suspects = []
+    for op in finals:
+        r = row_of.get(op["index"])
+        if r is not None:
+            t = int(enc.top[r])
+            exc = np.asarray(enc.exc[int(enc.exc_off[r]):int(enc.exc_off[r + 1])], np.int64)
+            cols = np.union1d(exc[exc < t], np.setdiff1d(np.arange(t, enc.E, dtype=np.int64), exc))
+            missing = [enc.elements[int(c)] for c in cols]
+        else:
+            seen = {_freeze(x) for x in (op.get("value") or [])}
+            missing = [v for v in in_order if _freeze(v) not in seen]
+        if missing:
+            suspects.append([op["index"], _sorted(missing)])
+    return {"valid?": False, "suspect-final-reads": suspects} if suspects else {"valid?": True}
