@@ -650,7 +650,9 @@ typedef struct tbc_setfull_out {   /* arrays caller-allocated, n_elements each; 
 } tbc_setfull_out;
 
 typedef struct tbc_setfull tbc_setfull;
-/* inputs become resident in HBM (H2D here); run scans them; results copied into `out` */
+/* inputs become resident in HBM (H2D here); run scans them; results copied into `out`.  All three creates (this one, _create_rows,
+ * tbc_setfull_keys_create) check every rule of their input on the host before any device call: TBC_ERR_INVALID_ARG, the message names
+ * the entry point.  words_per_row may exceed ceil(n_elements / 32): the extra words of a row are ignored. */
 tbc_status tbc_setfull_create(const tbc_setfull_in* in, tbc_setfull** handle);
 
 /* The same with the reads in COMPACT form, the membership matrix built ON THE DEVICE (nothing of size reads x elements exists on

@@ -14,8 +14,8 @@
 // Layout: rows = reads in invocation order, words_per_row 32-bit words each; a wavefront's 64 lanes take 64
 // consecutive words of a row (256 B coalesced).  Two passes, no atomics:
 //   setfull_any_kernel      grid = word columns x chunks of rows: a thread ORs "present" and "absent" over FOUR word
-//                           columns (128 elements, 16 B loads) of ONE chunk, four rows in flight -- the streaming
-//                           pass, coalesced words written per thread (one column, eight rows when a row is not a multiple of 16 B);
+//                           columns (128 elements, 16 B loads) of ONE chunk, eight rows in flight -- the streaming
+//                           pass, coalesced words written per thread;
 //   setfull_resolve_kernel  one thread per word column: the chunk summaries say WHICH chunk holds each element's last
 //                           present / last absent / first present read; only those chunks are walked again, bit-parallel
 //                           (a 32-bit "still wanted" mask per direction), and the thread writes its own 32 results.
@@ -25,6 +25,13 @@
 // known: the first read (in invocation order) containing e need not be the first to complete, so the walk keeps
 // offering later rows' read_ok while they were invoked before the latest first-completion seen -- a window bounded by
 // the number of concurrent readers.
+//
+// One object and one set of kernels behind the three entry points: jepsen.independent splits the reference's set-full history into keys
+// (set_full.clj:155) and checks each on its own, so an object holds n_keys keys (tbc_setfull_keys_create), and a single key
+// (tbc_setfull_create_rows; tbc_setfull_create with the matrix given dense) is an object of one key.  At real sizes a key's matrix is a
+// few MB: one object per key would pay its fixed price (allocation, stream, copies, synchronisation) once per key while its scan
+// fills a sliver of the GPU.  Every launch goes through the plan table below; create = rows + prefix, run = any + resolve, whatever
+// n_keys is.
 #include <hip/hip_runtime.h>
 #include <vector>
 #include <algorithm>
@@ -42,71 +49,70 @@ constexpr uint32_t kSetFullRows = 2048;      // rows per chunk at most (their me
 constexpr uint32_t kWordCounters = 256;      // the words-loaded statistic: a wavefront adds to counter (its workgroup mod 256), 128 B apart -- thousands of
                                              // atomics on ONE address queue up in one L2 channel; the host adds the counters up
 
-// The kernel bodies below are written once, as inline functions of one key's arrays and of the workgroup's place in that key's grid
-// (bx, by, gx, gy where a kernel read blockIdx / gridDim): the single-key kernels (tbc_setfull_*) pass their own launch's, the keyed
-// ones (tbc_setfull_keys_*, further down) find their key in the plan table first.
-__device__ __forceinline__ void setfull_prefix_row(const uint32_t* add_invoke, const uint32_t* read_ok, uint32_t E, uint32_t R,
-                                                   uint32_t rows_per_chunk, uint32_t chunks, uint32_t* P, uint32_t* pmax, uint32_t r) {
-  if (r >= R) return;
-  const uint32_t t = read_ok[r];
-  uint32_t lo = 0, hi = E;                       // first element whose add was invoked at or after this read's completion
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (add_invoke[mid] < t) lo = mid + 1; else hi = mid; }
-  P[r] = lo;
-  atomicMax(&pmax[r / rows_per_chunk], lo);
-  atomicMin(&pmax[chunks + r / rows_per_chunk], lo);         // (the minima lie behind the maxima)
+// ---- the plan: every object holds n_keys keys (tbc_setfull_create / _create_rows: one) in ONE arena, and each pass is ONE launch over
+// the tiles of all keys.  The plan table (built on the host at create) gives each key its arrays' offsets, its chunking and the first tile
+// of each grid; a workgroup finds its key by a binary search over those first tiles (uniform across the workgroup: scalar loads) and
+// then works on that key alone.  Each key's pitch is a multiple of four words, so every 16 B load and store of the scan is aligned; the
+// bits at or above a key's E never count (the kernels mask them, and the padding words of a row are zeros).
+struct SfKeyPlan {                 // one key (device table; offsets in 32-bit words)
+  uint32_t E, R, WPR, PITCH, rows_per_chunk, chunks, elem_base, row_base;
+  uint32_t pmax_off, any_gy;
+  unsigned long long m_off, sum_off;
+};
+enum { kFirstRows = 0, kFirstPrefix, kFirstAny, kFirstResolve, kFirsts };   // first[g * (n_keys + 1) + k]: key k's first tile in grid g
+
+// the last key whose first tile (row) is <= b: keys with no tile share their successor's first and are never picked for a tile of theirs
+__device__ __forceinline__ uint32_t sf_find_key(const uint32_t* __restrict__ first, uint32_t n_keys, uint32_t b) {
+  uint32_t lo = 0, hi = n_keys;
+  while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (first[mid] <= b) lo = mid; else hi = mid; }
+  return lo;
 }
 
-__global__ __launch_bounds__(256) void setfull_prefix_kernel(const uint32_t* add_invoke, const uint32_t* read_ok, uint32_t E, uint32_t R,
-                                                             uint32_t rows_per_chunk, uint32_t chunks, uint32_t* P, uint32_t* pmax) {
-  setfull_prefix_row(add_invoke, read_ok, E, R, rows_per_chunk, chunks, P, pmax, blockIdx.x * 256u + threadIdx.x);
+__global__ __launch_bounds__(256) void setfull_prefix_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
+                                                             const uint32_t* add_invoke, const uint32_t* read_ok, uint32_t* P, uint32_t* pmax) {
+  const uint32_t* f = first + kFirstPrefix * (n_keys + 1u);
+  const uint32_t k = sf_find_key(f, n_keys, blockIdx.x);
+  const SfKeyPlan& p = plan[k];
+  const uint32_t r = (blockIdx.x - f[k]) * 256u + threadIdx.x;
+  if (r >= p.R) return;
+  const uint32_t t = read_ok[p.row_base + r];
+  uint32_t lo = 0, hi = p.E;                     // first element whose add was invoked at or after this read's completion
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (add_invoke[p.elem_base + mid] < t) lo = mid + 1; else hi = mid; }
+  P[p.row_base + r] = lo;
+  atomicMax(&pmax[p.pmax_off + r / p.rows_per_chunk], lo);
+  atomicMin(&pmax[p.pmax_off + p.chunks + r / p.rows_per_chunk], lo);         // (the minima lie behind the maxima)
 }
 
 __device__ __forceinline__ uint32_t prefix_mask(uint32_t p, uint32_t w) {       // bits of word w below element number p
   return p >= 32u * w + 32u ? 0xFFFFFFFFu : (p <= 32u * w ? 0u : (1u << (p - 32u * w)) - 1u);
 }
 
-// ---- the membership matrix from the reads' compact form (tbc_setfull_create_rows): one workgroup per read writes its row --
-// ones below top[r], zeros above (a coalesced stream: the matrix is written once, at HBM's write rate) -- and then flips the
-// listed exceptions in it.  No row ever exists on the host.
-__device__ __forceinline__ void setfull_build_row(uint32_t* __restrict__ row, uint32_t t, unsigned long long e0, unsigned long long e1,
-                                                  const uint32_t* __restrict__ exc, uint32_t WPR) {
-  for (uint32_t w = threadIdx.x; w < WPR; w += 256u) row[w] = prefix_mask(t, w);
-  __syncthreads();
-  for (unsigned long long i = e0 + threadIdx.x; i < e1; i += 256u) {
-    const uint32_t e = exc[i];
-    atomicXor(&row[e >> 5], 1u << (e & 31u));
+// ---- the membership matrix from the reads' compact form (tbc_setfull_create_rows, tbc_setfull_keys_create): one workgroup per read
+// writes its row -- ones below top[r], zeros above (a coalesced stream: the matrix is written once, at HBM's write rate) -- and then
+// flips the listed exceptions in it.  No row ever exists on the host.  The whole pitch is written (zeros past E: top <= E), so no word
+// of the arena the scan loads is left unset.
+__global__ __launch_bounds__(256) void setfull_rows_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
+                                                           uint32_t R_all, const uint32_t* __restrict__ top, const unsigned long long* __restrict__ exc_off,
+                                                           const uint32_t* __restrict__ exc, uint32_t* __restrict__ M) {
+  for (uint32_t r = blockIdx.x; r < R_all; r += gridDim.x) {
+    const SfKeyPlan& p = plan[sf_find_key(first + kFirstRows * (n_keys + 1u), n_keys, r)];
+    uint32_t* __restrict__ row = M + p.m_off + (uint64_t)(r - p.row_base) * p.PITCH;
+    const uint32_t t = top[r];
+    for (uint32_t w = threadIdx.x; w < p.PITCH; w += 256u) row[w] = prefix_mask(t, w);
+    __syncthreads();
+    for (unsigned long long i = exc_off[r] + threadIdx.x; i < exc_off[r + 1]; i += 256u) {
+      const uint32_t e = exc[i];
+      atomicXor(&row[e >> 5], 1u << (e & 31u));
+    }
+    __syncthreads();
   }
-  __syncthreads();
 }
-
-__global__ __launch_bounds__(256) void setfull_rows_kernel(const uint32_t* __restrict__ top, const unsigned long long* __restrict__ exc_off,
-                                                           const uint32_t* __restrict__ exc, uint32_t R, uint32_t WPR, uint32_t PITCH, uint32_t* __restrict__ M) {
-  for (uint32_t r = blockIdx.x; r < R; r += gridDim.x) setfull_build_row(M + (uint64_t)r * PITCH, top[r], exc_off[r], exc_off[r + 1], exc, WPR);
-}
-
-// A workgroup's place in its key's grid: the launch's own (single key) ...
-struct LaunchGrid {
-  __device__ uint32_t bx() const { return blockIdx.x; }
-  __device__ uint32_t by() const { return blockIdx.y; }
-  __device__ uint32_t gx() const { return gridDim.x; }
-  __device__ uint32_t gy() const { return gridDim.y; }
-  __device__ uint32_t ctr() const { return blockIdx.x + blockIdx.y * gridDim.x; }     // which words-loaded counter
-};
-// ... or one found in the plan table (keyed: one flat grid over all keys' tiles)
-struct KeyGrid {
-  uint32_t x, y, nx, ny, flat;
-  __device__ uint32_t bx() const { return x; }
-  __device__ uint32_t by() const { return y; }
-  __device__ uint32_t gx() const { return nx; }
-  __device__ uint32_t gy() const { return ny; }
-  __device__ uint32_t ctr() const { return flat; }
-};
 
 // ---- pass 1: per (word column, chunk of rows) -- is any bit of the column present / absent in the chunk?  The streaming
-// pass.  VEC = 4: a lane takes FOUR consecutive word columns (16 B loads, a wavefront 1 KB of a row; rows of a multiple of four
-// words), VEC = 1: one column; eight rows are requested, then folded.  Nothing a load returns decides whether the next is issued (a
-// chunk is at most 2,048 rows: stopping at a saturated column saved nothing on set-full's matrices, where an element is absent before
-// its add and present after, and cost a round trip every eight rows); no atomics.  Three kinds of tile (256 VEC columns x a chunk):
+// pass.  A lane takes FOUR consecutive word columns (VEC: 16 B loads, a wavefront 1 KB of a row); eight rows are requested, then
+// folded.  Nothing a load returns decides whether the next is issued (a chunk is at most 2,048 rows: stopping at a saturated column
+// saved nothing on set-full's matrices, where an element is absent before its add and present after, and cost a round trip every
+// eight rows); no atomics.  Three kinds of tile (256 VEC columns x a chunk):
 // below the diagonal (return), on it (the general path: the chunk's row metadata in LDS, a mask per row and word), above it (the lean
 // path: every column counts in every row).
 // Round 6 (profiles/r06_setfull_*, scripts/exp/strip_read.hip = this access pattern, bare: 6.1 TB/s a rectangle, 5.3 the triangle):
@@ -119,27 +125,32 @@ struct KeyGrid {
 // workgroups on eight XCDs write -- 43 us of this kernel's 150 (scripts/exp/strip_read.hip: the bare triangle 0.114 ms, with the
 // column-major stores 0.157, with these 0.117).  Pass 2 reads a column's chunks as 64 words of 64 lines now, and is given its
 // columns so that the workgroups of one XCD share those lines (setfull_resolve_kernel).
-template <int VEC>
+constexpr int VEC = 4;
 __device__ __forceinline__ void store_summary(uint32_t* __restrict__ any_p, uint32_t* __restrict__ any_a, uint32_t SP, uint32_t c, uint32_t w0,
                                               const uint32_t (&pa)[VEC], const uint32_t (&aa)[VEC]) {
   const uint64_t at = (uint64_t)c * SP + w0;
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<uint4*>(any_p + at) = make_uint4(pa[0], pa[1], pa[2], pa[3]);
-    *reinterpret_cast<uint4*>(any_a + at) = make_uint4(aa[0], aa[1], aa[2], aa[3]);
-  } else {
-#pragma unroll
-    for (int v = 0; v < VEC; v++) { any_p[at + (uint32_t)v] = pa[v]; any_a[at + (uint32_t)v] = aa[v]; }
-  }
+  *reinterpret_cast<uint4*>(any_p + at) = make_uint4(pa[0], pa[1], pa[2], pa[3]);
+  *reinterpret_cast<uint4*>(any_a + at) = make_uint4(aa[0], aa[1], aa[2], aa[3]);
 }
 
-template <int VEC, class Grid>
-__device__ __forceinline__ void setfull_any_tile(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
-                                                 const uint32_t* __restrict__ pmax, uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH,
-                                                 uint32_t rows_per_chunk, uint32_t SP, uint32_t* __restrict__ any_p,
-                                                 uint32_t* __restrict__ any_a, unsigned long long* words_loaded,
-                                                 const Grid& g) {
-  constexpr uint32_t U = 8u;                            // rows in flight per lane (16 B each at VEC = 4)
-  // grid = (chunks, column blocks), the CHUNK in x.  Workgroup b runs on XCD b % 8 (observed, MI355X_MICROARCH.md "Workgroup dispatch"),
+__global__ __launch_bounds__(256) void setfull_any_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
+                                                          const uint32_t* __restrict__ M_all, const uint32_t* __restrict__ P_all,
+                                                          const uint32_t* __restrict__ pmax_all, uint32_t* __restrict__ any_p_all,
+                                                          uint32_t* __restrict__ any_a_all, unsigned long long* words_loaded) {
+  const uint32_t* f = first + kFirstAny * (n_keys + 1u);
+  const uint32_t key = sf_find_key(f, n_keys, blockIdx.x);
+  const SfKeyPlan& p = plan[key];
+  const uint32_t tile = blockIdx.x - f[key];
+  // the key's grid = (chunks, column blocks), the CHUNK in x: tile t is (t % chunks, t / chunks), the order a 2-D launch hands them out in
+  const uint32_t gx = p.chunks, gy = p.any_gy, bx = tile % gx, by = tile / gx;
+  const uint32_t* __restrict__ M = M_all + p.m_off;
+  const uint32_t* __restrict__ P = P_all + p.row_base;
+  const uint32_t* __restrict__ pmax = pmax_all + p.pmax_off;
+  uint32_t* __restrict__ any_p = any_p_all + p.sum_off;
+  uint32_t* __restrict__ any_a = any_a_all + p.sum_off;
+  const uint32_t E = p.E, R = p.R, WPR = p.WPR, PITCH = p.PITCH, rows_per_chunk = p.rows_per_chunk, SP = p.PITCH;
+  constexpr uint32_t U = 8u;                            // rows in flight per lane (16 B each)
+  // Workgroup b runs on XCD b % 8 (observed, MI355X_MICROARCH.md "Workgroup dispatch"),
   // and the work is a triangle: column block j counts in the chunks above j / n of the rows only.  With the column block in x (rounds
   // 3 - 5: eight of them for 262,144 elements, i.e. column block j WAS XCD j) XCD 0 streamed 256 chunks and XCD 7 32 -- the kernel
   // lasted as long as XCD 0's 22 % of the matrix through one XCD's fabric port.  With the chunk in x every XCD gets every eighth
@@ -147,8 +158,8 @@ __device__ __forceinline__ void setfull_any_tile(const uint32_t* __restrict__ M,
   // The order the workgroups are handed out in (x fastest, then y): the LAST column block first, and in every column block the chunks
   // from its diagonal on -- the tiles on the diagonal decide per row (the general path below: the longest workgroups) and start first,
   // the tiles below the diagonal, which return at once, come last.
-  const uint32_t cb = g.gy() - 1u - g.by();
-  const uint32_t c = (g.bx() + (uint32_t)((uint64_t)cb * g.gx() / g.gy())) % g.gx();
+  const uint32_t cb = gy - 1u - by;
+  const uint32_t c = (bx + (uint32_t)((uint64_t)cb * gx / gy)) % gx;
   const uint32_t w0 = (cb * 256u + threadIdx.x) * (uint32_t)VEC;
   uint32_t loaded = 0;
   __shared__ uint32_t s_P[kSetFullRows];
@@ -161,7 +172,7 @@ __device__ __forceinline__ void setfull_any_tile(const uint32_t* __restrict__ M,
   // a word -- the fold of the general path below costs ~50 vector instructions a row and wavefront, 43 us of a SIMD's time per launch
   // beside 88 us of streaming (scripts/exp/strip_read.hip: this very access pattern, bare, reads at 6.1 TB/s, 6.7 non-temporal).
   const uint32_t tile_hi = 32u * ((cb + 1u) * 256u * (uint32_t)VEC);
-  if (pmax[g.gx() + c] >= (tile_hi < E ? tile_hi : E)) {
+  if (pmax[gx + c] >= (tile_hi < E ? tile_hi : E)) {
     if (w0 < WPR) {
       typedef uint32_t wvec __attribute__((ext_vector_type(VEC)));
       uint32_t po[VEC], na[VEC];
@@ -192,11 +203,11 @@ __device__ __forceinline__ void setfull_any_tile(const uint32_t* __restrict__ M,
         pa[v] = po[v] & full; aa[v] = ~na[v] & full;
         loaded += full ? r1 - r0 : 0u;
       }
-      store_summary<VEC>(any_p, any_a, SP, c, w0, pa, aa);
+      store_summary(any_p, any_a, SP, c, w0, pa, aa);
     }
     unsigned long long tot = loaded;
     for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
-    if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (g.ctr() % kWordCounters), tot);
+    if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (blockIdx.x % kWordCounters), tot);
     return;
   }
   for (uint32_t i = threadIdx.x; i < r1 - r0; i += 256u) s_P[i] = P[r0 + i];
@@ -225,12 +236,8 @@ __device__ __forceinline__ void setfull_any_tile(const uint32_t* __restrict__ M,
           // are outstanding, and it then waits for ALL of them (s_waitcnt vmcnt(0)) before the fold: the rows requested ahead would
           // be waited for at once, i.e. nothing would be ahead
           const uint32_t* src = M + (need ? (uint64_t)r * PITCH : 0ull) + w0;
-          if constexpr (VEC == 4) {
-            const uint4 x = *reinterpret_cast<const uint4*>(src);
-            wd[q][0] = x.x; wd[q][1] = x.y; wd[q][2] = x.z; wd[q][3] = x.w;
-          } else {
-            wd[q][0] = *src;
-          }
+          const uint4 x = *reinterpret_cast<const uint4*>(src);
+          wd[q][0] = x.x; wd[q][1] = x.y; wd[q][2] = x.z; wd[q][3] = x.w;
         }
       };
       // ... and folded into the column's two words
@@ -254,19 +261,11 @@ __device__ __forceinline__ void setfull_any_tile(const uint32_t* __restrict__ M,
         fold(wa, pra);
       }
     }
-    store_summary<VEC>(any_p, any_a, SP, c, w0, pa, aa);
+    store_summary(any_p, any_a, SP, c, w0, pa, aa);
   }
   unsigned long long tot = loaded;
   for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
-  if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (g.ctr() % kWordCounters), tot);
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void setfull_any_kernel(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
-                                                          const uint32_t* __restrict__ pmax, uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH,
-                                                          uint32_t rows_per_chunk, uint32_t SP, uint32_t* __restrict__ any_p,
-                                                          uint32_t* __restrict__ any_a, unsigned long long* words_loaded) {
-  setfull_any_tile<VEC>(M, P, pmax, E, R, WPR, PITCH, rows_per_chunk, SP, any_p, any_a, words_loaded, LaunchGrid{});
+  if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (blockIdx.x % kWordCounters), tot);
 }
 
 // ---- pass 2: one WAVEFRONT per word column resolves its 32 elements.  The chunk summaries say WHICH chunk holds an
@@ -339,20 +338,40 @@ __device__ __forceinline__ uint32_t setfull_last_in_chunk(const uint32_t* __rest
 }
 
 #ifndef SF_RESOLVE_MIN_WAVES
-#define SF_RESOLVE_MIN_WAVES 8          /* 41 registers: every one of the 8,192 wavefronts of 262,144 elements resident at once */
+#define SF_RESOLVE_MIN_WAVES 8          /* 43 registers: every one of the 8,192 wavefronts of 262,144 elements resident at once */
 #endif
-template <class Grid>
-__device__ __forceinline__ void setfull_resolve_columns(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
-                                                      const uint32_t* __restrict__ read_invoke, const uint32_t* __restrict__ read_ok,
-                                                      const uint32_t* __restrict__ any_p, const uint32_t* __restrict__ any_a,
-                                                      uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH, uint32_t rows_per_chunk, uint32_t chunks, uint32_t SP,
-                                                      const uint32_t* __restrict__ add_ok, uint32_t* lp, uint32_t* la, uint32_t* known,
-                                                      unsigned long long* words_loaded, const Grid& g) {
+__global__ __launch_bounds__(256, SF_RESOLVE_MIN_WAVES) void setfull_resolve_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first,
+                                                              uint32_t n_keys, const uint32_t* __restrict__ M_all, const uint32_t* __restrict__ P_all,
+                                                              const uint32_t* __restrict__ read_invoke_all, const uint32_t* __restrict__ read_ok_all,
+                                                              const uint32_t* __restrict__ any_p_all, const uint32_t* __restrict__ any_a_all,
+                                                              const uint32_t* __restrict__ add_ok_all, uint32_t* lp_all, uint32_t* la_all, uint32_t* known_all,
+                                                              unsigned long long* words_loaded) {
+  const uint32_t* f = first + kFirstResolve * (n_keys + 1u);
+  const uint32_t key = sf_find_key(f, n_keys, blockIdx.x);
+  const SfKeyPlan& p = plan[key];
+  const uint32_t nb = (p.WPR + 3u) / 4u, bx = blockIdx.x - f[key];
+  // (a key of a multiple of eight workgroups starts on a multiple of eight -- the XCD-contiguous order below holds -- and the tiles
+  // skipped to get there belong to the key before, past its last workgroup)
+  if (bx >= nb) return;
+  // the results go straight into the caller's layout (key after key, n_elements each)
+  const uint32_t* __restrict__ add_ok = add_ok_all + p.elem_base;
+  uint32_t* lp = lp_all + p.elem_base; uint32_t* la = la_all + p.elem_base; uint32_t* known = known_all + p.elem_base;
+  const uint32_t E = p.E, R = p.R, WPR = p.WPR, PITCH = p.PITCH, rows_per_chunk = p.rows_per_chunk, chunks = p.chunks, SP = p.PITCH;
   const uint32_t lane = threadIdx.x & 63u;
+  if (R == 0u) {            // a key without reads: nothing was seen, known = the add's ack
+    const uint32_t e = 32u * (bx * 4u + (threadIdx.x >> 6)) + lane;
+    if (lane < 32u && e < E) { lp[e] = kNoneU; la[e] = kNoneU; known[e] = add_ok[e]; }
+    return;
+  }
+  const uint32_t* __restrict__ M = M_all + p.m_off;
+  const uint32_t* __restrict__ P = P_all + p.row_base;
+  const uint32_t* __restrict__ read_invoke = read_invoke_all + p.row_base;
+  const uint32_t* __restrict__ read_ok = read_ok_all + p.row_base;
+  const uint32_t* __restrict__ any_p = any_p_all + p.sum_off;
+  const uint32_t* __restrict__ any_a = any_a_all + p.sum_off;
   // workgroup b runs on XCD b % 8 (observed): the eight XCDs take eight contiguous ranges of the columns, so that the lines four
   // neighbouring workgroups read 16 B each of -- the summaries' and the matrix rows' -- are fetched into ONE L2 instead of eight
-  const uint32_t nb = g.gx();
-  const uint32_t bb = nb % 8u == 0u ? (g.bx() % 8u) * (nb / 8u) + g.bx() / 8u : g.bx();
+  const uint32_t bb = nb % 8u == 0u ? (bx % 8u) * (nb / 8u) + bx / 8u : bx;
   const uint32_t wv_ = threadIdx.x >> 6;
   const uint32_t w = __builtin_amdgcn_readfirstlane(bb * 4u + wv_);
   uint32_t loaded = 0;
@@ -482,34 +501,16 @@ __device__ __forceinline__ void setfull_resolve_columns(const uint32_t* __restri
         seen |= any_hits;
       }
     }
-    if (lane < 32u) {                                           // (the arrays are padded to whole word columns)
-      const uint32_t e = 32u * w + lane;
+    const uint32_t e = 32u * w + lane;
+    if (lane < 32u && e < E) {
       lp[e] = res_p ? res_p - 1u : kNoneU;
       la[e] = res_a ? res_a - 1u : kNoneU;
-      known[e] = min(best, e < E ? add_ok[e] : kNoneU);
+      known[e] = min(best, add_ok[e]);
     }
   }
   unsigned long long tot = loaded;
   for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
-  if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (g.ctr() % kWordCounters), tot);
-}
-
-__global__ __launch_bounds__(256, SF_RESOLVE_MIN_WAVES) void setfull_resolve_kernel(const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
-                                                              const uint32_t* __restrict__ read_invoke, const uint32_t* __restrict__ read_ok,
-                                                              const uint32_t* __restrict__ any_p, const uint32_t* __restrict__ any_a,
-                                                              uint32_t E, uint32_t R, uint32_t WPR, uint32_t PITCH, uint32_t rows_per_chunk, uint32_t chunks, uint32_t SP,
-                                                              const uint32_t* __restrict__ add_ok, uint32_t* lp, uint32_t* la, uint32_t* known,
-                                                              unsigned long long* words_loaded) {
-  setfull_resolve_columns(M, P, read_invoke, read_ok, any_p, any_a, E, R, WPR, PITCH, rows_per_chunk, chunks, SP, add_ok, lp, la, known, words_loaded,
-                          LaunchGrid{});
-}
-
-__global__ __launch_bounds__(256) void setfull_finish_kernel(uint32_t* lp1, uint32_t* la1, uint32_t* known, const uint32_t* add_ok, uint32_t E) {
-  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
-  if (e >= E) return;
-  lp1[e] = lp1[e] ? lp1[e] - 1u : kNoneU;
-  la1[e] = la1[e] ? la1[e] - 1u : kNoneU;
-  known[e] = min(known[e], add_ok[e]);
+  if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(words_loaded + 16u * (blockIdx.x % kWordCounters), tot);
 }
 
 #define SF_TRY(expr)                                                                         \
@@ -521,523 +522,309 @@ __global__ __launch_bounds__(256) void setfull_finish_kernel(uint32_t* lp1, uint
     }                                                                                        \
   } while (0)
 
-}  // namespace
-
-struct tbc_setfull {
-  int device = 0;
-  uint32_t E = 0, R = 0, WPR = 0, PITCH = 0, chunks = 1, rows_per_chunk = 1, chp = 4;       // chp: words per chunk of the summaries (words_per_row rounded up to four)
-  uint32_t *d_add_invoke = nullptr, *d_add_ok = nullptr, *d_read_invoke = nullptr, *d_read_ok = nullptr, *d_M = nullptr;
-  uint32_t *d_P = nullptr, *d_pmax = nullptr, *d_lp = nullptr, *d_la = nullptr, *d_known = nullptr, *d_anyp = nullptr, *d_anya = nullptr;
-  unsigned long long* d_words = nullptr;
-  void* arena = nullptr;            // ONE allocation holds every array above (and create_rows' compact reads): one hipMalloc, one hipFree
-  unsigned long long h_words[kWordCounters * 16] = {};
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~tbc_setfull() {
-    if (arena) (void)hipFree(arena);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-static tbc_status setfull_create_impl(const tbc_setfull_in* in, tbc_setfull* S, const tbc_setfull_rows* rows = nullptr) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || (int)in->device >= ndev) {
-    set_error("no usable HIP device; libtbcheck has no CPU fallback");
-    return TBC_ERR_NO_DEVICE;
-  }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, (int)in->device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-    set_error("device %u is not a gfx950 (MI355X) device", in->device);
-    return TBC_ERR_NO_DEVICE;
-  }
-  S->device = (int)in->device; S->E = in->n_elements; S->R = in->n_reads; S->WPR = in->words_per_row;
-  if ((uint64_t)S->WPR * 32 < S->E) { set_error("tbc_setfull: words_per_row too small for n_elements"); return TBC_ERR_INVALID_ARG; }
-  if (rows) {          // the compact form: every offset and element number is checked here, the kernel trusts them
-    if (rows->exc_off[0] != 0) { set_error("tbc_setfull_create_rows: exc_off[0] must be 0"); return TBC_ERR_INVALID_ARG; }
-    for (uint32_t r = 0; r < S->R; r++) {
-      if (rows->top[r] > S->E || rows->exc_off[r + 1] < rows->exc_off[r]) { set_error("tbc_setfull_create_rows: read %u: bad top / exc_off", r); return TBC_ERR_INVALID_ARG; }
-    }
-    const uint64_t ne = rows->exc_off[S->R];
-    for (uint64_t i = 0; i < ne; i++) if (rows->exc[i] >= S->E) { set_error("tbc_setfull_create_rows: exception %llu names element %u of %u", (unsigned long long)i, rows->exc[i], S->E); return TBC_ERR_INVALID_ARG; }
-    // each element at most once per read: the kernel FLIPS the listed bits, a duplicate would flip one back silently.  A strictly ascending
-    // list (what the in-repo encoders write) is seen to be duplicate-free in one pass; a list in any other order is sorted aside and looked
-    // at again -- round 5 refused every list that was not ascending, which a caller of the earlier header (any order, no duplicates) had
-    // no way to know at the same TBC_ABI_VERSION
-    std::vector<uint32_t> tmp;
-    for (uint32_t r = 0; r < S->R; r++) {
-      bool ascending = true;
-      for (uint64_t i = rows->exc_off[r] + 1; i < rows->exc_off[r + 1] && ascending; i++) ascending = rows->exc[i] > rows->exc[i - 1];
-      if (ascending) continue;
-      tmp.assign(rows->exc + rows->exc_off[r], rows->exc + rows->exc_off[r + 1]);
-      std::sort(tmp.begin(), tmp.end());
-      for (size_t i = 1; i < tmp.size(); i++)
-        if (tmp[i] == tmp[i - 1]) { set_error("tbc_setfull_create_rows: read %u lists element %u twice (each element at most once per read)", r, tmp[i]); return TBC_ERR_INVALID_ARG; }
-    }
-  }
-  // the prefix search per row and "the latest row" both rest on the documented orders
-  for (uint32_t e = 1; e < S->E; e++) if (in->add_invoke[e] <= in->add_invoke[e - 1]) { set_error("tbc_setfull: add_invoke must be strictly ascending (element %u)", e); return TBC_ERR_INVALID_ARG; }
-  for (uint32_t r = 1; r < S->R; r++) if (in->read_invoke[r] <= in->read_invoke[r - 1]) { set_error("tbc_setfull: read_invoke must be strictly ascending (read %u)", r); return TBC_ERR_INVALID_ARG; }
-  SF_TRY(hipSetDevice(S->device));
-  S->PITCH = std::max(1u, S->WPR);
-  // (PITCH: the words between two rows in device memory.  A pitch padded off the power of two was measured -- 16 .. 1,088 words: the
-  // same scan within 3 % either way, profiles/r06_setfull_pad_scan.txt -- so it is words_per_row)
-  // enough chunks to fill the GPU with wavefronts that each stream a good stretch of rows
-  const uint32_t col_blocks = (S->WPR + 255) / 256;
-  uint32_t chunks = std::max(1u, std::min(256u, 8192u / std::max(1u, col_blocks)));     // short chunks: what pass 2 walks again is one chunk
-  while (chunks > 1 && S->R / chunks < 64) chunks >>= 1;
-  while ((S->R + chunks - 1) / chunks > kSetFullRows) chunks <<= 1;
-  S->chunks = chunks; S->rows_per_chunk = std::max(1u, (S->R + chunks - 1) / chunks);
-  const size_t e4 = (size_t)std::max(1u, S->E) * 4, r4 = (size_t)std::max(1u, S->R) * 4, m4 = std::max<size_t>(4, (size_t)S->R * S->PITCH * 4);
-  const size_t ew = (size_t)std::max(1u, S->WPR) * 32 * 4;       // per-element outputs padded to whole words
-  S->chp = (std::max(1u, S->WPR) + 3u) / 4u * 4u;
-  const size_t any4 = (size_t)S->chp * S->chunks * 4;
-  // Everything in ONE allocation (round 6: fourteen hipMalloc + three more for the compact reads, and as many hipFree -- each of which
-  // waits for the device -- were most of a caller's 5 ms around a 0.16 ms scan; the reference checks one history per call site,
-  // set_full.clj:157, so create + run + destroy IS its time to verdict)
-  const uint64_t ne = (rows && S->R) ? rows->exc_off[S->R] : 0;
-  size_t cursor = 0;
-  const auto take = [&](size_t bytes) { const size_t at = cursor; cursor += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_M = take(m4), o_ai = take(e4), o_ao = take(e4), o_ri = take(r4), o_ro = take(r4), o_P = take(r4), o_pm = take((size_t)S->chunks * 8),
-               o_lp = take(ew), o_la = take(ew), o_kn = take(ew), o_w = take((size_t)kWordCounters * 128), o_ap = take(any4), o_aa = take(any4),
-               o_top = take(rows ? r4 : 0), o_off = take(rows ? ((size_t)S->R + 1) * 8 : 0), o_exc = take(rows ? std::max<size_t>(4, ne * 4) : 0);
-  SF_TRY(hipMalloc(&S->arena, std::max<size_t>(cursor, 256)));
-  char* const A0 = static_cast<char*>(S->arena);
-  S->d_M = (uint32_t*)(A0 + o_M); S->d_add_invoke = (uint32_t*)(A0 + o_ai); S->d_add_ok = (uint32_t*)(A0 + o_ao);
-  S->d_read_invoke = (uint32_t*)(A0 + o_ri); S->d_read_ok = (uint32_t*)(A0 + o_ro); S->d_P = (uint32_t*)(A0 + o_P);
-  S->d_pmax = (uint32_t*)(A0 + o_pm);                              // the chunks' greatest prefixes, then their least
-  S->d_lp = (uint32_t*)(A0 + o_lp); S->d_la = (uint32_t*)(A0 + o_la); S->d_known = (uint32_t*)(A0 + o_kn);
-  S->d_words = (unsigned long long*)(A0 + o_w); S->d_anyp = (uint32_t*)(A0 + o_ap); S->d_anya = (uint32_t*)(A0 + o_aa);
-  SF_TRY(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
-  SF_TRY(hipEventCreate(&S->ev0)); SF_TRY(hipEventCreate(&S->ev1));
-  if (S->E) {
-    SF_TRY(hipMemcpyAsync(S->d_add_invoke, in->add_invoke, (size_t)S->E * 4, hipMemcpyHostToDevice, S->stream));
-    SF_TRY(hipMemcpyAsync(S->d_add_ok, in->add_ok, (size_t)S->E * 4, hipMemcpyHostToDevice, S->stream));
-  }
-  if (S->R) {
-    SF_TRY(hipMemcpyAsync(S->d_read_invoke, in->read_invoke, (size_t)S->R * 4, hipMemcpyHostToDevice, S->stream));
-    SF_TRY(hipMemcpyAsync(S->d_read_ok, in->read_ok, (size_t)S->R * 4, hipMemcpyHostToDevice, S->stream));
-    if (!rows && S->WPR) SF_TRY(hipMemcpy2DAsync(S->d_M, (size_t)S->PITCH * 4, in->present, (size_t)S->WPR * 4, (size_t)S->WPR * 4, S->R, hipMemcpyHostToDevice, S->stream));
-  }
-  if (rows && S->R) {
-    uint32_t* const d_top = (uint32_t*)(A0 + o_top); uint32_t* const d_exc = (uint32_t*)(A0 + o_exc);
-    unsigned long long* const d_off = (unsigned long long*)(A0 + o_off);
-    hipError_t e = hipMemcpyAsync(d_top, rows->top, (size_t)S->R * 4, hipMemcpyHostToDevice, S->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, rows->exc_off, ((size_t)S->R + 1) * 8, hipMemcpyHostToDevice, S->stream);
-    if (e == hipSuccess && ne) e = hipMemcpyAsync(d_exc, rows->exc, ne * 4, hipMemcpyHostToDevice, S->stream);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(setfull_rows_kernel, dim3(std::min<uint32_t>(S->R, 16384u)), dim3(256), 0, S->stream, d_top, d_off, d_exc, S->R, std::max(1u, S->WPR), S->PITCH, S->d_M);
-      e = hipGetLastError();
-    }
-    if (e != hipSuccess) { set_error("tbc_setfull_create_rows: building the matrix failed: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? TBC_ERR_OOM : TBC_ERR_HIP; }
-  }
-  // p[r] (how many elements had been invoked when read r completed) and the chunks' maxima depend on the inputs only
-  SF_TRY(hipMemsetAsync(S->d_pmax, 0, (size_t)S->chunks * 4, S->stream));
-  SF_TRY(hipMemsetAsync(S->d_pmax + S->chunks, 0xFF, (size_t)S->chunks * 4, S->stream));
-  SF_TRY(hipMemsetAsync(S->d_anyp, 0, any4, S->stream)); SF_TRY(hipMemsetAsync(S->d_anya, 0, any4, S->stream));      // (the workgroups below the diagonal never write theirs)
-  if (S->R && S->E)
-    hipLaunchKernelGGL(setfull_prefix_kernel, dim3((S->R + 255) / 256), dim3(256), 0, S->stream, S->d_add_invoke, S->d_read_ok, S->E, S->R,
-                       S->rows_per_chunk, S->chunks, S->d_P, S->d_pmax);
-  SF_TRY(hipGetLastError());
-  SF_TRY(hipStreamSynchronize(S->stream));
-  return TBC_OK;
-}
-
-extern "C" {
-
-tbc_status tbc_setfull_create(const tbc_setfull_in* in, tbc_setfull** handle) {
-  if (!in || !handle || (in->n_elements && (!in->add_invoke || !in->add_ok)) ||
-      (in->n_reads && (!in->read_invoke || !in->read_ok || !in->present))) {
-    set_error("tbc_setfull_create: null argument");
-    return TBC_ERR_INVALID_ARG;
-  }
-  tbc_setfull* S = new (std::nothrow) tbc_setfull();
-  if (!S) return TBC_ERR_OOM;
-  const tbc_status st = setfull_create_impl(in, S);
-  if (st != TBC_OK) { delete S; return st; }
-  *handle = S;
-  return TBC_OK;
-}
-
-tbc_status tbc_setfull_run(tbc_setfull* S, tbc_setfull_out* out) {
-  if (!S || !out || (S->E && (!out->known || !out->last_present || !out->last_absent))) { set_error("tbc_setfull_run: null argument"); return TBC_ERR_INVALID_ARG; }
-  SF_TRY(hipSetDevice(S->device));
-  hipStream_t s = S->stream;
-  const size_t ew = (size_t)std::max(1u, S->WPR) * 32 * 4;
-  SF_TRY(hipMemsetAsync(S->d_lp, 0, ew, s)); SF_TRY(hipMemsetAsync(S->d_la, 0, ew, s));
-  SF_TRY(hipMemsetAsync(S->d_known, 0xFF, ew, s));
-  SF_TRY(hipMemsetAsync(S->d_words, 0, (size_t)kWordCounters * 128, s));
-  SF_TRY(hipEventRecord(S->ev0, s));
-  if (S->R && S->E) {
-    if (S->WPR % 4u == 0u)      // (hipMalloc'ed arrays, rows of a multiple of four words: every 16 B load and store is aligned)
-      hipLaunchKernelGGL(setfull_any_kernel<4>, dim3(S->chunks, (S->WPR / 4u + 255) / 256), dim3(256), 0, s, S->d_M, S->d_P, S->d_pmax, S->E, S->R, S->WPR, S->PITCH,
-                         S->rows_per_chunk, S->chp, S->d_anyp, S->d_anya, S->d_words);
-    else
-      hipLaunchKernelGGL(setfull_any_kernel<1>, dim3(S->chunks, (S->WPR + 255) / 256), dim3(256), 0, s, S->d_M, S->d_P, S->d_pmax, S->E, S->R, S->WPR, S->PITCH,
-                         S->rows_per_chunk, S->chp, S->d_anyp, S->d_anya, S->d_words);
-    hipLaunchKernelGGL(setfull_resolve_kernel, dim3((S->WPR + 3) / 4), dim3(256), 0, s, S->d_M, S->d_P, S->d_read_invoke, S->d_read_ok, S->d_anyp,
-                       S->d_anya, S->E, S->R, S->WPR, S->PITCH, S->rows_per_chunk, S->chunks, S->chp, S->d_add_ok, S->d_lp, S->d_la, S->d_known, S->d_words);
-  } else if (S->E) {        // no read at all: nothing was seen, known = the add's ack
-    hipLaunchKernelGGL(setfull_finish_kernel, dim3((S->E + 255) / 256), dim3(256), 0, s, S->d_lp, S->d_la, S->d_known, S->d_add_ok, S->E);
-  }
-  SF_TRY(hipGetLastError());
-  SF_TRY(hipEventRecord(S->ev1, s));
-  unsigned long long words = 0;
-  if (S->E) {
-    SF_TRY(hipMemcpyAsync(out->known, S->d_known, (size_t)S->E * 4, hipMemcpyDeviceToHost, s));
-    SF_TRY(hipMemcpyAsync(out->last_present, S->d_lp, (size_t)S->E * 4, hipMemcpyDeviceToHost, s));
-    SF_TRY(hipMemcpyAsync(out->last_absent, S->d_la, (size_t)S->E * 4, hipMemcpyDeviceToHost, s));
-  }
-  unsigned long long* counters = S->h_words;
-  SF_TRY(hipMemcpyAsync(counters, S->d_words, (size_t)kWordCounters * 128, hipMemcpyDeviceToHost, s));
-  SF_TRY(hipStreamSynchronize(s));
-  float ms = 0;
-  SF_TRY(hipEventElapsedTime(&ms, S->ev0, S->ev1));
-  out->ns_scan = (uint64_t)(ms * 1e6);
-  for (uint32_t k = 0; k < kWordCounters; k++) words += counters[16u * k];
-  out->bytes_scanned = (uint64_t)words * 4;
-  out->bytes_matrix = (uint64_t)S->R * S->WPR * 4;
-  return TBC_OK;
-}
-
-tbc_status tbc_setfull_create_rows(const tbc_setfull_rows* in, tbc_setfull** handle) {
-  if (!in || !handle || (in->n_elements && (!in->add_invoke || !in->add_ok)) ||
-      (in->n_reads && (!in->read_invoke || !in->read_ok || !in->top)) || !in->exc_off || (in->exc_off[in->n_reads] && !in->exc) || in->reserved0 != 0) {
-    set_error("tbc_setfull_create_rows: null argument");
-    return TBC_ERR_INVALID_ARG;
-  }
-  tbc_setfull_in dense{};
-  dense.n_elements = in->n_elements; dense.n_reads = in->n_reads; dense.words_per_row = std::max(1u, (in->n_elements + 31u) / 32u); dense.device = in->device;
-  dense.add_invoke = in->add_invoke; dense.add_ok = in->add_ok; dense.read_invoke = in->read_invoke; dense.read_ok = in->read_ok; dense.present = nullptr;
-  tbc_setfull* S = new (std::nothrow) tbc_setfull();
-  if (!S) return TBC_ERR_OOM;
-  const tbc_status st = setfull_create_impl(&dense, S, in);
-  if (st != TBC_OK) { delete S; return st; }
-  *handle = S;
-  return TBC_OK;
-}
-
-void tbc_setfull_destroy(tbc_setfull* S) {
-  if (!S) return;
-  (void)hipSetDevice(S->device);
-  delete S;
-}
-
-}  // extern "C"
-
-// ================================================================ many keys in one object (tbc_setfull_keys_*)
-// jepsen.independent splits the reference's set-full history into keys (set_full.clj:155) and checks each on its own; at real sizes a
-// key's matrix is a few MB and one object per key costs its fixed price (allocation, stream, copies, synchronisation) once per key while
-// its scan fills a sliver of the GPU.  Here every key lives in ONE arena, and each pass is ONE launch over the tiles of all keys: the plan
-// table (built on the host at create) gives each key its arrays' offsets, its chunking and the first tile of each grid; a workgroup finds
-// its key by a binary search over those first tiles (uniform across the workgroup: scalar loads) and then runs the single-key body on it.
-// Each key's pitch is a multiple of four words, so the scan always takes the 16 B path; the bits at or above a key's E never count (the
-// bodies mask them, and the rows kernel writes the padding words as zeros).
-namespace {
-
-struct SfKeyPlan {                 // one key (device table; offsets in 32-bit words)
-  uint32_t E, R, WPR, PITCH, rows_per_chunk, chunks, elem_base, row_base;
-  uint32_t pmax_off, out_off, any_gy, reserved;
-  unsigned long long m_off, sum_off;
-};
-enum { kFirstRows = 0, kFirstPrefix, kFirstAny, kFirstResolve, kFirstGather, kFirsts };   // first[g * (n_keys + 1) + k]: key k's first tile in grid g
-
-// the last key whose first tile (row) is <= b: keys with no tile share their successor's first and are never picked for a tile of theirs
-__device__ __forceinline__ uint32_t sf_find_key(const uint32_t* __restrict__ first, uint32_t n_keys, uint32_t b) {
-  uint32_t lo = 0, hi = n_keys;
-  while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (first[mid] <= b) lo = mid; else hi = mid; }
-  return lo;
-}
-
-__global__ __launch_bounds__(256) void setfull_keys_rows_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
-                                                                uint32_t R_all, const uint32_t* __restrict__ top, const unsigned long long* __restrict__ exc_off,
-                                                                const uint32_t* __restrict__ exc, uint32_t* __restrict__ M) {
-  for (uint32_t r = blockIdx.x; r < R_all; r += gridDim.x) {
-    const SfKeyPlan& p = plan[sf_find_key(first + kFirstRows * (n_keys + 1u), n_keys, r)];
-    // the whole pitch is written (zeros past E: top <= E), so no word of the arena the scan loads is left unset
-    setfull_build_row(M + p.m_off + (uint64_t)(r - p.row_base) * p.PITCH, top[r], exc_off[r], exc_off[r + 1], exc, p.PITCH);
-  }
-}
-
-__global__ __launch_bounds__(256) void setfull_keys_prefix_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
-                                                                  const uint32_t* add_invoke, const uint32_t* read_ok, uint32_t* P, uint32_t* pmax) {
-  const uint32_t* f = first + kFirstPrefix * (n_keys + 1u);
-  const uint32_t k = sf_find_key(f, n_keys, blockIdx.x);
-  const SfKeyPlan& p = plan[k];
-  setfull_prefix_row(add_invoke + p.elem_base, read_ok + p.row_base, p.E, p.R, p.rows_per_chunk, p.chunks, P + p.row_base, pmax + p.pmax_off,
-                     (blockIdx.x - f[k]) * 256u + threadIdx.x);
-}
-
-__global__ __launch_bounds__(256) void setfull_keys_any_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
-                                                               const uint32_t* __restrict__ M, const uint32_t* __restrict__ P, const uint32_t* __restrict__ pmax,
-                                                               uint32_t* __restrict__ any_p, uint32_t* __restrict__ any_a, unsigned long long* words_loaded) {
-  const uint32_t* f = first + kFirstAny * (n_keys + 1u);
-  const uint32_t k = sf_find_key(f, n_keys, blockIdx.x);
-  const SfKeyPlan& p = plan[k];
-  const uint32_t t = blockIdx.x - f[k];
-  // (chunk, column block) = (t % chunks, t / chunks): the order a 2-D launch hands them out in
-  const KeyGrid g{t % p.chunks, t / p.chunks, p.chunks, p.any_gy, blockIdx.x};
-  setfull_any_tile<4>(M + p.m_off, P + p.row_base, pmax + p.pmax_off, p.E, p.R, p.WPR, p.PITCH, p.rows_per_chunk, p.PITCH,
-                      any_p + p.sum_off, any_a + p.sum_off, words_loaded, g);
-}
-
-__global__ __launch_bounds__(256, SF_RESOLVE_MIN_WAVES) void setfull_keys_resolve_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first,
-                                                                  uint32_t n_keys, const uint32_t* __restrict__ M, const uint32_t* __restrict__ P,
-                                                                  const uint32_t* __restrict__ read_invoke, const uint32_t* __restrict__ read_ok,
-                                                                  const uint32_t* __restrict__ any_p, const uint32_t* __restrict__ any_a,
-                                                                  const uint32_t* __restrict__ add_ok, uint32_t* lp, uint32_t* la, uint32_t* known,
-                                                                  unsigned long long* words_loaded) {
-  const uint32_t* f = first + kFirstResolve * (n_keys + 1u);
-  const uint32_t k = sf_find_key(f, n_keys, blockIdx.x);
-  const SfKeyPlan& p = plan[k];
-  const uint32_t nb = (p.WPR + 3u) / 4u, bx = blockIdx.x - f[k];
-  // (a key of a multiple of eight workgroups starts on a multiple of eight -- the body's XCD-contiguous order holds -- and the tiles
-  // skipped to get there belong to the key before, past its last workgroup)
-  if (bx >= nb) return;
-  setfull_resolve_columns(M + p.m_off, P + p.row_base, read_invoke + p.row_base, read_ok + p.row_base, any_p + p.sum_off, any_a + p.sum_off,
-                          p.E, p.R, p.WPR, p.PITCH, p.rows_per_chunk, p.chunks, p.PITCH, add_ok + p.elem_base, lp + p.out_off, la + p.out_off,
-                          known + p.out_off, words_loaded, KeyGrid{bx, 0u, nb, 1u, blockIdx.x});
-}
-
-// the padded per-key results into the caller's layout (key after key, n_elements each); a key without reads takes the answer
-// setfull_finish_kernel gives one: nothing seen, known = the add's ack
-__global__ __launch_bounds__(256) void setfull_keys_gather_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
-                                                                  const uint32_t* __restrict__ add_ok, const uint32_t* __restrict__ lp_pad,
-                                                                  const uint32_t* __restrict__ la_pad, const uint32_t* __restrict__ known_pad,
-                                                                  uint32_t* __restrict__ known, uint32_t* __restrict__ lp, uint32_t* __restrict__ la) {
-  const uint32_t* f = first + kFirstGather * (n_keys + 1u);
-  const uint32_t k = sf_find_key(f, n_keys, blockIdx.x);
-  const SfKeyPlan& p = plan[k];
-  const uint32_t e = (blockIdx.x - f[k]) * 256u + threadIdx.x;
-  if (e >= p.E) return;
-  const uint32_t o = p.elem_base + e;
-  if (p.R == 0u) {
-    lp[o] = kNoneU; la[o] = kNoneU; known[o] = add_ok[o];
-  } else {
-    lp[o] = lp_pad[p.out_off + e]; la[o] = la_pad[p.out_off + e]; known[o] = known_pad[p.out_off + e];
-  }
-}
+constexpr size_t kCounterBytes = (size_t)kWordCounters * 128;
 
 }  // namespace
 
-struct tbc_setfull_keys {
+// One object behind all three entry points: a single key (tbc_setfull) is a keyed object with n_keys = 1.
+struct SfObject {
   int device = 0;
-  uint32_t n_keys = 0, sumE = 0, sumR = 0;
-  uint32_t tiles_rows = 0, tiles_prefix = 0, tiles_any = 0, tiles_resolve = 0, tiles_gather = 0;
+  uint32_t n_keys = 0, sumE = 0;
+  uint32_t tiles_any = 0, tiles_resolve = 0;
   uint64_t bytes_matrix = 0;
   SfKeyPlan* d_plan = nullptr;
   uint32_t *d_first = nullptr, *d_add_ok = nullptr, *d_read_invoke = nullptr, *d_read_ok = nullptr, *d_M = nullptr, *d_P = nullptr;
-  uint32_t *d_pmax = nullptr, *d_anyp = nullptr, *d_anya = nullptr, *d_pad = nullptr, *d_out = nullptr;     // d_pad: lp | la | known padded; d_out: known | lp | la, then the counters
+  uint32_t *d_pmax = nullptr, *d_anyp = nullptr, *d_anya = nullptr, *d_out = nullptr;     // d_out: known | lp | la, each in the caller's layout
   unsigned long long* d_words = nullptr;
-  size_t out_bytes = 0, pad_words = 0;                       // the one D2H of a run: d_out .. the end of the counters
-  std::vector<unsigned char> h_out;
-  void* arena = nullptr;
+  unsigned long long h_words[kWordCounters * 16] = {};
+  void* arena = nullptr;            // ONE allocation holds every array above and the inputs: one hipMalloc, one hipFree
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~tbc_setfull_keys() {
+  ~SfObject() {
     if (arena) (void)hipFree(arena);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
+// (the C handles tbc_setfull and tbc_setfull_keys stay incomplete types: two names of a pointer to this object)
+SfObject* sf_obj(tbc_setfull* h) { return reinterpret_cast<SfObject*>(h); }
+SfObject* sf_obj(tbc_setfull_keys* h) { return reinterpret_cast<SfObject*>(h); }
 
-// every rule of tbc_setfull_create_rows, key by key, on the host; nothing has touched a device yet
-static tbc_status setfull_keys_validate(const tbc_setfull_keys_in* in, uint64_t& sumE, uint64_t& sumR) {
-  const char* fn = "tbc_setfull_keys_create";
-  if (in->n_keys == 0) { set_error("%s: n_keys is 0", fn); return TBC_ERR_INVALID_ARG; }
-  if (!in->n_elements || !in->n_reads || !in->exc_off) { set_error("%s: null argument", fn); return TBC_ERR_INVALID_ARG; }
-  sumE = 0; sumR = 0;
-  for (uint32_t k = 0; k < in->n_keys; k++) { sumE += in->n_elements[k]; sumR += in->n_reads[k]; }
-  if (sumE >= 0xFFFFFFFFull || sumR >= 0xFFFFFFFFull) { set_error("%s: more than 2^32 - 2 elements or reads in one object", fn); return TBC_ERR_INVALID_ARG; }
-  if ((sumE && (!in->add_invoke || !in->add_ok)) || (sumR && (!in->read_invoke || !in->read_ok || !in->top)) || (in->exc_off[sumR] && !in->exc)) {
-    set_error("%s: null argument", fn);
-    return TBC_ERR_INVALID_ARG;
-  }
-  if (in->exc_off[0] != 0) { set_error("%s: exc_off[0] must be 0", fn); return TBC_ERR_INVALID_ARG; }
-  std::vector<uint32_t> tmp;
-  uint64_t e0 = 0, r0 = 0;
-  for (uint32_t k = 0; k < in->n_keys; e0 += in->n_elements[k], r0 += in->n_reads[k], k++) {
-    const uint32_t E = in->n_elements[k], R = in->n_reads[k];
-    for (uint32_t e = 1; e < E; e++)
-      if (in->add_invoke[e0 + e] <= in->add_invoke[e0 + e - 1]) { set_error("%s: key %u: add_invoke must be strictly ascending (element %u)", fn, k, e); return TBC_ERR_INVALID_ARG; }
-    for (uint32_t r = 0; r < R; r++) {
-      const uint64_t g = r0 + r;
-      if (r && in->read_invoke[g] <= in->read_invoke[g - 1]) { set_error("%s: key %u: read_invoke must be strictly ascending (read %u)", fn, k, r); return TBC_ERR_INVALID_ARG; }
-      if (in->top[g] > E || in->exc_off[g + 1] < in->exc_off[g]) { set_error("%s: key %u read %u: bad top / exc_off (top %u, n_elements %u)", fn, k, r, in->top[g], E); return TBC_ERR_INVALID_ARG; }
-      bool ascending = true;
-      for (uint64_t i = in->exc_off[g]; i < in->exc_off[g + 1]; i++) {
-        if (in->exc[i] >= E) { set_error("%s: key %u read %u: exception names element %u of %u", fn, k, r, in->exc[i], E); return TBC_ERR_INVALID_ARG; }
-        if (i > in->exc_off[g] && in->exc[i] <= in->exc[i - 1]) ascending = false;
-      }
-      if (ascending) continue;        // (strictly ascending: no element twice; any other order is sorted aside, as tbc_setfull_create_rows does)
-      tmp.assign(in->exc + in->exc_off[g], in->exc + in->exc_off[g + 1]);
-      std::sort(tmp.begin(), tmp.end());
-      for (size_t i = 1; i < tmp.size(); i++)
-        if (tmp[i] == tmp[i - 1]) { set_error("%s: key %u read %u lists element %u twice (each element at most once per read)", fn, k, r, tmp[i]); return TBC_ERR_INVALID_ARG; }
-    }
-  }
-  return TBC_OK;
-}
+namespace {
 
-static tbc_status setfull_keys_create_impl(const tbc_setfull_keys_in* in, tbc_setfull_keys* S, uint32_t sumE, uint32_t sumR) {
+tbc_status sf_check_device(uint32_t device) {
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || (int)in->device >= ndev) {
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || (int)device >= ndev) {
     set_error("no usable HIP device; libtbcheck has no CPU fallback");
     return TBC_ERR_NO_DEVICE;
   }
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, (int)in->device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-    set_error("device %u is not a gfx950 (MI355X) device", in->device);
+  if (hipGetDeviceProperties(&prop, (int)device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+    set_error("device %u is not a gfx950 (MI355X) device", device);
     return TBC_ERR_NO_DEVICE;
   }
+  return TBC_OK;
+}
+
+// Every rule of one key's inputs, on the host (the kernels trust them): the prefix search per row and "the latest row" rest on the
+// documented orders; every offset and element number of the compact reads is checked (top == nullptr: the dense entry, no compact reads).
+// exc_off and the rows' arrays start at the key's first read; `where` names the entry point (and the key).
+bool sf_key_is_valid(const char* where, uint32_t E, uint32_t R, const uint32_t* add_invoke, const uint32_t* read_invoke, const uint32_t* top,
+                     const uint64_t* exc_off, const uint32_t* exc, std::vector<uint32_t>& tmp) {
+  for (uint32_t e = 1; e < E; e++)
+    if (add_invoke[e] <= add_invoke[e - 1]) { set_error("%s: add_invoke must be strictly ascending (element %u)", where, e); return false; }
+  for (uint32_t r = 0; r < R; r++) {
+    if (r && read_invoke[r] <= read_invoke[r - 1]) { set_error("%s: read_invoke must be strictly ascending (read %u)", where, r); return false; }
+    if (!top) continue;
+    if (top[r] > E || exc_off[r + 1] < exc_off[r]) { set_error("%s read %u: bad top / exc_off (top %u, n_elements %u)", where, r, top[r], E); return false; }
+    bool ascending = true;
+    for (uint64_t i = exc_off[r]; i < exc_off[r + 1]; i++) {
+      if (exc[i] >= E) { set_error("%s read %u: exception names element %u of %u", where, r, exc[i], E); return false; }
+      if (i > exc_off[r] && exc[i] <= exc[i - 1]) ascending = false;
+    }
+    // each element at most once per read: the rows kernel FLIPS the listed bits, a duplicate would flip one back silently.  A strictly
+    // ascending list (what the in-repo encoders write) is seen to be duplicate-free in one pass; a list in any other order is sorted
+    // aside and looked at again (the header allows any order)
+    if (ascending) continue;
+    tmp.assign(exc + exc_off[r], exc + exc_off[r + 1]);
+    std::sort(tmp.begin(), tmp.end());
+    for (size_t i = 1; i < tmp.size(); i++)
+      if (tmp[i] == tmp[i - 1]) { set_error("%s read %u lists element %u twice (each element at most once per read)", where, r, tmp[i]); return false; }
+  }
+  return true;
+}
+
+// enough chunks to fill the GPU with wavefronts that each stream a good stretch of rows; short chunks: what pass 2 walks again is one chunk
+uint32_t sf_chunks(uint32_t WPR, uint32_t R) {
+  const uint32_t col_blocks = std::max(1u, (WPR + 255) / 256);
+  uint32_t chunks = std::max(1u, std::min(256u, 8192u / col_blocks));
+  while (chunks > 1 && R / chunks < 64) chunks >>= 1;
+  while ((R + chunks - 1) / chunks > kSetFullRows) chunks <<= 1;
+  return chunks;
+}
+
+// The create behind all three entry points.  `in`: the keys' arrays end to end (tbc_setfull_keys_in; the single-key entries point it at
+// their own one key), sumE / sumR its totals; `keyed`: name the key in a message.  `dense` (tbc_setfull_create only, one key): the
+// caller's matrix is copied into the key's pitch where the other entries build the matrix from top / exc.
+tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, uint32_t sumE, uint32_t sumR, const tbc_setfull_in* dense, SfObject* S) {
   const uint32_t n = in->n_keys;
-  S->device = (int)in->device; S->n_keys = n; S->sumE = sumE; S->sumR = sumR;
-  // ---- the plan: per key its chunking (tbc_setfull_create's rule: a key of a few reads is one chunk, a large key is chunked as a single
-  // key is) and its place in the arena's regions; per grid the first tile of every key
+  // ---- every rule, key by key, before any device call
+  if (!dense && in->exc_off[0] != 0) { set_error("%s: exc_off[0] must be 0", fn); return TBC_ERR_INVALID_ARG; }
+  {
+    std::vector<uint32_t> tmp;
+    char where[64];
+    uint32_t e0 = 0, r0 = 0;
+    for (uint32_t k = 0; k < n; e0 += in->n_elements[k], r0 += in->n_reads[k], k++) {
+      if (keyed) std::snprintf(where, sizeof where, "%s: key %u", fn, k); else std::snprintf(where, sizeof where, "%s", fn);
+      if (!sf_key_is_valid(where, in->n_elements[k], in->n_reads[k], in->add_invoke + e0, in->read_invoke + r0, dense ? nullptr : in->top + r0,
+                           dense ? nullptr : in->exc_off + r0, in->exc, tmp))
+        return TBC_ERR_INVALID_ARG;
+    }
+  }
+  const tbc_status dev = sf_check_device(in->device);
+  if (dev != TBC_OK) return dev;
+  S->device = (int)in->device; S->n_keys = n; S->sumE = sumE;
+  // ---- the plan: per key its chunking (a key of a few reads is one chunk) and its place in the arena's regions; per grid the first tile
+  // of every key
   std::vector<SfKeyPlan> plan(n);
   std::vector<uint32_t> first((size_t)kFirsts * (n + 1), 0u);
-  uint64_t m_words = 0, sum_words = 0, pmax_words = 0, pad_words = 0, tiles[kFirsts] = {};
+  uint64_t m_words = 0, sum_words = 0, pmax_words = 0, tiles[kFirsts] = {};
   const auto up = [](uint64_t x, uint64_t a) { return (x + a - 1) / a * a; };
   uint32_t eb = 0, rb = 0;
   for (uint32_t k = 0; k < n; k++) {
     SfKeyPlan& p = plan[k];
     p = SfKeyPlan{};
     p.E = in->n_elements[k]; p.R = in->n_reads[k]; p.elem_base = eb; p.row_base = rb;
+    // (PITCH: the words between two rows in device memory.  A pitch padded off the power of two was measured -- 16 .. 1,088 words: the
+    // same scan within 3 % either way, profiles/r06_setfull_pad_scan.txt -- so it is the words of a row, rounded up to four)
     p.WPR = (p.E + 31u) / 32u; p.PITCH = (p.WPR + 3u) / 4u * 4u;
     const bool scan = p.E && p.R;
-    uint32_t chunks = 1;
-    if (scan) {
-      const uint32_t col_blocks = (p.WPR + 255) / 256;
-      chunks = std::max(1u, std::min(256u, 8192u / std::max(1u, col_blocks)));
-      while (chunks > 1 && p.R / chunks < 64) chunks >>= 1;
-      while ((p.R + chunks - 1) / chunks > kSetFullRows) chunks <<= 1;
-    }
-    p.chunks = chunks; p.rows_per_chunk = std::max(1u, (p.R + chunks - 1) / chunks);
+    p.chunks = scan ? sf_chunks(p.WPR, p.R) : 1u; p.rows_per_chunk = std::max(1u, (p.R + p.chunks - 1) / p.chunks);
     p.any_gy = (p.PITCH / 4u + 255u) / 256u;
     m_words = up(m_words, 64); p.m_off = m_words; m_words += (uint64_t)p.R * p.PITCH;
     sum_words = up(sum_words, 64); p.sum_off = sum_words; sum_words += scan ? (uint64_t)p.chunks * p.PITCH : 0;
     p.pmax_off = (uint32_t)pmax_words; pmax_words += 2ull * p.chunks;
-    p.out_off = (uint32_t)pad_words; pad_words += 32ull * p.WPR;
-    const uint32_t nb = (p.WPR + 3u) / 4u;
+    const uint32_t nb = (p.WPR + 3u) / 4u;        // resolve: every key that has elements (one without reads: "nothing seen" is written there)
     first[kFirstRows * (n + 1) + k] = rb;
     first[kFirstPrefix * (n + 1) + k] = (uint32_t)tiles[kFirstPrefix]; tiles[kFirstPrefix] += scan ? (p.R + 255u) / 256u : 0u;
     first[kFirstAny * (n + 1) + k] = (uint32_t)tiles[kFirstAny]; tiles[kFirstAny] += scan ? (uint64_t)p.chunks * p.any_gy : 0u;
-    if (scan && nb % 8u == 0u) tiles[kFirstResolve] = up(tiles[kFirstResolve], 8);
-    first[kFirstResolve * (n + 1) + k] = (uint32_t)tiles[kFirstResolve]; tiles[kFirstResolve] += scan ? nb : 0u;
-    first[kFirstGather * (n + 1) + k] = (uint32_t)tiles[kFirstGather]; tiles[kFirstGather] += (p.E + 255u) / 256u;
-    S->bytes_matrix += (uint64_t)p.R * p.WPR * 4;
+    if (nb && nb % 8u == 0u) tiles[kFirstResolve] = up(tiles[kFirstResolve], 8);
+    first[kFirstResolve * (n + 1) + k] = (uint32_t)tiles[kFirstResolve]; tiles[kFirstResolve] += nb;
+    S->bytes_matrix += (uint64_t)p.R * (dense ? dense->words_per_row : p.WPR) * 4;
     eb += p.E; rb += p.R;
   }
   first[kFirstRows * (n + 1) + n] = rb;
   for (int g = kFirstPrefix; g < kFirsts; g++) first[(size_t)g * (n + 1) + n] = (uint32_t)tiles[g];
-  if (pad_words >= 0xFFFFFFFFull || pmax_words >= 0xFFFFFFFFull || tiles[kFirstAny] >= 0x7FFFFFFFull || tiles[kFirstResolve] >= 0x7FFFFFFFull) {
-    set_error("tbc_setfull_keys_create: too many elements for one object"); return TBC_ERR_INVALID_ARG;
+  if (pmax_words >= 0xFFFFFFFFull || tiles[kFirstAny] >= 0x7FFFFFFFull || tiles[kFirstResolve] >= 0x7FFFFFFFull) {
+    set_error("%s: too many elements for one object", fn); return TBC_ERR_INVALID_ARG;
   }
-  S->tiles_rows = std::min<uint32_t>(sumR, 16384u); S->tiles_prefix = (uint32_t)tiles[kFirstPrefix]; S->tiles_any = (uint32_t)tiles[kFirstAny];
-  S->tiles_resolve = (uint32_t)tiles[kFirstResolve]; S->tiles_gather = (uint32_t)tiles[kFirstGather]; S->pad_words = pad_words;
-  // ---- one arena: the inputs first (ONE H2D from a host image of the same layout), then what the device makes
-  const uint64_t ne = in->exc_off[sumR];
+  S->tiles_any = (uint32_t)tiles[kFirstAny]; S->tiles_resolve = (uint32_t)tiles[kFirstResolve];
+  // ---- one arena (round 6: fourteen hipMalloc and as many hipFree -- each of which waits for the device -- were most of a caller's 5 ms
+  // around a 0.16 ms scan; the reference checks one history per call site, set_full.clj:157, so create + run + destroy IS its time to
+  // verdict): what the host makes (plan, first tiles, the prefix extremes' start values), the caller's arrays, then what the device makes
+  const uint64_t ne = dense ? 0 : in->exc_off[sumR];
+  const size_t top4 = dense ? 0 : (size_t)sumR * 4, off8 = dense ? 0 : ((size_t)sumR + 1) * 8;
   size_t cursor = 0;
   const auto take = [&](size_t bytes) { const size_t at = cursor; cursor += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_plan = take(sizeof(SfKeyPlan) * n), o_first = take(first.size() * 4), o_ai = take((size_t)sumE * 4), o_ao = take((size_t)sumE * 4),
-               o_ri = take((size_t)sumR * 4), o_ro = take((size_t)sumR * 4), o_top = take((size_t)sumR * 4), o_off = take(((size_t)sumR + 1) * 8),
-               o_exc = take(ne * 4), o_pm = take(pmax_words * 4);
-  const size_t in_bytes = cursor;
-  const size_t o_M = take(m_words * 4), o_P = take((size_t)sumR * 4), o_any = take(sum_words * 8), o_pad = take(pad_words * 12);
-  const size_t o_out = take((size_t)sumE * 12), o_w = take((size_t)kWordCounters * 128);
-  S->out_bytes = o_w + (size_t)kWordCounters * 128 - o_out;
+  const size_t o_plan = take(sizeof(SfKeyPlan) * n), o_first = take(first.size() * 4), o_pm = take(pmax_words * 4);
+  const size_t head_bytes = cursor;
+  const size_t o_ai = take((size_t)sumE * 4), o_ao = take((size_t)sumE * 4), o_ri = take((size_t)sumR * 4), o_ro = take((size_t)sumR * 4),
+               o_top = take(top4), o_off = take(off8), o_exc = take(ne * 4);
+  const size_t o_M = take(m_words * 4), o_P = take((size_t)sumR * 4), o_any = take(sum_words * 8);
+  const size_t o_out = take((size_t)sumE * 12), o_w = take(kCounterBytes);
   std::vector<unsigned char> img;
-  try { img.assign(in_bytes, 0); S->h_out.assign(S->out_bytes, 0); } catch (const std::bad_alloc&) { set_error("tbc_setfull_keys_create: host memory"); return TBC_ERR_OOM; }
-  const auto put = [&](size_t at, const void* src, size_t bytes) { if (bytes) std::memcpy(img.data() + at, src, bytes); };
-  put(o_plan, plan.data(), sizeof(SfKeyPlan) * n); put(o_first, first.data(), first.size() * 4);
-  put(o_ai, in->add_invoke, (size_t)sumE * 4); put(o_ao, in->add_ok, (size_t)sumE * 4);
-  put(o_ri, in->read_invoke, (size_t)sumR * 4); put(o_ro, in->read_ok, (size_t)sumR * 4); put(o_top, in->top, (size_t)sumR * 4);
-  put(o_off, in->exc_off, ((size_t)sumR + 1) * 8); put(o_exc, in->exc, ne * 4);
+  try { img.assign(head_bytes, 0); } catch (const std::bad_alloc&) { set_error("%s: host memory", fn); return TBC_ERR_OOM; }
+  std::memcpy(img.data() + o_plan, plan.data(), sizeof(SfKeyPlan) * n);
+  std::memcpy(img.data() + o_first, first.data(), first.size() * 4);
   for (uint32_t k = 0; k < n; k++)        // the chunks' greatest prefixes start at 0, their least at ~0 (the minima lie behind the maxima)
     std::memset(img.data() + o_pm + ((size_t)plan[k].pmax_off + plan[k].chunks) * 4, 0xFF, (size_t)plan[k].chunks * 4);
   SF_TRY(hipSetDevice(S->device));
   SF_TRY(hipMalloc(&S->arena, std::max<size_t>(cursor, 256)));
   char* const A0 = static_cast<char*>(S->arena);
-  S->d_plan = (SfKeyPlan*)(A0 + o_plan); S->d_first = (uint32_t*)(A0 + o_first); S->d_add_ok = (uint32_t*)(A0 + o_ao);
+  S->d_plan = (SfKeyPlan*)(A0 + o_plan); S->d_first = (uint32_t*)(A0 + o_first); S->d_pmax = (uint32_t*)(A0 + o_pm); S->d_add_ok = (uint32_t*)(A0 + o_ao);
   S->d_read_invoke = (uint32_t*)(A0 + o_ri); S->d_read_ok = (uint32_t*)(A0 + o_ro); S->d_M = (uint32_t*)(A0 + o_M); S->d_P = (uint32_t*)(A0 + o_P);
-  S->d_anyp = (uint32_t*)(A0 + o_any); S->d_anya = S->d_anyp + sum_words; S->d_pad = (uint32_t*)(A0 + o_pad);
-  S->d_out = (uint32_t*)(A0 + o_out); S->d_words = (unsigned long long*)(A0 + o_w); S->d_pmax = (uint32_t*)(A0 + o_pm);
+  S->d_anyp = (uint32_t*)(A0 + o_any); S->d_anya = S->d_anyp + sum_words;
+  S->d_out = (uint32_t*)(A0 + o_out); S->d_words = (unsigned long long*)(A0 + o_w);
   SF_TRY(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
   SF_TRY(hipEventCreate(&S->ev0)); SF_TRY(hipEventCreate(&S->ev1));
-  SF_TRY(hipMemcpyAsync(A0, img.data(), in_bytes, hipMemcpyHostToDevice, S->stream));
+  // Each of the caller's arrays straight to its place in the arena: eight copies whatever n_keys is.  (Packing them into the host image
+  // first -- one H2D -- gains 0.04-0.09 ms on objects below ~1 MB and loses from ~1.5 MB on, 0.8 ms at the bench key's 13 MB and 3 ms at
+  // 256 keys x 2k ops; the direct copies alone hold the parent's end-to-end time at every shape measured: DESIGN.md K7.)  The copies
+  // read pageable memory of the caller's: the synchronise below ends them before create returns.
+  const auto put = [&](size_t at, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(A0 + at, src, bytes, hipMemcpyHostToDevice, S->stream) : hipSuccess;
+  };
+  SF_TRY(put(o_ai, in->add_invoke, (size_t)sumE * 4)); SF_TRY(put(o_ao, in->add_ok, (size_t)sumE * 4));
+  SF_TRY(put(o_ri, in->read_invoke, (size_t)sumR * 4)); SF_TRY(put(o_ro, in->read_ok, (size_t)sumR * 4));
+  SF_TRY(put(o_top, in->top, top4)); SF_TRY(put(o_off, in->exc_off, off8)); SF_TRY(put(o_exc, in->exc, ne * 4));
+  SF_TRY(hipMemcpyAsync(A0, img.data(), img.size(), hipMemcpyHostToDevice, S->stream));
   if (sum_words) SF_TRY(hipMemsetAsync(S->d_anyp, 0, sum_words * 8, S->stream));     // (the tiles below the diagonal never write theirs)
-  if (S->tiles_rows)
-    hipLaunchKernelGGL(setfull_keys_rows_kernel, dim3(S->tiles_rows), dim3(256), 0, S->stream, S->d_plan, S->d_first, n, sumR,
+  // ---- the matrix: the caller's, copied into the key's pitch (its padding zeroed: no word the scan loads is left unset; words of the
+  // caller's rows past the key's are ignored), or built from the compact reads
+  if (dense && plan[0].R && plan[0].WPR) {
+    const SfKeyPlan& p = plan[0];
+    if (p.PITCH > p.WPR) SF_TRY(hipMemset2DAsync(S->d_M + p.WPR, (size_t)p.PITCH * 4, 0, (size_t)(p.PITCH - p.WPR) * 4, p.R, S->stream));
+    SF_TRY(hipMemcpy2DAsync(S->d_M, (size_t)p.PITCH * 4, dense->present, (size_t)dense->words_per_row * 4, (size_t)p.WPR * 4, p.R, hipMemcpyHostToDevice, S->stream));
+  } else if (!dense && sumR) {
+    hipLaunchKernelGGL(setfull_rows_kernel, dim3(std::min<uint32_t>(sumR, 16384u)), dim3(256), 0, S->stream, S->d_plan, S->d_first, n, sumR,
                        (const uint32_t*)(A0 + o_top), (const unsigned long long*)(A0 + o_off), (const uint32_t*)(A0 + o_exc), S->d_M);
-  if (S->tiles_prefix)
-    hipLaunchKernelGGL(setfull_keys_prefix_kernel, dim3(S->tiles_prefix), dim3(256), 0, S->stream, S->d_plan, S->d_first, n,
+  }
+  // p[r] (how many elements had been invoked when read r completed) and the chunks' extremes depend on the inputs only
+  if (tiles[kFirstPrefix])
+    hipLaunchKernelGGL(setfull_prefix_kernel, dim3((uint32_t)tiles[kFirstPrefix]), dim3(256), 0, S->stream, S->d_plan, S->d_first, n,
                        (const uint32_t*)(A0 + o_ai), S->d_read_ok, S->d_P, S->d_pmax);
   SF_TRY(hipGetLastError());
   SF_TRY(hipStreamSynchronize(S->stream));
   return TBC_OK;
 }
 
-extern "C" {
-
-tbc_status tbc_setfull_keys_create(const tbc_setfull_keys_in* in, tbc_setfull_keys** handle) {
-  if (!in || !handle) { set_error("tbc_setfull_keys_create: null argument"); return TBC_ERR_INVALID_ARG; }
-  uint64_t sumE = 0, sumR = 0;
-  tbc_status st = setfull_keys_validate(in, sumE, sumR);
-  if (st != TBC_OK) return st;
-  tbc_setfull_keys* S = new (std::nothrow) tbc_setfull_keys();
+template <class Handle>
+tbc_status sf_new(const char* fn, bool keyed, const tbc_setfull_keys_in* in, uint32_t sumE, uint32_t sumR, const tbc_setfull_in* dense, Handle** handle) {
+  SfObject* S = new (std::nothrow) SfObject();
   if (!S) return TBC_ERR_OOM;
-  st = setfull_keys_create_impl(in, S, (uint32_t)sumE, (uint32_t)sumR);
+  const tbc_status st = sf_create(fn, keyed, in, sumE, sumR, dense, S);
   if (st != TBC_OK) { delete S; return st; }
-  *handle = S;
+  *handle = reinterpret_cast<Handle*>(S);
   return TBC_OK;
 }
 
-tbc_status tbc_setfull_keys_run(tbc_setfull_keys* S, tbc_setfull_keys_out* out) {
-  if (!S || !out || (S->sumE && (!out->known || !out->last_present || !out->last_absent))) { set_error("tbc_setfull_keys_run: null argument"); return TBC_ERR_INVALID_ARG; }
+// The run behind both: the scan's two launches between the events, then the results (n_elements each, key after key) and the counters back,
+// each array straight into the caller's
+tbc_status sf_run(SfObject* S, uint32_t* known, uint32_t* last_present, uint32_t* last_absent, uint64_t* ns_scan, uint64_t* bytes_scanned, uint64_t* bytes_matrix) {
   SF_TRY(hipSetDevice(S->device));
   hipStream_t s = S->stream;
   const uint32_t n = S->n_keys;
-  uint32_t* const lp_pad = S->d_pad; uint32_t* const la_pad = S->d_pad + S->pad_words; uint32_t* const kn_pad = S->d_pad + 2 * S->pad_words;
-  uint32_t* const known = S->d_out; uint32_t* const lp = S->d_out + S->sumE; uint32_t* const la = S->d_out + 2ull * S->sumE;
-  SF_TRY(hipMemsetAsync(S->d_words, 0, (size_t)kWordCounters * 128, s));
+  const size_t e4 = (size_t)S->sumE * 4;
+  uint32_t* const d_known = S->d_out; uint32_t* const d_lp = S->d_out + S->sumE; uint32_t* const d_la = S->d_out + 2ull * S->sumE;
+  SF_TRY(hipMemsetAsync(S->d_words, 0, kCounterBytes, s));
   SF_TRY(hipEventRecord(S->ev0, s));
-  // three launches whatever n_keys is (the resolve pass writes every padded result of a key that has reads; the gather every result)
   if (S->tiles_any)
-    hipLaunchKernelGGL(setfull_keys_any_kernel, dim3(S->tiles_any), dim3(256), 0, s, S->d_plan, S->d_first, n, S->d_M, S->d_P, S->d_pmax,
+    hipLaunchKernelGGL(setfull_any_kernel, dim3(S->tiles_any), dim3(256), 0, s, S->d_plan, S->d_first, n, S->d_M, S->d_P, S->d_pmax,
                        S->d_anyp, S->d_anya, S->d_words);
   if (S->tiles_resolve)
-    hipLaunchKernelGGL(setfull_keys_resolve_kernel, dim3(S->tiles_resolve), dim3(256), 0, s, S->d_plan, S->d_first, n, S->d_M, S->d_P, S->d_read_invoke,
-                       S->d_read_ok, S->d_anyp, S->d_anya, S->d_add_ok, lp_pad, la_pad, kn_pad, S->d_words);
-  if (S->tiles_gather)
-    hipLaunchKernelGGL(setfull_keys_gather_kernel, dim3(S->tiles_gather), dim3(256), 0, s, S->d_plan, S->d_first, n, S->d_add_ok, lp_pad, la_pad, kn_pad,
-                       known, lp, la);
+    hipLaunchKernelGGL(setfull_resolve_kernel, dim3(S->tiles_resolve), dim3(256), 0, s, S->d_plan, S->d_first, n, S->d_M, S->d_P, S->d_read_invoke,
+                       S->d_read_ok, S->d_anyp, S->d_anya, S->d_add_ok, d_lp, d_la, d_known, S->d_words);
   SF_TRY(hipGetLastError());
   SF_TRY(hipEventRecord(S->ev1, s));
-  SF_TRY(hipMemcpyAsync(S->h_out.data(), S->d_out, S->out_bytes, hipMemcpyDeviceToHost, s));        // results and counters: one copy
+  if (e4) {
+    SF_TRY(hipMemcpyAsync(known, d_known, e4, hipMemcpyDeviceToHost, s));
+    SF_TRY(hipMemcpyAsync(last_present, d_lp, e4, hipMemcpyDeviceToHost, s));
+    SF_TRY(hipMemcpyAsync(last_absent, d_la, e4, hipMemcpyDeviceToHost, s));
+  }
+  SF_TRY(hipMemcpyAsync(S->h_words, S->d_words, kCounterBytes, hipMemcpyDeviceToHost, s));
   SF_TRY(hipStreamSynchronize(s));
   float ms = 0;
   SF_TRY(hipEventElapsedTime(&ms, S->ev0, S->ev1));
-  const unsigned char* h = S->h_out.data();
-  if (S->sumE) {
-    std::memcpy(out->known, h, (size_t)S->sumE * 4);
-    std::memcpy(out->last_present, h + (size_t)S->sumE * 4, (size_t)S->sumE * 4);
-    std::memcpy(out->last_absent, h + (size_t)S->sumE * 8, (size_t)S->sumE * 4);
-  }
-  const unsigned long long* counters = reinterpret_cast<const unsigned long long*>(h + ((char*)S->d_words - (char*)S->d_out));
   unsigned long long words = 0;
-  for (uint32_t k = 0; k < kWordCounters; k++) words += counters[16u * k];
-  out->ns_scan = (uint64_t)(ms * 1e6);
-  out->bytes_scanned = (uint64_t)words * 4;
-  out->bytes_matrix = S->bytes_matrix;
+  for (uint32_t k = 0; k < kWordCounters; k++) words += S->h_words[16u * k];
+  *ns_scan = (uint64_t)(ms * 1e6);
+  *bytes_scanned = (uint64_t)words * 4;
+  *bytes_matrix = S->bytes_matrix;
   return TBC_OK;
 }
 
-void tbc_setfull_keys_destroy(tbc_setfull_keys* S) {
+void sf_destroy(SfObject* S) {
   if (!S) return;
   (void)hipSetDevice(S->device);
   delete S;
 }
+
+}  // namespace
+
+extern "C" {
+
+tbc_status tbc_setfull_create(const tbc_setfull_in* in, tbc_setfull** handle) {
+  const char* fn = "tbc_setfull_create";
+  if (!in || !handle || (in->n_elements && (!in->add_invoke || !in->add_ok)) ||
+      (in->n_reads && (!in->read_invoke || !in->read_ok || !in->present))) {
+    set_error("%s: null argument", fn);
+    return TBC_ERR_INVALID_ARG;
+  }
+  if ((uint64_t)in->words_per_row * 32 < in->n_elements) { set_error("%s: words_per_row too small for n_elements", fn); return TBC_ERR_INVALID_ARG; }
+  const tbc_setfull_keys_in one = {1u, in->device, &in->n_elements, &in->n_reads, in->add_invoke, in->add_ok, in->read_invoke, in->read_ok, nullptr, nullptr, nullptr};
+  return sf_new(fn, false, &one, in->n_elements, in->n_reads, in, handle);
+}
+
+tbc_status tbc_setfull_create_rows(const tbc_setfull_rows* in, tbc_setfull** handle) {
+  const char* fn = "tbc_setfull_create_rows";
+  if (!in || !handle || (in->n_elements && (!in->add_invoke || !in->add_ok)) ||
+      (in->n_reads && (!in->read_invoke || !in->read_ok || !in->top)) || !in->exc_off || (in->exc_off[in->n_reads] && !in->exc) || in->reserved0 != 0) {
+    set_error("%s: null argument", fn);
+    return TBC_ERR_INVALID_ARG;
+  }
+  const tbc_setfull_keys_in one = {1u, in->device, &in->n_elements, &in->n_reads, in->add_invoke, in->add_ok, in->read_invoke, in->read_ok, in->top, in->exc_off, in->exc};
+  return sf_new(fn, false, &one, in->n_elements, in->n_reads, nullptr, handle);
+}
+
+tbc_status tbc_setfull_keys_create(const tbc_setfull_keys_in* in, tbc_setfull_keys** handle) {
+  const char* fn = "tbc_setfull_keys_create";
+  if (!in || !handle) { set_error("%s: null argument", fn); return TBC_ERR_INVALID_ARG; }
+  if (in->n_keys == 0) { set_error("%s: n_keys is 0", fn); return TBC_ERR_INVALID_ARG; }
+  if (!in->n_elements || !in->n_reads || !in->exc_off) { set_error("%s: null argument", fn); return TBC_ERR_INVALID_ARG; }
+  uint64_t sumE = 0, sumR = 0;
+  for (uint32_t k = 0; k < in->n_keys; k++) { sumE += in->n_elements[k]; sumR += in->n_reads[k]; }
+  if (sumE >= 0xFFFFFFFFull || sumR >= 0xFFFFFFFFull) { set_error("%s: more than 2^32 - 2 elements or reads in one object", fn); return TBC_ERR_INVALID_ARG; }
+  if ((sumE && (!in->add_invoke || !in->add_ok)) || (sumR && (!in->read_invoke || !in->read_ok || !in->top)) || (in->exc_off[sumR] && !in->exc)) {
+    set_error("%s: null argument", fn);
+    return TBC_ERR_INVALID_ARG;
+  }
+  return sf_new(fn, true, in, (uint32_t)sumE, (uint32_t)sumR, nullptr, handle);
+}
+
+tbc_status tbc_setfull_run(tbc_setfull* handle, tbc_setfull_out* out) {
+  SfObject* const S = sf_obj(handle);
+  if (!S || !out || (S->sumE && (!out->known || !out->last_present || !out->last_absent))) { set_error("tbc_setfull_run: null argument"); return TBC_ERR_INVALID_ARG; }
+  return sf_run(S, out->known, out->last_present, out->last_absent, &out->ns_scan, &out->bytes_scanned, &out->bytes_matrix);
+}
+
+tbc_status tbc_setfull_keys_run(tbc_setfull_keys* handle, tbc_setfull_keys_out* out) {
+  SfObject* const S = sf_obj(handle);
+  if (!S || !out || (S->sumE && (!out->known || !out->last_present || !out->last_absent))) { set_error("tbc_setfull_keys_run: null argument"); return TBC_ERR_INVALID_ARG; }
+  return sf_run(S, out->known, out->last_present, out->last_absent, &out->ns_scan, &out->bytes_scanned, &out->bytes_matrix);
+}
+
+void tbc_setfull_destroy(tbc_setfull* handle) { sf_destroy(sf_obj(handle)); }
+void tbc_setfull_keys_destroy(tbc_setfull_keys* handle) { sf_destroy(sf_obj(handle)); }
 
 }  // extern "C"

@@ -127,8 +127,34 @@ def _freeze(v):
     return tuple(v) if isinstance(v, list) else v
 
 
-class Scan:
+class _Handle:
+    """A tbc_setfull / tbc_setfull_keys object: subclasses create `_h` and name the C calls; the handle's lifetime and the three result
+    arrays of a run are the same for both."""
+    _run = _destroy = _Out = None
+
+    def _scan(self, n_elements):
+        n = max(1, int(n_elements))
+        known, lp, la = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        o = self._Out()
+        o.known, o.last_present, o.last_absent = _p(known, C.c_uint32), _p(lp, C.c_uint32), _p(la, C.c_uint32)
+        N.check_status(getattr(N.lib(), self._run)(self._h, C.byref(o)))
+        return known, lp, la, {"ns_scan": o.ns_scan, "bytes_scanned": o.bytes_scanned, "bytes_matrix": o.bytes_matrix}
+
+    def close(self):
+        if self._h:
+            getattr(N.lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Scan(_Handle):
     """tbc_setfull_*: the matrix resident in HBM, `run()` scans it."""
+    _run, _destroy, _Out = "tbc_setfull_run", "tbc_setfull_destroy", N.SetFullOut
 
     def __init__(self, enc_or_arrays, device=0, rows=None):
         """rows: True = hand the reads over in compact form (top / exc_off / exc: tbc_setfull_create_rows, the matrix is built on
@@ -161,24 +187,8 @@ class Scan:
         N.check_status(N.lib().tbc_setfull_create(C.byref(s), C.byref(self._h)))
 
     def run(self):
-        n = max(1, self.E)
-        known, lp, la = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-        o = N.SetFullOut()
-        o.known, o.last_present, o.last_absent = _p(known, C.c_uint32), _p(lp, C.c_uint32), _p(la, C.c_uint32)
-        N.check_status(N.lib().tbc_setfull_run(self._h, C.byref(o)))
-        return {"known": known[:self.E], "last_present": lp[:self.E], "last_absent": la[:self.E],
-                "ns_scan": o.ns_scan, "bytes_scanned": o.bytes_scanned, "bytes_matrix": o.bytes_matrix}
-
-    def close(self):
-        if self._h:
-            N.lib().tbc_setfull_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        known, lp, la, tot = self._scan(self.E)
+        return {"known": known[:self.E], "last_present": lp[:self.E], "last_absent": la[:self.E], **tot}
 
 
 def frequency_distribution(points, xs):
@@ -253,9 +263,10 @@ def _matrix_bytes(enc):
     return int(enc.R) * ((int(enc.wpr) + 3) // 4 * 4) * 4 if enc.E else 0
 
 
-class KeyedScan:
+class KeyedScan(_Handle):
     """tbc_setfull_keys_*: the compact reads of MANY keys (each an `Encoded`) resident in one object; `run()` scans all of them in one
     fixed sequence of launches and returns each key's known / last-present / last-absent, in the order the encodings were given."""
+    _run, _destroy, _Out = "tbc_setfull_keys_run", "tbc_setfull_keys_destroy", N.SetFullKeysOut
 
     def __init__(self, encs, device=0):
         encs = list(encs)
@@ -281,25 +292,10 @@ class KeyedScan:
 
     def run(self):
         """-> ([per key {"known", "last_present", "last_absent"}], {"ns_scan", "bytes_scanned", "bytes_matrix"} of the whole object)"""
-        n = max(1, int(self.Es.sum()))
-        known, lp, la = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-        o = N.SetFullKeysOut()
-        o.known, o.last_present, o.last_absent = _p(known, C.c_uint32), _p(lp, C.c_uint32), _p(la, C.c_uint32)
-        N.check_status(N.lib().tbc_setfull_keys_run(self._h, C.byref(o)))
+        known, lp, la, tot = self._scan(self.Es.sum())
         cut = np.concatenate([[0], np.cumsum(self.Es, dtype=np.int64)])
         per = [{"known": known[a:b], "last_present": lp[a:b], "last_absent": la[a:b]} for a, b in zip(cut[:-1], cut[1:])]
-        return per, {"ns_scan": o.ns_scan, "bytes_scanned": o.bytes_scanned, "bytes_matrix": o.bytes_matrix}
-
-    def close(self):
-        if self._h:
-            N.lib().tbc_setfull_keys_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        return per, tot
 
 
 def groups_within_budget(encs, budget=None):

@@ -218,9 +218,9 @@ def test_large_matrix_against_numpy(native):
 @pytest.mark.gpu
 @pytest.mark.parametrize("E,R", [(1000, 700), (4096 + 77, 3000), (130, 5000)])
 def test_rows_of_a_multiple_of_16_bytes_and_rows_that_are_not(native, E, R):
-    """the streaming pass takes four word columns a lane (16 B loads) when a row is a multiple of four words and one otherwise: the
-    same matrix at words_per_row = ceil(E / 32) rounded up to four, + 1, + 2 and + 3 -- the same three indices as numpy's, the
-    same bytes counted"""
+    """the streaming pass takes four word columns a lane (16 B loads) whatever the caller's row length is (the matrix is copied into
+    a pitch of a multiple of four words): the same matrix at words_per_row = ceil(E / 32) rounded up to four, + 1, + 2 and + 3 -- the
+    same three indices as numpy's, the same bytes counted"""
     rng = np.random.default_rng(E + R)
     add_invoke = np.sort(rng.choice(4 * (E + R), E, replace=False)).astype(np.uint32) * 2
     read_invoke = (np.sort(rng.choice(4 * (E + R), R, replace=False)).astype(np.uint32) * 2 + 1)
@@ -287,8 +287,8 @@ def test_more_than_256_chunks_of_reads(native):
 
 
 def test_unsorted_inputs_are_rejected_before_any_device_work(native_lib_loaded=None):
-    """tbc_setfull_create checks the documented orders (add_invoke / read_invoke strictly ascending) -- on a machine without
-    a GPU it answers TBC_ERR_NO_DEVICE first, which is fine: nothing is computed either way."""
+    """tbc_setfull_create checks the documented orders (add_invoke / read_invoke strictly ascending) on the host, before it asks for
+    a device: the same answer with or without a GPU."""
     import ctypes as C
     lib = N.lib()
     ai = np.array([4, 2], np.uint32); ao = np.array([5, 3], np.uint32)
@@ -297,9 +297,39 @@ def test_unsorted_inputs_are_rejected_before_any_device_work(native_lib_loaded=N
                       ri.ctypes.data_as(C.POINTER(C.c_uint32)), ro.ctypes.data_as(C.POINTER(C.c_uint32)), pr.ctypes.data_as(C.POINTER(C.c_uint32)))
     h = C.c_void_p()
     st = lib.tbc_setfull_create(C.byref(inp), C.byref(h))
-    assert st in (N.ERR_INVALID_ARG, N.ERR_NO_DEVICE)
-    if lib.tbc_device_count() > 0:
-        assert st == N.ERR_INVALID_ARG and b"ascending" in lib.tbc_last_error()
+    assert st == N.ERR_INVALID_ARG and b"ascending" in lib.tbc_last_error()
+
+
+def test_malformed_compact_reads_are_rejected_before_any_device_work():
+    """tbc_setfull_create_rows through raw ctypes: every rule of the compact form is checked on the host (no GPU needed), and the
+    message names the entry point that was called."""
+    import ctypes as C
+    lib = N.lib()
+    u32, u64 = lambda *x: np.array(x, np.uint32), lambda *x: np.array(x, np.uint64)
+    good = dict(ai=u32(0, 2, 4, 6), ao=u32(1, 3, 5, 7), ri=u32(8, 10, 12), ro=u32(9, 11, 13), top=u32(4, 3, 4), off=u64(0, 2, 2, 3), exc=u32(0, 2, 1))
+    cases = [({}, None),
+             ({"exc": u32(2, 2, 1)}, b"twice"),                       # a duplicate exception
+             ({"exc": u32(2, 0, 2), "off": u64(0, 3, 3, 3)}, b"twice"),   # ... in a list that is not ascending
+             ({"top": u32(4, 5, 4)}, b"top"),                          # top > E
+             ({"exc": u32(0, 4, 1)}, b"element 4 of 4"),               # an exception >= E
+             ({"off": u64(1, 2, 2, 3)}, b"exc_off[0]"),
+             ({"ri": u32(8, 12, 10)}, b"read_invoke must be strictly ascending")]
+    for change, want in cases:
+        a = dict(good, **change)
+        ptr = lambda k, t=C.c_uint32: a[k].ctypes.data_as(C.POINTER(t))
+        inp = N.SetFullRows()
+        inp.n_elements, inp.n_reads, inp.device, inp.reserved0 = 4, 3, 0, 0
+        inp.add_invoke, inp.add_ok, inp.read_invoke, inp.read_ok = ptr("ai"), ptr("ao"), ptr("ri"), ptr("ro")
+        inp.top, inp.exc_off, inp.exc = ptr("top"), ptr("off", C.c_uint64), ptr("exc")
+        h = C.c_void_p()
+        st = lib.tbc_setfull_create_rows(C.byref(inp), C.byref(h))
+        msg = lib.tbc_last_error()
+        if want is None:                    # the well-formed input gets past the host checks: a scan object, or "no device"
+            assert st in (N.OK_STATUS, N.ERR_NO_DEVICE), (st, msg)
+            if st == N.OK_STATUS:
+                lib.tbc_setfull_destroy(h)
+            continue
+        assert st == N.ERR_INVALID_ARG and want in msg and b"tbc_setfull_create_rows" in msg, (change, st, msg)
 
 
 def test_recalled_jepsen_details_latency_duplicates_readd():

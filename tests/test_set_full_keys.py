@@ -196,19 +196,29 @@ def _synthetic_key(E, R, seed, shuffle_exc=False):
     return a
 
 
-def _dense_states(a):
-    """known / last-present / last-absent by a numpy reduction over the dense matrix (only reads completing after the add count)."""
+def _dense_states(a, block_cells=4_000_000):
+    """known / last-present / last-absent by a numpy reduction over the dense matrix (only reads completing after the add count), a
+    block of rows x columns of at most `block_cells` cells at a time (the reductions are a max and two mins: blocks combine exactly)."""
     E, R = a.E, a.R
-    pres = np.zeros((R, E), bool)
-    for r in range(R):
-        pres[r, :int(a.top[r])] = True
-        ex = a.exc[int(a.exc_off[r]):int(a.exc_off[r + 1])].astype(np.int64)
-        pres[r, ex] ^= True
-    counts = a.add_invoke[None, :].astype(np.int64) < a.read_ok[:, None].astype(np.int64)
-    inv = a.read_invoke.astype(np.int64)[:, None]
-    lp = np.where(pres & counts, inv, -1).max(axis=0, initial=-1)
-    la = np.where(~pres & counts, inv, -1).max(axis=0, initial=-1)
-    kn = np.minimum(np.where(pres & counts, a.read_ok.astype(np.int64)[:, None], 2 ** 40).min(axis=0, initial=2 ** 40), a.add_ok.astype(np.int64))
+    lp, la, kn = np.full(E, -1, np.int64), np.full(E, -1, np.int64), np.full(E, 2 ** 40, np.int64)
+    cols = max(1, min(E, 8192))
+    rows = max(1, min(R, block_cells // cols))
+    exc_row = np.repeat(np.arange(R, dtype=np.int64), np.diff(a.exc_off.astype(np.int64)))
+    exc = a.exc.astype(np.int64)
+    for r0 in range(0, R, rows):
+        r1 = min(R, r0 + rows)
+        x0, x1 = int(a.exc_off[r0]), int(a.exc_off[r1])
+        inv, ok = a.read_invoke[r0:r1].astype(np.int64)[:, None], a.read_ok[r0:r1].astype(np.int64)[:, None]
+        for c0 in range(0, E, cols):
+            c1 = min(E, c0 + cols)
+            pres = np.arange(c0, c1, dtype=np.int64)[None, :] < a.top[r0:r1].astype(np.int64)[:, None]
+            m = (exc[x0:x1] >= c0) & (exc[x0:x1] < c1)
+            pres[exc_row[x0:x1][m] - r0, exc[x0:x1][m] - c0] ^= True          # (each element at most once per read: no pair twice)
+            counts = a.add_invoke[None, c0:c1].astype(np.int64) < ok
+            lp[c0:c1] = np.maximum(lp[c0:c1], np.where(pres & counts, inv, -1).max(axis=0, initial=-1))
+            la[c0:c1] = np.maximum(la[c0:c1], np.where(~pres & counts, inv, -1).max(axis=0, initial=-1))
+            kn[c0:c1] = np.minimum(kn[c0:c1], np.where(pres & counts, ok, 2 ** 40).min(axis=0, initial=2 ** 40))
+    kn = np.minimum(kn, a.add_ok.astype(np.int64))
     u = lambda x, big: np.where((x < 0) | (x >= big), NONE, x).astype(np.uint32)
     return {"known": u(np.where(kn == NONE, 2 ** 40, kn), 2 ** 40), "last_present": u(lp, 2 ** 40), "last_absent": u(la, 2 ** 40)}
 
@@ -294,7 +304,25 @@ def _single(a):
     return st
 
 
-def _assert_keyed_equals_single(arrs, dense_limit=4_000_000):
+def test_blocked_dense_states_equal_the_unblocked_ones():
+    """_dense_states is the keyed scan's independent partner on every key, the large ones block by block: blocks of any size give what
+    one block over the whole matrix gives, and that is the oracle's answer on a history."""
+    for E, R, seed, shuffle in ((0, 5, 1, False), (7, 0, 2, False), (1, 1, 3, False), (33, 129, 4, True), (129, 2049, 5, False), (5000, 300, 6, True)):
+        a = _synthetic_key(E, R, seed, shuffle_exc=shuffle)
+        whole = _dense_states(a, block_cells=1 << 62)
+        for cells in (1, 1000, 100_000):
+            part = _dense_states(a, block_cells=cells)
+            for f in ("known", "last_present", "last_absent"):
+                assert np.array_equal(part[f], whole[f]), (E, R, cells, f)
+    h = set_history(1500, 5, 31, busy=0.3, info=0.02)
+    d, want = _dense_states(sf.Encoded(h), block_cells=5000), osf.element_states(h)
+    for f in ("known", "last_present", "last_absent"):
+        assert [int(x) for x in d[f]] == [w[f] for w in want], f
+
+
+def _assert_keyed_equals_single(arrs, dense_limit=None):
+    """keyed == Scan(rows=True) key by key (many keys placed == one key placed: both share the host code) and, for every key of at most
+    `dense_limit` cells (None: every key), == the numpy reduction, which shares nothing with either."""
     with sf.KeyedScan(arrs) as ks:
         per, tot = ks.run()
     assert len(per) == len(arrs)
@@ -302,7 +330,7 @@ def _assert_keyed_equals_single(arrs, dense_limit=4_000_000):
         want = _single(a)
         for f in ("known", "last_present", "last_absent"):
             assert np.array_equal(got[f], want[f]), (i, a.E, a.R, f)
-        if a.E * a.R <= dense_limit:
+        if dense_limit is None or a.E * a.R <= dense_limit:
             d = _dense_states(a)
             for f in ("known", "last_present", "last_absent"):
                 assert np.array_equal(got[f], d[f]), (i, a.E, a.R, f, "numpy")
@@ -339,7 +367,7 @@ def test_keyed_equals_single_key_on_every_edge_shape(native):
     long = _synthetic_key(64, 2048 * 256 + 3000, 77)
     arrs.insert(len(arrs) // 2, long)
     assert len(arrs) >= 280
-    _assert_keyed_equals_single(arrs, dense_limit=2_000_000)
+    _assert_keyed_equals_single(arrs)
 
 
 @pytest.mark.gpu
