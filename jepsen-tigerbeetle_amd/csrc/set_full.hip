@@ -24,7 +24,8 @@
 // column's adds is skipped without a load: the all-zero triangle below the diagonal is never read.
 // known: the first read (in invocation order) containing e need not be the first to complete, so the walk keeps
 // offering later rows' read_ok while they were invoked before the latest first-completion seen -- a window bounded by
-// the number of concurrent readers.
+// the LONGEST READ, in rows: every read invoked while it was open (one paused reader holds the window open over hundreds of rows
+// and across chunks, however few readers there are).
 //
 // One object and one set of kernels behind the three entry points: jepsen.independent splits the reference's set-full history into keys
 // (set_full.clj:155) and checks each on its own, so an object holds n_keys keys (tbc_setfull_keys_create), and a single key
