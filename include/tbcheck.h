@@ -624,8 +624,9 @@ tbc_status tbc_memo_build(int64_t init_state, uint32_t n_classes,
  *   last_absent   invocation of the latest-invoked :ok read that did not
  * (only reads completing after the element's add was invoked count).  The device part is the scan of the
  * reads x elements membership matrix that yields those three per element -- a streaming pass, the one
- * kernel on this path with a real HBM roofline; outcomes (:stable / :lost / :never-read, latencies,
- * :valid?) are a few operations per element on the host (jepsen-tigerbeetle_amd/jepsen/set_full.py).
+ * kernel on this path with a real HBM roofline.  tbc_setfull_run hands those three indices back; tbc_setfull_results
+ * (below) goes on to decide outcomes (:stable / :lost / :never-read), latencies, counts, :valid?, latency quantiles
+ * and the worst stale elements on the device and returns the check result.
  *
  * Inputs (caller-owned): elements numbered in order of their first :add invocation (add_invoke ascending),
  * reads = the :ok reads in order of invocation (read_invoke ascending); present = n_reads rows of
@@ -700,6 +701,57 @@ typedef struct tbc_setfull_keys tbc_setfull_keys;
 tbc_status tbc_setfull_keys_create(const tbc_setfull_keys_in* in, tbc_setfull_keys** handle);
 tbc_status tbc_setfull_keys_run(tbc_setfull_keys* handle, tbc_setfull_keys_out* out);
 void tbc_setfull_keys_destroy(tbc_setfull_keys* handle);
+
+/* The check result itself, decided on the device: tbc_setfull_results / tbc_setfull_keys_results scan (exactly what _run does) and then
+ * turn the three indices -- which stay on the device -- into every element's outcome and latencies and every key's counts, :valid?,
+ * latency quantiles and worst stale elements (csrc/set_full_results.h).  A fixed number of launches whatever n_keys is.  Semantics as
+ * oracle/set_full.py `outcomes` and `check`, all in 64-bit integers:
+ *   stable  <=> last_present exists and last_absent < last_present
+ *   lost    <=> known, last_absent exists, last_present < last_absent and known < last_absent;  otherwise never-read
+ *   stable_latency = max(0, (time[last_absent] + 1, or 0 if there is none) - time[known]) / unit;  lost_latency likewise from last_present
+ *   stale   <=> stable and stable_latency > 0
+ *   valid: false if anything is lost, else unknown if nothing is stable, else false if TBC_SETFULL_F_LINEARIZABLE and something is stale,
+ *          else true.  Duplicated elements are found by the caller's encoder and are NOT known here: the caller ANDs them in
+ *          (any duplicate makes the result false).
+ *   quantile p of n values = the value at rank min(n - 1, (uint64_t)((double)n * p)) of the ascending order
+ *   worst stale = the 8 greatest stable latencies among stale elements, equal latencies by ascending element number.
+ * Times: op_time[time_off[k] + i] is the :time of key k's op i -- i the same local op index add_invoke, add_ok, read_invoke and read_ok
+ * use; slots of other ops may hold anything; time differences must fit an int64.  Each key's slice must be longer than the greatest
+ * index among the key's inputs.  op_time == NULL: time = the op index and unit 1 (time_off is not read).  A short slice, a null
+ * argument or unit == 0 is TBC_ERR_INVALID_ARG before any device work; the message names the entry point and the key. */
+#define TBC_SETFULL_F_LINEARIZABLE 1u
+enum { TBC_SETFULL_NEVER_READ = 0, TBC_SETFULL_STABLE = 1, TBC_SETFULL_LOST = 2 };            /* outcome */
+enum { TBC_SETFULL_VALID_FALSE = 0, TBC_SETFULL_VALID_TRUE = 1, TBC_SETFULL_VALID_UNKNOWN = 2 };
+#define TBC_SETFULL_WORST 8
+typedef struct tbc_setfull_times {
+  const int64_t* op_time;        /* [time_off[n_keys]] or NULL */
+  const uint64_t* time_off;      /* [n_keys + 1], ascending (one key: {0, n_ops}) */
+  uint64_t unit;                 /* 1,000,000 for jepsen's ns -> whole ms, or 1; never 0 */
+  uint32_t flags, reserved0;     /* TBC_SETFULL_F_* */
+} tbc_setfull_times;
+typedef struct tbc_setfull_key_summary {
+  uint32_t attempt_count, stable_count, lost_count, never_read_count, stale_count;
+  uint8_t valid;                                     /* TBC_SETFULL_VALID_* (duplicates not counted in: see above) */
+  uint8_t stable_q_present, lost_q_present;          /* 1: the five points below hold values (the count is not 0) */
+  uint8_t n_worst;                                   /* <= TBC_SETFULL_WORST */
+  int64_t stable_q[5], lost_q[5];                    /* the points {0, .5, .95, .99, 1} */
+  uint32_t worst_element[TBC_SETFULL_WORST];         /* element numbers local to the key, worst first */
+  uint32_t worst_known[TBC_SETFULL_WORST];           /* their known and last_absent (TBC_NO_OP = none) */
+  uint32_t worst_last_absent[TBC_SETFULL_WORST];
+  int64_t worst_latency[TBC_SETFULL_WORST];
+} tbc_setfull_key_summary;
+typedef struct tbc_setfull_results_out {             /* arrays caller-allocated, [sum n_elements] each, key after key */
+  uint8_t* outcome;                                  /* TBC_SETFULL_NEVER_READ / _STABLE / _LOST */
+  int64_t* stable_latency;                           /* -1 where the element is not stable */
+  int64_t* lost_latency;                             /* -1 where it is not lost */
+  uint32_t *known, *last_present, *last_absent;      /* each optional: NULL = not wanted */
+  tbc_setfull_key_summary* summary;                  /* [n_keys] */
+  uint64_t ns_scan;                                  /* as tbc_setfull_out */
+  uint64_t ns_results;                               /* device time of the kernels after the scan (HIP events) */
+  uint64_t bytes_scanned, bytes_matrix;
+} tbc_setfull_results_out;
+tbc_status tbc_setfull_results(tbc_setfull* handle, const tbc_setfull_times* times, tbc_setfull_results_out* out);
+tbc_status tbc_setfull_keys_results(tbc_setfull_keys* handle, const tbc_setfull_times* times, tbc_setfull_results_out* out);
 
 /* ------------------------------------------------------------------- misc */
 uint32_t tbc_version(void);             /* TBC_ABI_VERSION                       */

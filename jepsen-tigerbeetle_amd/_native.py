@@ -154,6 +154,32 @@ class SetFullKeysOut(C.Structure):
                 ("ns_scan", C.c_uint64), ("bytes_scanned", C.c_uint64), ("bytes_matrix", C.c_uint64)]
 
 
+SETFULL_F_LINEARIZABLE = 1
+SETFULL_NEVER_READ, SETFULL_STABLE, SETFULL_LOST = 0, 1, 2
+SETFULL_VALID_FALSE, SETFULL_VALID_TRUE, SETFULL_VALID_UNKNOWN = 0, 1, 2
+SETFULL_WORST = 8
+
+
+class SetFullTimes(C.Structure):
+    _fields_ = [("op_time", C.POINTER(C.c_int64)), ("time_off", C.POINTER(C.c_uint64)), ("unit", C.c_uint64), ("flags", C.c_uint32),
+                ("reserved0", C.c_uint32)]
+
+
+class SetFullKeySummary(C.Structure):
+    _fields_ = [("attempt_count", C.c_uint32), ("stable_count", C.c_uint32), ("lost_count", C.c_uint32), ("never_read_count", C.c_uint32),
+                ("stale_count", C.c_uint32), ("valid", C.c_uint8), ("stable_q_present", C.c_uint8), ("lost_q_present", C.c_uint8),
+                ("n_worst", C.c_uint8), ("stable_q", C.c_int64 * 5), ("lost_q", C.c_int64 * 5), ("worst_element", C.c_uint32 * SETFULL_WORST),
+                ("worst_known", C.c_uint32 * SETFULL_WORST), ("worst_last_absent", C.c_uint32 * SETFULL_WORST),
+                ("worst_latency", C.c_int64 * SETFULL_WORST)]
+
+
+class SetFullResultsOut(C.Structure):
+    _fields_ = [("outcome", C.POINTER(C.c_uint8)), ("stable_latency", C.POINTER(C.c_int64)), ("lost_latency", C.POINTER(C.c_int64)),
+                ("known", C.POINTER(C.c_uint32)), ("last_present", C.POINTER(C.c_uint32)), ("last_absent", C.POINTER(C.c_uint32)),
+                ("summary", C.POINTER(SetFullKeySummary)), ("ns_scan", C.c_uint64), ("ns_results", C.c_uint64), ("bytes_scanned", C.c_uint64),
+                ("bytes_matrix", C.c_uint64)]
+
+
 class BatchInput(C.Structure):
     """tbc_batch_input: pointers into one pinned slot of a batch (tbc_batch_map_input)."""
     _fields_ = [("n_hist_cap", C.c_uint32), ("reserved0", C.c_uint32), ("ops_cap", C.c_uint64),
@@ -219,6 +245,8 @@ SYMBOLS = {
     "tbc_setfull_keys_create": (C.c_int, [C.POINTER(SetFullKeysIn), C.POINTER(C.c_void_p)]),
     "tbc_setfull_keys_run": (C.c_int, [C.c_void_p, C.POINTER(SetFullKeysOut)]),
     "tbc_setfull_keys_destroy": (None, [C.c_void_p]),
+    "tbc_setfull_results": (C.c_int, [C.c_void_p, C.POINTER(SetFullTimes), C.POINTER(SetFullResultsOut)]),
+    "tbc_setfull_keys_results": (C.c_int, [C.c_void_p, C.POINTER(SetFullTimes), C.POINTER(SetFullResultsOut)]),
     "tbc_batch_destroy": (None, [C.c_void_p]),
     "tbc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "tbc_comm_init": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),

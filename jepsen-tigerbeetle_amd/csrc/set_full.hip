@@ -40,34 +40,15 @@
 #include <cstring>
 #include <new>
 #include "tbc_internal.h"
+#include "set_full_plan.h"
 
 using namespace tbc;
 
 namespace {
 
-constexpr uint32_t kNoneU = 0xFFFFFFFFu;
 constexpr uint32_t kSetFullRows = 2048;      // rows per chunk at most (their metadata is staged in LDS)
 constexpr uint32_t kWordCounters = 256;      // the words-loaded statistic: a wavefront adds to counter (its workgroup mod 256), 128 B apart -- thousands of
                                              // atomics on ONE address queue up in one L2 channel; the host adds the counters up
-
-// ---- the plan: every object holds n_keys keys (tbc_setfull_create / _create_rows: one) in ONE arena, and each pass is ONE launch over
-// the tiles of all keys.  The plan table (built on the host at create) gives each key its arrays' offsets, its chunking and the first tile
-// of each grid; a workgroup finds its key by a binary search over those first tiles (uniform across the workgroup: scalar loads) and
-// then works on that key alone.  Each key's pitch is a multiple of four words, so every 16 B load and store of the scan is aligned; the
-// bits at or above a key's E never count (the kernels mask them, and the padding words of a row are zeros).
-struct SfKeyPlan {                 // one key (device table; offsets in 32-bit words)
-  uint32_t E, R, WPR, PITCH, rows_per_chunk, chunks, elem_base, row_base;
-  uint32_t pmax_off, any_gy;
-  unsigned long long m_off, sum_off;
-};
-enum { kFirstRows = 0, kFirstPrefix, kFirstAny, kFirstResolve, kFirsts };   // first[g * (n_keys + 1) + k]: key k's first tile in grid g
-
-// the last key whose first tile (row) is <= b: keys with no tile share their successor's first and are never picked for a tile of theirs
-__device__ __forceinline__ uint32_t sf_find_key(const uint32_t* __restrict__ first, uint32_t n_keys, uint32_t b) {
-  uint32_t lo = 0, hi = n_keys;
-  while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (first[mid] <= b) lo = mid; else hi = mid; }
-  return lo;
-}
 
 __global__ __launch_bounds__(256) void setfull_prefix_kernel(const SfKeyPlan* __restrict__ plan, const uint32_t* __restrict__ first, uint32_t n_keys,
                                                              const uint32_t* add_invoke, const uint32_t* read_ok, uint32_t* P, uint32_t* pmax) {
@@ -527,6 +508,8 @@ constexpr size_t kCounterBytes = (size_t)kWordCounters * 128;
 
 }  // namespace
 
+#include "set_full_results.h"
+
 // One object behind all three entry points: a single key (tbc_setfull) is a keyed object with n_keys = 1.
 struct SfObject {
   int device = 0;
@@ -541,10 +524,20 @@ struct SfObject {
   void* arena = nullptr;            // ONE allocation holds every array above and the inputs: one hipMalloc, one hipFree
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // tbc_setfull_results: the greatest op index among each key's inputs (-1: none), recorded at create; the results' own arena (made by
+  // the first call, again when a call brings more times than it holds) and events
+  std::vector<int64_t> key_max;
+  uint32_t tiles_select = 0;
+  void* res_arena = nullptr;
+  uint64_t res_times = 0;
+  hipEvent_t ev2 = nullptr, ev3 = nullptr;
   ~SfObject() {
     if (arena) (void)hipFree(arena);
+    if (res_arena) (void)hipFree(res_arena);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
+    if (ev2) (void)hipEventDestroy(ev2);
+    if (ev3) (void)hipEventDestroy(ev3);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -633,6 +626,7 @@ tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, 
   uint64_t m_words = 0, sum_words = 0, pmax_words = 0, tiles[kFirsts] = {};
   const auto up = [](uint64_t x, uint64_t a) { return (x + a - 1) / a * a; };
   uint32_t eb = 0, rb = 0;
+  try { S->key_max.assign(n, -1); } catch (const std::bad_alloc&) { set_error("%s: host memory", fn); return TBC_ERR_OOM; }
   for (uint32_t k = 0; k < n; k++) {
     SfKeyPlan& p = plan[k];
     p = SfKeyPlan{};
@@ -652,6 +646,15 @@ tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, 
     first[kFirstAny * (n + 1) + k] = (uint32_t)tiles[kFirstAny]; tiles[kFirstAny] += scan ? (uint64_t)p.chunks * p.any_gy : 0u;
     if (nb && nb % 8u == 0u) tiles[kFirstResolve] = up(tiles[kFirstResolve], 8);
     first[kFirstResolve * (n + 1) + k] = (uint32_t)tiles[kFirstResolve]; tiles[kFirstResolve] += nb;
+    first[kFirstSelect * (n + 1) + k] = (uint32_t)tiles[kFirstSelect]; tiles[kFirstSelect] += (p.E + kSelTile - 1u) / kSelTile;
+    {   // (add_invoke and read_invoke ascend: their last entries are their greatest; add_ok may be TBC_NO_OP)
+      int64_t mx = -1;
+      if (p.E) mx = std::max<int64_t>(mx, in->add_invoke[eb + p.E - 1u]);
+      for (uint32_t e = 0; e < p.E; e++) if (in->add_ok[eb + e] != kNoneU) mx = std::max<int64_t>(mx, in->add_ok[eb + e]);
+      if (p.R) mx = std::max<int64_t>(mx, in->read_invoke[rb + p.R - 1u]);
+      for (uint32_t r = 0; r < p.R; r++) mx = std::max<int64_t>(mx, in->read_ok[rb + r]);
+      S->key_max[k] = mx;
+    }
     S->bytes_matrix += (uint64_t)p.R * (dense ? dense->words_per_row : p.WPR) * 4;
     eb += p.E; rb += p.R;
   }
@@ -660,7 +663,7 @@ tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, 
   if (pmax_words >= 0xFFFFFFFFull || tiles[kFirstAny] >= 0x7FFFFFFFull || tiles[kFirstResolve] >= 0x7FFFFFFFull) {
     set_error("%s: too many elements for one object", fn); return TBC_ERR_INVALID_ARG;
   }
-  S->tiles_any = (uint32_t)tiles[kFirstAny]; S->tiles_resolve = (uint32_t)tiles[kFirstResolve];
+  S->tiles_any = (uint32_t)tiles[kFirstAny]; S->tiles_resolve = (uint32_t)tiles[kFirstResolve]; S->tiles_select = (uint32_t)tiles[kFirstSelect];
   // ---- one arena (round 6: fourteen hipMalloc and as many hipFree -- each of which waits for the device -- were most of a caller's 5 ms
   // around a 0.16 ms scan; the reference checks one history per call site, set_full.clj:157, so create + run + destroy IS its time to
   // verdict): what the host makes (plan, first tiles, the prefix extremes' start values), the caller's arrays, then what the device makes
@@ -732,11 +735,10 @@ tbc_status sf_new(const char* fn, bool keyed, const tbc_setfull_keys_in* in, uin
 
 // The run behind both: the scan's two launches between the events, then the results (n_elements each, key after key) and the counters back,
 // each array straight into the caller's
-tbc_status sf_run(SfObject* S, uint32_t* known, uint32_t* last_present, uint32_t* last_absent, uint64_t* ns_scan, uint64_t* bytes_scanned, uint64_t* bytes_matrix) {
-  SF_TRY(hipSetDevice(S->device));
+// the scan's two launches between its events (ev0, ev1), on the object's stream: what run and results share
+tbc_status sf_scan(SfObject* S) {
   hipStream_t s = S->stream;
   const uint32_t n = S->n_keys;
-  const size_t e4 = (size_t)S->sumE * 4;
   uint32_t* const d_known = S->d_out; uint32_t* const d_lp = S->d_out + S->sumE; uint32_t* const d_la = S->d_out + 2ull * S->sumE;
   SF_TRY(hipMemsetAsync(S->d_words, 0, kCounterBytes, s));
   SF_TRY(hipEventRecord(S->ev0, s));
@@ -748,6 +750,15 @@ tbc_status sf_run(SfObject* S, uint32_t* known, uint32_t* last_present, uint32_t
                        S->d_read_ok, S->d_anyp, S->d_anya, S->d_add_ok, d_lp, d_la, d_known, S->d_words);
   SF_TRY(hipGetLastError());
   SF_TRY(hipEventRecord(S->ev1, s));
+  return TBC_OK;
+}
+
+tbc_status sf_run(SfObject* S, uint32_t* known, uint32_t* last_present, uint32_t* last_absent, uint64_t* ns_scan, uint64_t* bytes_scanned, uint64_t* bytes_matrix) {
+  SF_TRY(hipSetDevice(S->device));
+  hipStream_t s = S->stream;
+  const size_t e4 = (size_t)S->sumE * 4;
+  uint32_t* const d_known = S->d_out; uint32_t* const d_lp = S->d_out + S->sumE; uint32_t* const d_la = S->d_out + 2ull * S->sumE;
+  { const tbc_status st = sf_scan(S); if (st != TBC_OK) return st; }
   if (e4) {
     SF_TRY(hipMemcpyAsync(known, d_known, e4, hipMemcpyDeviceToHost, s));
     SF_TRY(hipMemcpyAsync(last_present, d_lp, e4, hipMemcpyDeviceToHost, s));
@@ -762,6 +773,96 @@ tbc_status sf_run(SfObject* S, uint32_t* known, uint32_t* last_present, uint32_t
   *ns_scan = (uint64_t)(ms * 1e6);
   *bytes_scanned = (uint64_t)words * 4;
   *bytes_matrix = S->bytes_matrix;
+  return TBC_OK;
+}
+
+// The results behind both handles: every rule of the call on the host first; then the times up, the scan, the deciding passes
+// (set_full_results.h) between their own events, and the arrays and summaries back, each straight into the caller's.
+tbc_status sf_results(const char* fn, SfObject* S, const tbc_setfull_times* times, tbc_setfull_results_out* out) {
+  if (!S || !times || !out || !out->summary || (S->sumE && (!out->outcome || !out->stable_latency || !out->lost_latency)) ||
+      (times->op_time && !times->time_off)) {
+    set_error("%s: null argument", fn);
+    return TBC_ERR_INVALID_ARG;
+  }
+  if (times->unit == 0) { set_error("%s: unit is 0", fn); return TBC_ERR_INVALID_ARG; }
+  if (times->reserved0 != 0 || (times->flags & ~TBC_SETFULL_F_LINEARIZABLE)) { set_error("%s: unknown flags / reserved0 not 0", fn); return TBC_ERR_INVALID_ARG; }
+  const uint32_t n = S->n_keys;
+  uint64_t T = 0;
+  if (times->op_time) {
+    for (uint32_t k = 0; k < n; k++) {
+      const uint64_t a = times->time_off[k], b = times->time_off[k + 1];
+      if (b < a || (S->key_max[k] >= 0 && b - a <= (uint64_t)S->key_max[k])) {
+        set_error("%s: key %u: %llu times, but the key's inputs name op %lld", fn, k, (unsigned long long)(b < a ? 0 : b - a), (long long)S->key_max[k]);
+        return TBC_ERR_INVALID_ARG;
+      }
+    }
+    if (times->time_off[0] != 0) { set_error("%s: key 0: time_off[0] must be 0", fn); return TBC_ERR_INVALID_ARG; }
+    T = times->time_off[n];
+  }
+  SF_TRY(hipSetDevice(S->device));
+  hipStream_t s = S->stream;
+  const size_t sumE = S->sumE;
+  // ---- the results' arena: accumulators, select state, histograms, summaries | offsets, per-element arrays, times
+  size_t cursor = 0;
+  const auto take = [&](size_t bytes) { const size_t at = cursor; cursor += (bytes + 255) & ~(size_t)255; return at; };
+  const size_t o_acc = take(sizeof(SfKeyAcc) * n), o_sel = take(sizeof(SfSel) * kSelTargets * n), o_hist = take((size_t)4 * kSelTargets * kSelBins * n),
+               o_sum = take(sizeof(tbc_setfull_key_summary) * n), o_toff = take((size_t)8 * (n + 1)), o_oc = take(sumE), o_sl = take(sumE * 8),
+               o_ll = take(sumE * 8), o_time = take((size_t)std::max<uint64_t>(T, S->res_times) * 8);
+  if (!S->res_arena || T > S->res_times) {
+    if (S->res_arena) { SF_TRY(hipStreamSynchronize(s)); SF_TRY(hipFree(S->res_arena)); S->res_arena = nullptr; }
+    SF_TRY(hipMalloc(&S->res_arena, std::max<size_t>(cursor, 256)));
+    S->res_times = std::max<uint64_t>(T, S->res_times);
+    SF_TRY(hipMemsetAsync(S->res_arena, 0, o_toff, s));         // (select state and histograms start at zero; every pick leaves its histogram zeroed)
+    if (!S->ev2) { SF_TRY(hipEventCreate(&S->ev2)); SF_TRY(hipEventCreate(&S->ev3)); }
+  }
+  char* const R0 = static_cast<char*>(S->res_arena);
+  SfResArgs A;
+  A.plan = S->d_plan; A.first = S->d_first; A.n_keys = n; A.flags = times->flags;
+  A.known = S->d_out; A.lp = S->d_out + S->sumE; A.la = S->d_out + 2ull * S->sumE;
+  A.op_time = times->op_time ? (const long long*)(R0 + o_time) : nullptr;
+  A.time_off = (const unsigned long long*)(R0 + o_toff);
+  A.unit = times->op_time ? times->unit : 1ull;
+  A.outcome = (uint8_t*)(R0 + o_oc); A.slat = (long long*)(R0 + o_sl); A.llat = (long long*)(R0 + o_ll);
+  A.acc = (SfKeyAcc*)(R0 + o_acc); A.sel = (SfSel*)(R0 + o_sel); A.hist = (uint32_t*)(R0 + o_hist); A.summary = (tbc_setfull_key_summary*)(R0 + o_sum);
+  if (times->op_time) {
+    SF_TRY(hipMemcpyAsync(R0 + o_toff, times->time_off, (size_t)8 * (n + 1), hipMemcpyHostToDevice, s));
+    if (T) SF_TRY(hipMemcpyAsync(R0 + o_time, times->op_time, (size_t)T * 8, hipMemcpyHostToDevice, s));
+  }
+  { const tbc_status st = sf_scan(S); if (st != TBC_OK) return st; }
+  SF_TRY(hipEventRecord(S->ev2, s));
+  const uint32_t key_blocks = (n + 255u) / 256u;
+  hipLaunchKernelGGL(sf_results_init_kernel, dim3(key_blocks), dim3(256), 0, s, A);
+  if (S->tiles_select) {
+    hipLaunchKernelGGL(sf_decide_kernel, dim3(S->tiles_select), dim3(256), 0, s, A);
+    for (uint32_t level = 8; level-- > 0;) {
+      hipLaunchKernelGGL(sf_select_hist_kernel, dim3(S->tiles_select), dim3(256), 0, s, A, level);
+      hipLaunchKernelGGL(sf_select_pick_kernel, dim3(n), dim3(kSelTargets * 64), 0, s, A, level);
+    }
+    hipLaunchKernelGGL(sf_worst_collect_kernel, dim3(S->tiles_select), dim3(256), 0, s, A);
+  }
+  hipLaunchKernelGGL(sf_results_final_kernel, dim3(key_blocks), dim3(256), 0, s, A);
+  SF_TRY(hipGetLastError());
+  SF_TRY(hipEventRecord(S->ev3, s));
+  if (sumE) {
+    SF_TRY(hipMemcpyAsync(out->outcome, A.outcome, sumE, hipMemcpyDeviceToHost, s));
+    SF_TRY(hipMemcpyAsync(out->stable_latency, A.slat, sumE * 8, hipMemcpyDeviceToHost, s));
+    SF_TRY(hipMemcpyAsync(out->lost_latency, A.llat, sumE * 8, hipMemcpyDeviceToHost, s));
+    if (out->known) SF_TRY(hipMemcpyAsync(out->known, A.known, sumE * 4, hipMemcpyDeviceToHost, s));
+    if (out->last_present) SF_TRY(hipMemcpyAsync(out->last_present, A.lp, sumE * 4, hipMemcpyDeviceToHost, s));
+    if (out->last_absent) SF_TRY(hipMemcpyAsync(out->last_absent, A.la, sumE * 4, hipMemcpyDeviceToHost, s));
+  }
+  SF_TRY(hipMemcpyAsync(out->summary, A.summary, sizeof(tbc_setfull_key_summary) * n, hipMemcpyDeviceToHost, s));
+  SF_TRY(hipMemcpyAsync(S->h_words, S->d_words, kCounterBytes, hipMemcpyDeviceToHost, s));
+  SF_TRY(hipStreamSynchronize(s));
+  float ms_scan = 0, ms_res = 0;
+  SF_TRY(hipEventElapsedTime(&ms_scan, S->ev0, S->ev1));
+  SF_TRY(hipEventElapsedTime(&ms_res, S->ev2, S->ev3));
+  unsigned long long words = 0;
+  for (uint32_t k = 0; k < kWordCounters; k++) words += S->h_words[16u * k];
+  out->ns_scan = (uint64_t)(ms_scan * 1e6);
+  out->ns_results = (uint64_t)(ms_res * 1e6);
+  out->bytes_scanned = (uint64_t)words * 4;
+  out->bytes_matrix = S->bytes_matrix;
   return TBC_OK;
 }
 
@@ -823,6 +924,13 @@ tbc_status tbc_setfull_keys_run(tbc_setfull_keys* handle, tbc_setfull_keys_out* 
   SfObject* const S = sf_obj(handle);
   if (!S || !out || (S->sumE && (!out->known || !out->last_present || !out->last_absent))) { set_error("tbc_setfull_keys_run: null argument"); return TBC_ERR_INVALID_ARG; }
   return sf_run(S, out->known, out->last_present, out->last_absent, &out->ns_scan, &out->bytes_scanned, &out->bytes_matrix);
+}
+
+tbc_status tbc_setfull_results(tbc_setfull* handle, const tbc_setfull_times* times, tbc_setfull_results_out* out) {
+  return sf_results("tbc_setfull_results", sf_obj(handle), times, out);
+}
+tbc_status tbc_setfull_keys_results(tbc_setfull_keys* handle, const tbc_setfull_times* times, tbc_setfull_results_out* out) {
+  return sf_results("tbc_setfull_keys_results", sf_obj(handle), times, out);
 }
 
 void tbc_setfull_destroy(tbc_setfull* handle) { sf_destroy(sf_obj(handle)); }

@@ -107,18 +107,20 @@ class IndependentChecker(jc.Checker):
 
     def _check_set_full(self, keys, subs, members, opts):
         """set-full (alone or composed, set_full.clj:155-158) over all keys: every key encoded once, every key's matrix scanned in one
-        device pass (jepsen/set_full.py scan_keys), each set-full member's result map from the same scan, read-all-invoked-adds from
+        device pass and decided there (jepsen/set_full.py results_keys), each set-full member's result map from that, read-all-invoked-adds from
         the same encoding, linearizable members as one batch.  Per key what Compose.check / SetFull.check give on its sub-history."""
         from . import set_full as sf
         encs = {k: sf.Encoded(subs[k]) for k in keys}
-        sts = sf.scan_keys(encs, device=(opts or {}).get("device", 0))
+        # (one scan and one deciding pass per :linearizable? value among the set-full members -- the flag is the device's to apply)
+        devs = {flag: sf.results_keys(encs, flag, device=(opts or {}).get("device", 0))
+                for flag in sorted({c.linearizable for c in members.values() if isinstance(c, jc.SetFull)})}
         lin = {name: IndependentChecker(c)._check_batched(keys, subs) for name, c in members.items() if isinstance(c, jc.Linearizable)}
         out = {}
         for k in keys:
             res = {}
             for name, c in members.items():
                 if isinstance(c, jc.SetFull):
-                    res[name] = sf.result_map(encs[k], sts[k], c.linearizable)
+                    res[name] = sf.result_from_device(encs[k], devs[c.linearizable][k])
                 elif isinstance(c, jc.ReadAllInvokedAdds):
                     res[name] = sf.read_all_invoked_adds(subs[k], encs[k])
                 else:

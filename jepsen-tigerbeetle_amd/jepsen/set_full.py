@@ -3,9 +3,12 @@
 `(independent/checker (checker/compose {:set-full (checker/set-full {:linearizable? true}) ...}))`).
 
 Host side: flatten the history into the reads x elements membership matrix and four index columns, call
-`tbc_setfull_*` (csrc/set_full.hip scans the matrix for known / last-present / last-absent per element), turn the
-three indices into jepsen's result map (:valid? :attempt-count :stable-count :lost :never-read :stale :worst-stale
-...).  The semantics are recalled from jepsen.checker (jepsen is not in /root/reference and cannot run here) and
+`tbc_setfull_*` (csrc/set_full.hip scans the matrix for known / last-present / last-absent per element;
+csrc/set_full_results.h decides every element's outcome and latencies and every key's counts, :valid?, latency
+quantiles and worst stale elements from them, on the device), and name the elements in jepsen's result map
+(:valid? :attempt-count :stable-count :lost :never-read :stale :worst-stale ...: `result_from_device`).  `result_map`
+is the host statement of the same arithmetic from the three indices, kept for the tests to compare with.  The
+semantics are recalled from jepsen.checker (jepsen is not in /root/reference and cannot run here) and
 restated independently in oracle/set_full.py, which the tests compare with.  No CPU fallback: without a GPU
 `check` raises NoDeviceError."""
 from __future__ import annotations
@@ -33,6 +36,14 @@ class Encoded:
         hist = [op for op in H.index(list(history)) if H.client_op(op)]
         self.has_time = all("time" in op for op in hist) and bool(hist)
         self.times = {op["index"]: op.get("time", op["index"]) for op in hist}
+        # the same as ONE column for the device (tbc_setfull_times.op_time: a slot per op of the history, client op or not), built once;
+        # None when no op carries :time -- the library then takes the op index, as `times` does
+        self.n_ops = (hist[-1]["index"] + 1) if hist else 0
+        self.unit = 1_000_000 if self.has_time else 1
+        self.op_time = None
+        if any("time" in op for op in hist):
+            self.op_time = np.zeros(self.n_ops, np.int64)
+            self.op_time[[op["index"] for op in hist]] = [self.times[op["index"]] for op in hist]
         last_invoke, add_ok, reads, open_reads = {}, {}, [], {}
         self.duplicated = {}
         for op in hist:
@@ -140,6 +151,30 @@ class _Handle:
         N.check_status(getattr(N.lib(), self._run)(self._h, C.byref(o)))
         return known, lp, la, {"ns_scan": o.ns_scan, "bytes_scanned": o.bytes_scanned, "bytes_matrix": o.bytes_matrix}
 
+    def _decide(self, n_elements, n_keys, op_time, time_off, unit, linearizable, indices=False):
+        """tbc_setfull_results / tbc_setfull_keys_results: -> per-element arrays over all keys, the per-key summaries (a ctypes array) and
+        the call's totals.  op_time: one int64 array over all keys (time_off its n_keys + 1 offsets) or None (time = the op index)."""
+        n = max(1, int(n_elements))
+        outcome, slat, llat = np.zeros(n, np.uint8), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        summary = (N.SetFullKeySummary * max(1, int(n_keys)))()
+        t = N.SetFullTimes()
+        keep = None
+        if op_time is not None:
+            keep = (np.ascontiguousarray(op_time if len(op_time) else np.zeros(1, np.int64), np.int64), np.ascontiguousarray(time_off, np.uint64))
+            t.op_time, t.time_off = _p(keep[0], C.c_int64), _p(keep[1], C.c_uint64)
+        t.unit, t.flags, t.reserved0 = int(unit), (N.SETFULL_F_LINEARIZABLE if linearizable else 0), 0
+        o = N.SetFullResultsOut()
+        o.outcome, o.stable_latency, o.lost_latency = _p(outcome, C.c_uint8), _p(slat, C.c_int64), _p(llat, C.c_int64)
+        o.summary = summary
+        arrays = {"outcome": outcome, "stable_latency": slat, "lost_latency": llat}
+        if indices:
+            for f in ("known", "last_present", "last_absent"):
+                arrays[f] = np.zeros(n, np.uint32)
+                setattr(o, f, _p(arrays[f], C.c_uint32))
+        N.check_status(getattr(N.lib(), self._results)(self._h, C.byref(t), C.byref(o)))
+        tot = {"ns_scan": o.ns_scan, "ns_results": o.ns_results, "bytes_scanned": o.bytes_scanned, "bytes_matrix": o.bytes_matrix}
+        return arrays, summary, tot
+
     def close(self):
         if self._h:
             getattr(N.lib(), self._destroy)(self._h)
@@ -154,7 +189,7 @@ class _Handle:
 
 class Scan(_Handle):
     """tbc_setfull_*: the matrix resident in HBM, `run()` scans it."""
-    _run, _destroy, _Out = "tbc_setfull_run", "tbc_setfull_destroy", N.SetFullOut
+    _run, _destroy, _Out, _results = "tbc_setfull_run", "tbc_setfull_destroy", N.SetFullOut, "tbc_setfull_results"
 
     def __init__(self, enc_or_arrays, device=0, rows=None):
         """rows: True = hand the reads over in compact form (top / exc_off / exc: tbc_setfull_create_rows, the matrix is built on
@@ -189,6 +224,14 @@ class Scan(_Handle):
     def run(self):
         known, lp, la, tot = self._scan(self.E)
         return {"known": known[:self.E], "last_present": lp[:self.E], "last_absent": la[:self.E], **tot}
+
+    def results(self, times=None, unit=1, linearizable=False, indices=False):
+        """The check result from the device (tbc_setfull_results): -> {"outcome", "stable_latency", "lost_latency" per element,
+        "summary": the key's summary as a dict, "ns_scan", "ns_results", ...}.  times: the :time of every op of the history by op index
+        (an int64 array, `Encoded.op_time`) or None = the op index; unit: what one latency unit is in those times (1,000,000: ns -> ms)."""
+        off = None if times is None else np.array([0, len(times)], np.uint64)
+        arrays, summary, tot = self._decide(self.E, 1, times, off, unit, linearizable, indices)
+        return {**{f: a[:self.E] for f, a in arrays.items()}, "summary": summary_dict(summary[0]), **tot}
 
 
 def frequency_distribution(points, xs):
@@ -246,11 +289,47 @@ def _sorted(xs):
         return xs
 
 
+QUANTILE_POINTS = (0, 0.5, 0.95, 0.99, 1)
+_VALID = {N.SETFULL_VALID_FALSE: False, N.SETFULL_VALID_TRUE: True, N.SETFULL_VALID_UNKNOWN: "unknown"}
+
+
+def summary_dict(s):
+    """A tbc_setfull_key_summary as plain Python values."""
+    nw = int(s.n_worst)
+    none = lambda x: None if x == NONE else int(x)
+    return {"attempt_count": int(s.attempt_count), "stable_count": int(s.stable_count), "lost_count": int(s.lost_count),
+            "never_read_count": int(s.never_read_count), "stale_count": int(s.stale_count), "valid": _VALID[int(s.valid)],
+            "stable_q": list(s.stable_q) if s.stable_q_present else None, "lost_q": list(s.lost_q) if s.lost_q_present else None,
+            "worst": [{"element": int(s.worst_element[i]), "latency": int(s.worst_latency[i]), "known": none(s.worst_known[i]),
+                       "last_absent": none(s.worst_last_absent[i])} for i in range(nw)]}
+
+
+def result_from_device(enc: Encoded, dev: dict):
+    """jepsen.checker/set-full's result map from what the device decided (`Scan.results` / `KeyedScan.results`: the outcome byte and
+    the stable latency per element, the key's summary): nothing is computed here but WHICH elements the lists name -- np.nonzero over
+    the outcome bytes -- and the one thing the device cannot know, the encoder's duplicates, which make any verdict false."""
+    oc, s, el = dev["outcome"], dev["summary"], enc.elements
+    names = lambda mask: _sorted([el[i] for i in np.nonzero(mask)[0].tolist()])
+    dups = dict(sorted(getattr(enc, "duplicated", {}).items(), key=lambda kv: repr(kv[0])))
+    out = {"valid?": False if dups else s["valid"],     # (and (empty? dups) (:valid? results)): nil / :unknown -> falsey
+           "attempt-count": s["attempt_count"], "stable-count": s["stable_count"], "lost-count": s["lost_count"],
+           "lost": names(oc == N.SETFULL_LOST), "never-read-count": s["never_read_count"], "never-read": names(oc == N.SETFULL_NEVER_READ),
+           "stale-count": s["stale_count"], "stale": names((oc == N.SETFULL_STABLE) & (dev["stable_latency"] > 0)),
+           "worst-stale": [{"element": el[w["element"]], "outcome": "stable", "stable-latency": w["latency"], "lost-latency": None,
+                            "known": w["known"], "last-absent": w["last_absent"]} for w in s["worst"]],
+           "duplicated-count": len(dups), "duplicated": dups}
+    if s["stable_q"] is not None:
+        out["stable-latencies"] = dict(zip(QUANTILE_POINTS, s["stable_q"]))
+    if s["lost_q"] is not None:
+        out["lost-latencies"] = dict(zip(QUANTILE_POINTS, s["lost_q"]))
+    return out
+
+
 def check(history, linearizable=False, device=0):
     enc = Encoded(history)
     with Scan(enc, device) as s:
-        st = s.run()
-    return result_map(enc, st, linearizable)
+        dev = s.results(enc.op_time, enc.unit, linearizable)
+    return result_from_device(enc, dev)
 
 
 # ---------------------------------------------------------------------------------------------------- many keys, one device pass
@@ -266,7 +345,7 @@ def _matrix_bytes(enc):
 class KeyedScan(_Handle):
     """tbc_setfull_keys_*: the compact reads of MANY keys (each an `Encoded`) resident in one object; `run()` scans all of them in one
     fixed sequence of launches and returns each key's known / last-present / last-absent, in the order the encodings were given."""
-    _run, _destroy, _Out = "tbc_setfull_keys_run", "tbc_setfull_keys_destroy", N.SetFullKeysOut
+    _run, _destroy, _Out, _results = "tbc_setfull_keys_run", "tbc_setfull_keys_destroy", N.SetFullKeysOut, "tbc_setfull_keys_results"
 
     def __init__(self, encs, device=0):
         encs = list(encs)
@@ -297,6 +376,19 @@ class KeyedScan(_Handle):
         per = [{"known": known[a:b], "last_present": lp[a:b], "last_absent": la[a:b]} for a, b in zip(cut[:-1], cut[1:])]
         return per, tot
 
+    def results(self, times=None, unit=1, linearizable=False, indices=False):
+        """tbc_setfull_keys_results: -> ([per key what `Scan.results` gives without the totals], the totals of the whole object).
+        times: per key an int64 array (the :time of every op of the key's history by op index), or None = the op index for every key."""
+        op_time = off = None
+        if times is not None:
+            times = [np.asarray(t, np.int64) for t in times]
+            off = np.concatenate([[0], np.cumsum([len(t) for t in times], dtype=np.int64)]).astype(np.uint64)
+            op_time = np.concatenate(times + [np.zeros(0, np.int64)])
+        arrays, summary, tot = self._decide(self.Es.sum(), len(self.Es), op_time, off, unit, linearizable, indices)
+        cut = np.concatenate([[0], np.cumsum(self.Es, dtype=np.int64)])
+        per = [{**{f: x[a:b] for f, x in arrays.items()}, "summary": summary_dict(summary[k])} for k, (a, b) in enumerate(zip(cut[:-1], cut[1:]))]
+        return per, tot
+
 
 def groups_within_budget(encs, budget=None):
     """The keys (a list of (key, Encoded)) in order, cut into runs of at most `budget` matrix bytes each (a larger key alone)."""
@@ -324,14 +416,33 @@ def scan_keys(encs, device=0):
     return out
 
 
+def _time_column(enc):
+    return enc.op_time if enc.op_time is not None else np.arange(enc.n_ops, dtype=np.int64)
+
+
+def results_keys(encs, linearizable=False, device=0):
+    """{k: Encoded} -> {k: what the device decided for the key (`KeyedScan.results`)}: one keyed object, one scan and one deciding pass
+    per budget group.  A call has ONE latency unit: keys whose ops all carry :time (ns -> ms) and keys that lack some go in calls of
+    their own."""
+    out = {}
+    for unit in sorted({e.unit for e in encs.values()}):
+        part = [(k, e) for k, e in encs.items() if e.unit == unit]
+        for grp in groups_within_budget(part):
+            times = None if all(e.op_time is None for _, e in grp) else [_time_column(e) for _, e in grp]
+            with KeyedScan([e for _, e in grp], device) as ks:
+                per, _ = ks.results(times, unit, linearizable)
+            out.update({k: dev for (k, _), dev in zip(grp, per)})
+    return {k: out[k] for k in encs}
+
+
 def check_keys(histories, linearizable=False, device=0):
-    """{k: history} -> {k: set-full result}: each key encoded as `check` encodes it, all keys scanned in one device pass per budget
-    group; per key exactly what `check(history, linearizable)` gives."""
+    """{k: history} -> {k: set-full result}: each key encoded as `check` encodes it, all keys scanned and decided in one device pass
+    per budget group; per key exactly what `check(history, linearizable)` gives."""
     if not histories:
         return {}
     encs = {k: Encoded(h) for k, h in histories.items()}
-    sts = scan_keys(encs, device)
-    return {k: result_map(encs[k], sts[k], linearizable) for k in encs}
+    devs = results_keys(encs, linearizable, device)
+    return {k: result_from_device(encs[k], devs[k]) for k in encs}
 
 
 # ---------------------------------------------------------------------------------------------------- read-all-invoked-adds
