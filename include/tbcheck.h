@@ -753,6 +753,71 @@ typedef struct tbc_setfull_results_out {             /* arrays caller-allocated,
 tbc_status tbc_setfull_results(tbc_setfull* handle, const tbc_setfull_times* times, tbc_setfull_results_out* out);
 tbc_status tbc_setfull_keys_results(tbc_setfull_keys* handle, const tbc_setfull_times* times, tbc_setfull_results_out* out);
 
+/* The history itself, as op columns: tbc_setfull_keys_create_ops takes each key's client ops (in history order) and the raw values of
+ * its reads, and encodes them here -- the caller flattens nothing and knows none of set-full's rules.  The host plans the O(ops) part
+ * (csrc/set_full_encode_plan.h): which value is which column, which :ok read belongs to which invocation.  The device does the
+ * O(values) part (csrc/set_full_encode.h): every value of every read is looked up in a hash table of its key's elements and its bit
+ * set in the read's row; duplicates are found on the way.  The handle is an ordinary tbc_setfull_keys: _run, _results and _destroy work
+ * on it unchanged, and its matrix is bit for bit the one tbc_setfull_keys_create builds from the compact form of the same history.
+ * A single history is n_keys = 1.
+ *   elements  an element is a distinct :add value.  An :add INVOCATION starts the element afresh: an element added again is numbered
+ *             by its LAST add invocation; elements are numbered in the order of those.  add_ok = the first :ok add of the value after
+ *             that invocation, from any process; an :ok add of a value never invoked is ignored.  An :add with TBC_SETFULL_T_NIL is
+ *             skipped.
+ *   reads     an :ok read is paired with the open read invocation of its process; a :fail closes it; an :info leaves it open until
+ *             the process invokes a read again.  An :ok read with TBC_SETFULL_T_NIL, or without an open invocation, closes the open
+ *             read and is no read; one with an empty value is a read that saw nothing.  Reads are numbered by invocation.  A value
+ *             that names no element of the key is not a column: it is counted in unknown_values and otherwise ignored.
+ * Every rule of the struct is checked on the host before any device call -- non-null pointers, op_off ascending, index strictly
+ * ascending within a key (and never TBC_NO_OP), val_off ascending from 0, type and f in range: TBC_ERR_INVALID_ARG, the message names
+ * the entry point, the key and the op.  Valid input without a gfx950 device: TBC_ERR_NO_DEVICE (no CPU fallback). */
+enum { TBC_SETFULL_T_INVOKE = 0, TBC_SETFULL_T_OK = 1, TBC_SETFULL_T_FAIL = 2, TBC_SETFULL_T_INFO = 3 };
+#define TBC_SETFULL_T_NIL 0x80u          /* or-ed into type: the op's :value is nil */
+enum { TBC_SETFULL_OP_OTHER = 0, TBC_SETFULL_OP_ADD = 1, TBC_SETFULL_OP_READ = 2 };
+/* A read's row is assembled in a window of this many 32-bit words of LDS (csrc/set_full_encode.h); a key of more than 32 x this many
+ * elements takes one pass over the read's values per window. */
+#define TBC_SETFULL_ENCODE_WINDOW_WORDS 8192u
+
+typedef struct tbc_setfull_ops_in {
+  uint32_t n_keys, device;
+  const uint64_t* op_off;   /* [n_keys + 1] key k's client ops are rows op_off[k] .. op_off[k+1], in history order */
+  const uint32_t* index;    /* [n_ops] the op's index in ITS KEY's history (what add_invoke ... are numbered by); strictly ascending per key */
+  const uint8_t*  type;     /* TBC_SETFULL_T_* (| TBC_SETFULL_T_NIL) */
+  const uint8_t*  f;        /* TBC_SETFULL_OP_* ; OTHER is skipped */
+  const int64_t*  process;
+  const int64_t*  value;    /* an :add's element; not read for other ops */
+  const uint64_t* val_off;  /* [n_ops + 1] ascending, val_off[0] = 0: vals[val_off[i] .. val_off[i+1]) = the value of op i if it is an :ok read, else empty */
+  const int64_t*  vals;     /* the reads' values, in any order, repeats allowed */
+} tbc_setfull_ops_in;
+tbc_status tbc_setfull_keys_create_ops(const tbc_setfull_ops_in* in, tbc_setfull_keys** handle);
+
+/* The sums over the object's keys of n_elements and n_reads: what the arrays of tbc_setfull_keys_out, tbc_setfull_results_out and
+ * tbc_setfull_encoding are sized by.  Works on every keyed handle, however it was made. */
+tbc_status tbc_setfull_keys_shape(tbc_setfull_keys* h, uint64_t* sum_elements, uint64_t* sum_reads);
+
+/* What tbc_setfull_keys_create_ops made of the ops: the encoding (what a caller of tbc_setfull_keys_create would have had to compute)
+ * and the two things only the raw values show.
+ *   dup_max / dup_count   an element that occurs more than once in ONE read's value is a duplicate.  dup_count[k] != 0 MAKES KEY k's
+ *                         RESULT FALSE, whatever tbc_setfull_key_summary.valid says: the summary's verdict keeps its documented
+ *                         meaning (duplicates not counted in), and the caller ANDs `dup_count[k] == 0` into it.
+ *   unknown_values        read values that name no element of the key.  They are not columns and do not enter the scan.  DUPLICATES
+ *                         AMONG THEM ARE NOT SEEN by the library (dup_max has a slot per element only): a caller that wants jepsen's
+ *                         `duplicated` in full counts the repeats among a key's unknown values itself -- only keys with
+ *                         unknown_values[k] != 0 can have any.
+ * On a handle that was not made by tbc_setfull_keys_create_ops: TBC_ERR_INVALID_ARG (the message says that the object was not made
+ * from ops). */
+typedef struct tbc_setfull_encoding {          /* every pointer optional (NULL = not wanted); caller-allocated */
+  uint32_t *n_elements, *n_reads;              /* [n_keys] */
+  int64_t*  element;                           /* [sum_elements] the value of each column, key after key */
+  uint32_t *add_invoke, *add_ok;               /* [sum_elements] */
+  uint32_t *read_invoke, *read_ok;             /* [sum_reads] */
+  uint32_t* dup_max;                           /* [sum_elements] greatest multiplicity of the element within ONE read (0 or 1: not duplicated) */
+  uint32_t* dup_count;                         /* [n_keys] elements with dup_max > 1 */
+  uint64_t* unknown_values;                    /* [n_keys] read values that name no element of the key */
+  uint64_t  ns_encode;                         /* device time of the encoding kernels at create (HIP events) */
+} tbc_setfull_encoding;
+tbc_status tbc_setfull_keys_encoding(tbc_setfull_keys* h, tbc_setfull_encoding* out);
+
 /* ------------------------------------------------------------------- misc */
 uint32_t tbc_version(void);             /* TBC_ABI_VERSION                       */
 const char* tbc_strerror(int status);

@@ -180,6 +180,26 @@ class SetFullResultsOut(C.Structure):
                 ("bytes_matrix", C.c_uint64)]
 
 
+# tbc_setfull_keys_create_ops: the history as op columns (include/tbcheck.h TBC_SETFULL_T_* / TBC_SETFULL_OP_*)
+SETFULL_T_INVOKE, SETFULL_T_OK, SETFULL_T_FAIL, SETFULL_T_INFO = 0, 1, 2, 3
+SETFULL_T_NIL = 0x80
+SETFULL_OP_OTHER, SETFULL_OP_ADD, SETFULL_OP_READ = 0, 1, 2
+SETFULL_ENCODE_WINDOW_WORDS = 8192
+
+
+class SetFullOpsIn(C.Structure):
+    _fields_ = [("n_keys", C.c_uint32), ("device", C.c_uint32), ("op_off", C.POINTER(C.c_uint64)), ("index", C.POINTER(C.c_uint32)),
+                ("type", C.POINTER(C.c_uint8)), ("f", C.POINTER(C.c_uint8)), ("process", C.POINTER(C.c_int64)),
+                ("value", C.POINTER(C.c_int64)), ("val_off", C.POINTER(C.c_uint64)), ("vals", C.POINTER(C.c_int64))]
+
+
+class SetFullEncoding(C.Structure):
+    _fields_ = [("n_elements", C.POINTER(C.c_uint32)), ("n_reads", C.POINTER(C.c_uint32)), ("element", C.POINTER(C.c_int64)),
+                ("add_invoke", C.POINTER(C.c_uint32)), ("add_ok", C.POINTER(C.c_uint32)), ("read_invoke", C.POINTER(C.c_uint32)),
+                ("read_ok", C.POINTER(C.c_uint32)), ("dup_max", C.POINTER(C.c_uint32)), ("dup_count", C.POINTER(C.c_uint32)),
+                ("unknown_values", C.POINTER(C.c_uint64)), ("ns_encode", C.c_uint64)]
+
+
 class BatchInput(C.Structure):
     """tbc_batch_input: pointers into one pinned slot of a batch (tbc_batch_map_input)."""
     _fields_ = [("n_hist_cap", C.c_uint32), ("reserved0", C.c_uint32), ("ops_cap", C.c_uint64),
@@ -247,6 +267,9 @@ SYMBOLS = {
     "tbc_setfull_keys_destroy": (None, [C.c_void_p]),
     "tbc_setfull_results": (C.c_int, [C.c_void_p, C.POINTER(SetFullTimes), C.POINTER(SetFullResultsOut)]),
     "tbc_setfull_keys_results": (C.c_int, [C.c_void_p, C.POINTER(SetFullTimes), C.POINTER(SetFullResultsOut)]),
+    "tbc_setfull_keys_create_ops": (C.c_int, [C.POINTER(SetFullOpsIn), C.POINTER(C.c_void_p)]),
+    "tbc_setfull_keys_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "tbc_setfull_keys_encoding": (C.c_int, [C.c_void_p, C.POINTER(SetFullEncoding)]),
     "tbc_batch_destroy": (None, [C.c_void_p]),
     "tbc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "tbc_comm_init": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),

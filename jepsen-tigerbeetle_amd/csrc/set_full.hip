@@ -41,6 +41,7 @@
 #include <new>
 #include "tbc_internal.h"
 #include "set_full_plan.h"
+#include "set_full_encode_plan.h"
 
 using namespace tbc;
 
@@ -509,11 +510,12 @@ constexpr size_t kCounterBytes = (size_t)kWordCounters * 128;
 }  // namespace
 
 #include "set_full_results.h"
+#include "set_full_encode.h"
 
 // One object behind all three entry points: a single key (tbc_setfull) is a keyed object with n_keys = 1.
 struct SfObject {
   int device = 0;
-  uint32_t n_keys = 0, sumE = 0;
+  uint32_t n_keys = 0, sumE = 0, sumR = 0;
   uint32_t tiles_any = 0, tiles_resolve = 0;
   uint64_t bytes_matrix = 0;
   SfKeyPlan* d_plan = nullptr;
@@ -531,8 +533,21 @@ struct SfObject {
   void* res_arena = nullptr;
   uint64_t res_times = 0;
   hipEvent_t ev2 = nullptr, ev3 = nullptr;
+  // tbc_setfull_keys_create_ops: the plan the host made of the ops (what tbc_setfull_keys_encoding hands back), what the encoding kernels
+  // found, their events, and the reads' raw values on the device -- an allocation of its own, freed before create returns (8 B a value
+  // where the matrix has a bit)
+  bool from_ops = false;
+  sfenc::Plan enc;
+  std::vector<uint32_t> dup_max, dup_count;
+  std::vector<uint64_t> unknown;
+  uint64_t ns_encode = 0;
+  uint32_t h_repeats = 0;
+  void* d_vals = nullptr;
+  hipEvent_t ev_e0 = nullptr, ev_e1 = nullptr, ev_d0 = nullptr, ev_d1 = nullptr;
   ~SfObject() {
     if (arena) (void)hipFree(arena);
+    if (d_vals) (void)hipFree(d_vals);
+    for (hipEvent_t e : {ev_e0, ev_e1, ev_d0, ev_d1}) if (e) (void)hipEventDestroy(e);
     if (res_arena) (void)hipFree(res_arena);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
@@ -600,25 +615,30 @@ uint32_t sf_chunks(uint32_t WPR, uint32_t R) {
 
 // The create behind all three entry points.  `in`: the keys' arrays end to end (tbc_setfull_keys_in; the single-key entries point it at
 // their own one key), sumE / sumR its totals; `keyed`: name the key in a message.  `dense` (tbc_setfull_create only, one key): the
-// caller's matrix is copied into the key's pitch where the other entries build the matrix from top / exc.
-tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, uint32_t sumE, uint32_t sumR, const tbc_setfull_in* dense, SfObject* S) {
+// caller's matrix is copied into the key's pitch where the other entries build the matrix from top / exc.  `ops`
+// (tbc_setfull_keys_create_ops only): `in` holds what the host plan made of the ops (S->enc; no top / exc_off / exc), and the matrix is
+// built from the reads' raw values `vals` by the kernels of set_full_encode.h -- in place of top / exc_off / exc the arena holds the
+// element values, the rows' value slices, the keys' tables and the duplicate counters.
+tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, uint32_t sumE, uint32_t sumR, const tbc_setfull_in* dense, SfObject* S,
+                     const int64_t* ops_vals = nullptr) {
   const uint32_t n = in->n_keys;
+  const bool ops = S->from_ops;
   // ---- every rule, key by key, before any device call
-  if (!dense && in->exc_off[0] != 0) { set_error("%s: exc_off[0] must be 0", fn); return TBC_ERR_INVALID_ARG; }
+  if (!dense && !ops && in->exc_off[0] != 0) { set_error("%s: exc_off[0] must be 0", fn); return TBC_ERR_INVALID_ARG; }
   {
     std::vector<uint32_t> tmp;
     char where[64];
     uint32_t e0 = 0, r0 = 0;
     for (uint32_t k = 0; k < n; e0 += in->n_elements[k], r0 += in->n_reads[k], k++) {
       if (keyed) std::snprintf(where, sizeof where, "%s: key %u", fn, k); else std::snprintf(where, sizeof where, "%s", fn);
-      if (!sf_key_is_valid(where, in->n_elements[k], in->n_reads[k], in->add_invoke + e0, in->read_invoke + r0, dense ? nullptr : in->top + r0,
-                           dense ? nullptr : in->exc_off + r0, in->exc, tmp))
+      if (!sf_key_is_valid(where, in->n_elements[k], in->n_reads[k], in->add_invoke + e0, in->read_invoke + r0, dense || ops ? nullptr : in->top + r0,
+                           dense || ops ? nullptr : in->exc_off + r0, in->exc, tmp))
         return TBC_ERR_INVALID_ARG;
     }
   }
   const tbc_status dev = sf_check_device(in->device);
   if (dev != TBC_OK) return dev;
-  S->device = (int)in->device; S->n_keys = n; S->sumE = sumE;
+  S->device = (int)in->device; S->n_keys = n; S->sumE = sumE; S->sumR = sumR;
   // ---- the plan: per key its chunking (a key of a few reads is one chunk) and its place in the arena's regions; per grid the first tile
   // of every key
   std::vector<SfKeyPlan> plan(n);
@@ -626,7 +646,9 @@ tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, 
   uint64_t m_words = 0, sum_words = 0, pmax_words = 0, tiles[kFirsts] = {};
   const auto up = [](uint64_t x, uint64_t a) { return (x + a - 1) / a * a; };
   uint32_t eb = 0, rb = 0;
-  try { S->key_max.assign(n, -1); } catch (const std::bad_alloc&) { set_error("%s: host memory", fn); return TBC_ERR_OOM; }
+  std::vector<SfEncKey> enc_keys;
+  uint64_t tab_slots = 0;
+  try { S->key_max.assign(n, -1); if (ops) enc_keys.assign(n, SfEncKey{}); } catch (const std::bad_alloc&) { set_error("%s: host memory", fn); return TBC_ERR_OOM; }
   for (uint32_t k = 0; k < n; k++) {
     SfKeyPlan& p = plan[k];
     p = SfKeyPlan{};
@@ -656,6 +678,11 @@ tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, 
       S->key_max[k] = mx;
     }
     S->bytes_matrix += (uint64_t)p.R * (dense ? dense->words_per_row : p.WPR) * 4;
+    if (ops) {
+      const uint64_t cap = sfenc::table_slots(p.E);
+      enc_keys[k].tab_off = tab_slots; enc_keys[k].mask = cap ? (uint32_t)(cap - 1u) : 0u;
+      tab_slots += cap;
+    }
     eb += p.E; rb += p.R;
   }
   first[kFirstRows * (n + 1) + n] = rb;
@@ -667,20 +694,29 @@ tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, 
   // ---- one arena (round 6: fourteen hipMalloc and as many hipFree -- each of which waits for the device -- were most of a caller's 5 ms
   // around a 0.16 ms scan; the reference checks one history per call site, set_full.clj:157, so create + run + destroy IS its time to
   // verdict): what the host makes (plan, first tiles, the prefix extremes' start values), the caller's arrays, then what the device makes
-  const uint64_t ne = dense ? 0 : in->exc_off[sumR];
-  const size_t top4 = dense ? 0 : (size_t)sumR * 4, off8 = dense ? 0 : ((size_t)sumR + 1) * 8;
+  const uint64_t ne = dense || ops ? 0 : in->exc_off[sumR];
+  const size_t top4 = dense || ops ? 0 : (size_t)sumR * 4, off8 = dense || ops ? 0 : ((size_t)sumR + 1) * 8;
   size_t cursor = 0;
   const auto take = [&](size_t bytes) { const size_t at = cursor; cursor += (bytes + 255) & ~(size_t)255; return at; };
   const size_t o_plan = take(sizeof(SfKeyPlan) * n), o_first = take(first.size() * 4), o_pm = take(pmax_words * 4);
+  const size_t o_enc = take(sizeof(SfEncKey) * enc_keys.size());
   const size_t head_bytes = cursor;
   const size_t o_ai = take((size_t)sumE * 4), o_ao = take((size_t)sumE * 4), o_ri = take((size_t)sumR * 4), o_ro = take((size_t)sumR * 4),
                o_top = take(top4), o_off = take(off8), o_exc = take(ne * 4);
   const size_t o_M = take(m_words * 4), o_P = take((size_t)sumR * 4), o_any = take(sum_words * 8);
   const size_t o_out = take((size_t)sumE * 12), o_w = take(kCounterBytes);
+  // (tbc_setfull_keys_create_ops) the element values and the rows' value slices; then what starts as zeros, side by side: the tables, the
+  // rows' and keys' flags, the unknown counts, the repeat counter, cnt, dup_max, dup_count
+  const size_t o_el = take(ops ? (size_t)sumE * 8 : 0), o_vlo = take(ops ? (size_t)sumR * 8 : 0), o_vhi = take(ops ? (size_t)sumR * 8 : 0);
+  const size_t o_slots = take(tab_slots * sizeof(SfEncSlot)), o_rflag = take(ops ? sumR : 0), o_kflag = take(ops ? (size_t)n * 4 : 0),
+               o_unk = take(ops ? (size_t)n * 8 : 0), o_rep = take(ops ? 4 : 0), o_cnt = take(ops ? (size_t)sumE * 4 : 0),
+               o_dmax = take(ops ? (size_t)sumE * 4 : 0), o_dcnt = take(ops ? (size_t)n * 4 : 0);
+  const size_t enc_zero_bytes = cursor - o_slots;
   std::vector<unsigned char> img;
   try { img.assign(head_bytes, 0); } catch (const std::bad_alloc&) { set_error("%s: host memory", fn); return TBC_ERR_OOM; }
   std::memcpy(img.data() + o_plan, plan.data(), sizeof(SfKeyPlan) * n);
   std::memcpy(img.data() + o_first, first.data(), first.size() * 4);
+  if (ops) std::memcpy(img.data() + o_enc, enc_keys.data(), sizeof(SfEncKey) * n);
   for (uint32_t k = 0; k < n; k++)        // the chunks' greatest prefixes start at 0, their least at ~0 (the minima lie behind the maxima)
     std::memset(img.data() + o_pm + ((size_t)plan[k].pmax_off + plan[k].chunks) * 4, 0xFF, (size_t)plan[k].chunks * 4);
   SF_TRY(hipSetDevice(S->device));
@@ -710,6 +746,50 @@ tbc_status sf_create(const char* fn, bool keyed, const tbc_setfull_keys_in* in, 
     const SfKeyPlan& p = plan[0];
     if (p.PITCH > p.WPR) SF_TRY(hipMemset2DAsync(S->d_M + p.WPR, (size_t)p.PITCH * 4, 0, (size_t)(p.PITCH - p.WPR) * 4, p.R, S->stream));
     SF_TRY(hipMemcpy2DAsync(S->d_M, (size_t)p.PITCH * 4, dense->present, (size_t)dense->words_per_row * 4, (size_t)p.WPR * 4, p.R, hipMemcpyHostToDevice, S->stream));
+  } else if (ops) {
+    SfEncArgs E;
+    E.plan = S->d_plan; E.first = S->d_first; E.enc = (const SfEncKey*)(A0 + o_enc); E.n_keys = n; E.R_all = sumR; E.E_all = sumE;
+    E.grid = std::min<uint32_t>(sumR, 16384u);
+    E.element = (const long long*)(A0 + o_el); E.slots = (SfEncSlot*)(A0 + o_slots);
+    E.val_lo = (const unsigned long long*)(A0 + o_vlo); E.val_hi = (const unsigned long long*)(A0 + o_vhi);
+    E.M = S->d_M; E.row_flag = (uint8_t*)(A0 + o_rflag); E.key_flag = (uint32_t*)(A0 + o_kflag); E.unknown = (unsigned long long*)(A0 + o_unk);
+    E.repeats = (uint32_t*)(A0 + o_rep); E.cnt = (uint32_t*)(A0 + o_cnt); E.dup_max = (uint32_t*)(A0 + o_dmax); E.dup_count = (uint32_t*)(A0 + o_dcnt);
+    const uint64_t nv = S->enc.n_values;
+    if (nv) SF_TRY(hipMalloc(&S->d_vals, nv * 8));
+    E.vals = (const long long*)S->d_vals;
+    SF_TRY(hipEventCreate(&S->ev_e0)); SF_TRY(hipEventCreate(&S->ev_e1));
+    SF_TRY(put(o_el, S->enc.element.data(), (size_t)sumE * 8));
+    SF_TRY(put(o_vlo, S->enc.val_lo.data(), (size_t)sumR * 8)); SF_TRY(put(o_vhi, S->enc.val_hi.data(), (size_t)sumR * 8));
+    if (nv) SF_TRY(hipMemcpyAsync(S->d_vals, ops_vals, nv * 8, hipMemcpyHostToDevice, S->stream));
+    SF_TRY(hipMemsetAsync(A0 + o_slots, 0, enc_zero_bytes, S->stream));
+    SF_TRY(hipEventRecord(S->ev_e0, S->stream));
+    if (sumE) hipLaunchKernelGGL(sf_table_build_kernel, dim3((sumE + 255u) / 256u), dim3(256), 0, S->stream, E);
+    if (sumR) hipLaunchKernelGGL(sf_values_kernel<TBC_SETFULL_ENCODE_WINDOW_WORDS>, dim3(E.grid), dim3(256), 0, S->stream, E);
+    SF_TRY(hipGetLastError());
+    SF_TRY(hipEventRecord(S->ev_e1, S->stream));
+    // the repeat counter back: only a history with a duplicated element pays for the exact pass
+    SF_TRY(hipMemcpyAsync(&S->h_repeats, E.repeats, 4, hipMemcpyDeviceToHost, S->stream));
+    SF_TRY(hipStreamSynchronize(S->stream));
+    float ms = 0, ms_d = 0;
+    SF_TRY(hipEventElapsedTime(&ms, S->ev_e0, S->ev_e1));
+    if (S->h_repeats) {
+      SF_TRY(hipEventCreate(&S->ev_d0)); SF_TRY(hipEventCreate(&S->ev_d1));
+      SF_TRY(hipEventRecord(S->ev_d0, S->stream));
+      hipLaunchKernelGGL(sf_dups_kernel, dim3(n), dim3(256), 0, S->stream, E);
+      SF_TRY(hipGetLastError());
+      SF_TRY(hipEventRecord(S->ev_d1, S->stream));
+    }
+    try { S->dup_max.assign(sumE, 0u); S->dup_count.assign(n, 0u); S->unknown.assign(n, 0ull); }
+    catch (const std::bad_alloc&) { set_error("%s: host memory", fn); return TBC_ERR_OOM; }
+    if (S->h_repeats) {
+      if (sumE) SF_TRY(hipMemcpyAsync(S->dup_max.data(), E.dup_max, (size_t)sumE * 4, hipMemcpyDeviceToHost, S->stream));
+      SF_TRY(hipMemcpyAsync(S->dup_count.data(), E.dup_count, (size_t)n * 4, hipMemcpyDeviceToHost, S->stream));
+    }
+    SF_TRY(hipMemcpyAsync(S->unknown.data(), E.unknown, (size_t)n * 8, hipMemcpyDeviceToHost, S->stream));
+    SF_TRY(hipStreamSynchronize(S->stream));
+    if (S->h_repeats) SF_TRY(hipEventElapsedTime(&ms_d, S->ev_d0, S->ev_d1));
+    S->ns_encode = (uint64_t)((ms + ms_d) * 1e6);
+    if (S->d_vals) { SF_TRY(hipFree(S->d_vals)); S->d_vals = nullptr; }
   } else if (!dense && sumR) {
     hipLaunchKernelGGL(setfull_rows_kernel, dim3(std::min<uint32_t>(sumR, 16384u)), dim3(256), 0, S->stream, S->d_plan, S->d_first, n, sumR,
                        (const uint32_t*)(A0 + o_top), (const unsigned long long*)(A0 + o_off), (const uint32_t*)(A0 + o_exc), S->d_M);
@@ -931,6 +1011,62 @@ tbc_status tbc_setfull_results(tbc_setfull* handle, const tbc_setfull_times* tim
 }
 tbc_status tbc_setfull_keys_results(tbc_setfull_keys* handle, const tbc_setfull_times* times, tbc_setfull_results_out* out) {
   return sf_results("tbc_setfull_keys_results", sf_obj(handle), times, out);
+}
+
+tbc_status tbc_setfull_keys_create_ops(const tbc_setfull_ops_in* in, tbc_setfull_keys** handle) {
+  const char* fn = "tbc_setfull_keys_create_ops";
+  if (!in || !handle) { set_error("%s: null argument", fn); return TBC_ERR_INVALID_ARG; }
+  if (in->n_keys == 0) { set_error("%s: n_keys is 0", fn); return TBC_ERR_INVALID_ARG; }
+  if (!in->op_off || !in->index || !in->type || !in->f || !in->process || !in->value || !in->val_off || !in->vals) {
+    set_error("%s: null argument (every pointer of tbc_setfull_ops_in must be set)", fn);
+    return TBC_ERR_INVALID_ARG;
+  }
+  SfObject* S = new (std::nothrow) SfObject();
+  if (!S) return TBC_ERR_OOM;
+  tbc_status st = TBC_OK;
+  try {
+    std::string err;
+    if (!sfenc::validate(fn, in, err)) { set_error("%s", err.c_str()); st = TBC_ERR_INVALID_ARG; }
+    if (st == TBC_OK) {
+      sfenc::plan(in, S->enc);
+      if (S->enc.element.size() >= 0xFFFFFFFFull || S->enc.read_ok.size() >= 0xFFFFFFFFull) {
+        set_error("%s: more than 2^32 - 2 elements or reads in one object", fn); st = TBC_ERR_INVALID_ARG;
+      }
+    }
+  } catch (const std::bad_alloc&) { set_error("%s: host memory", fn); st = TBC_ERR_OOM; }
+  if (st == TBC_OK) {
+    const sfenc::Plan& P = S->enc;
+    S->from_ops = true;
+    const tbc_setfull_keys_in made = {in->n_keys, in->device, P.n_elements.data(), P.n_reads.data(), P.add_invoke.data(), P.add_ok.data(),
+                                      P.read_invoke.data(), P.read_ok.data(), nullptr, nullptr, nullptr};
+    st = sf_create(fn, true, &made, (uint32_t)P.element.size(), (uint32_t)P.read_ok.size(), nullptr, S, in->vals);
+  }
+  if (st != TBC_OK) { delete S; return st; }
+  *handle = reinterpret_cast<tbc_setfull_keys*>(S);
+  return TBC_OK;
+}
+
+tbc_status tbc_setfull_keys_shape(tbc_setfull_keys* h, uint64_t* sum_elements, uint64_t* sum_reads) {
+  SfObject* const S = sf_obj(h);
+  if (!S || !sum_elements || !sum_reads) { set_error("tbc_setfull_keys_shape: null argument"); return TBC_ERR_INVALID_ARG; }
+  *sum_elements = S->sumE; *sum_reads = S->sumR;
+  return TBC_OK;
+}
+
+tbc_status tbc_setfull_keys_encoding(tbc_setfull_keys* h, tbc_setfull_encoding* out) {
+  SfObject* const S = sf_obj(h);
+  if (!S || !out) { set_error("tbc_setfull_keys_encoding: null argument"); return TBC_ERR_INVALID_ARG; }
+  if (!S->from_ops) {
+    set_error("tbc_setfull_keys_encoding: the object was not made from ops (tbc_setfull_keys_create_ops): its caller has the encoding");
+    return TBC_ERR_INVALID_ARG;
+  }
+  const sfenc::Plan& P = S->enc;
+  const auto give = [](auto* dst, const auto& src) { if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(src[0])); };
+  give(out->n_elements, P.n_elements); give(out->n_reads, P.n_reads); give(out->element, P.element);
+  give(out->add_invoke, P.add_invoke); give(out->add_ok, P.add_ok); give(out->read_invoke, P.read_invoke); give(out->read_ok, P.read_ok);
+  give(out->dup_max, S->dup_max); give(out->dup_count, S->dup_count); give(out->unknown_values, S->unknown);
+  out->ns_encode = S->ns_encode;
+  return TBC_OK;
 }
 
 void tbc_setfull_destroy(tbc_setfull* handle) { sf_destroy(sf_obj(handle)); }

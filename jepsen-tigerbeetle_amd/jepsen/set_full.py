@@ -369,6 +369,51 @@ class KeyedScan(_Handle):
         self._h = C.c_void_p()
         N.check_status(N.lib().tbc_setfull_keys_create(C.byref(s), C.byref(self._h)))
 
+    @classmethod
+    def from_ops(cls, columns, device=0):
+        """tbc_setfull_keys_create_ops: the keys of an `OpColumns` resident in one object, ENCODED BY THE LIBRARY (the host plans which
+        value is which column and which :ok read is which row; the device looks every read value up and builds the matrix).  The object
+        is an ordinary keyed one: `run()` and `results()` as ever, `encoding()` says what the library made of the ops."""
+        c = columns
+        self = cls.__new__(cls)
+        pad = lambda a: a if len(a) else np.zeros(1, a.dtype)                     # (a valid pointer for every array)
+        self._keep = k = {f: pad(getattr(c, f)) for f in ("op_off", "index", "type", "f", "process", "value", "val_off", "vals")}
+        s = N.SetFullOpsIn()
+        s.n_keys, s.device = len(c.keys), device
+        s.op_off, s.val_off = _p(k["op_off"], C.c_uint64), _p(k["val_off"], C.c_uint64)
+        s.index, s.type, s.f = _p(k["index"], C.c_uint32), _p(k["type"], C.c_uint8), _p(k["f"], C.c_uint8)
+        s.process, s.value, s.vals = _p(k["process"], C.c_int64), _p(k["value"], C.c_int64), _p(k["vals"], C.c_int64)
+        self._h = C.c_void_p()
+        N.check_status(N.lib().tbc_setfull_keys_create_ops(C.byref(s), C.byref(self._h)))
+        self.Es, self.Rs = np.zeros(len(c.keys), np.uint32), np.zeros(len(c.keys), np.uint32)
+        e = N.SetFullEncoding()
+        e.n_elements, e.n_reads = _p(self.Es, C.c_uint32), _p(self.Rs, C.c_uint32)
+        N.check_status(N.lib().tbc_setfull_keys_encoding(self._h, C.byref(e)))
+        return self
+
+    def shape(self):
+        """tbc_setfull_keys_shape: (sum of the keys' elements, sum of their reads)."""
+        se, sr = C.c_uint64(), C.c_uint64()
+        N.check_status(N.lib().tbc_setfull_keys_shape(self._h, C.byref(se), C.byref(sr)))
+        return se.value, sr.value
+
+    def encoding(self):
+        """tbc_setfull_keys_encoding (an object made by `from_ops` only): -> {"n_elements", "n_reads", "dup_count", "unknown_values" per
+        key; "element", "add_invoke", "add_ok", "dup_max" per element and "read_invoke", "read_ok" per read, key after key; "ns_encode"}."""
+        sumE, sumR = self.shape()
+        n = len(self.Es)
+        out = {"n_elements": np.zeros(n, np.uint32), "n_reads": np.zeros(n, np.uint32), "element": np.zeros(sumE, np.int64),
+               "add_invoke": np.zeros(sumE, np.uint32), "add_ok": np.zeros(sumE, np.uint32), "read_invoke": np.zeros(sumR, np.uint32),
+               "read_ok": np.zeros(sumR, np.uint32), "dup_max": np.zeros(sumE, np.uint32), "dup_count": np.zeros(n, np.uint32),
+               "unknown_values": np.zeros(n, np.uint64)}
+        e = N.SetFullEncoding()
+        for f, a in out.items():
+            if len(a):
+                setattr(e, f, _p(a, {np.dtype(np.uint32): C.c_uint32, np.dtype(np.int64): C.c_int64, np.dtype(np.uint64): C.c_uint64}[a.dtype]))
+        N.check_status(N.lib().tbc_setfull_keys_encoding(self._h, C.byref(e)))
+        out["ns_encode"] = int(e.ns_encode)
+        return out
+
     def run(self):
         """-> ([per key {"known", "last_present", "last_absent"}], {"ns_scan", "bytes_scanned", "bytes_matrix"} of the whole object)"""
         known, lp, la, tot = self._scan(self.Es.sum())
@@ -443,6 +488,197 @@ def check_keys(histories, linearizable=False, device=0):
     encs = {k: Encoded(h) for k, h in histories.items()}
     devs = results_keys(encs, linearizable, device)
     return {k: result_from_device(encs[k], devs[k]) for k in encs}
+
+
+# ---------------------------------------------------------------------------------------------------- the history as op columns
+_TYPE_CODE = {"invoke": N.SETFULL_T_INVOKE, "ok": N.SETFULL_T_OK, "fail": N.SETFULL_T_FAIL, "info": N.SETFULL_T_INFO}
+_F_CODE = {"add": N.SETFULL_OP_ADD, "read": N.SETFULL_OP_READ}
+_I64 = (-(2 ** 63), 2 ** 63)
+
+
+class OpColumns:
+    """The client ops of one history (`OpColumns(history)`) or of the keys of an independent one (`OpColumns.of_keys({k: history})`) as
+    the flat columns of tbc_setfull_ops_in: index, type, f, process, value per op, and the :ok reads' values end to end.  One plain pass
+    that copies; it knows none of set-full's rules (the library applies them: `KeyedScan.from_ops`).  An element or a read value that
+    is not an int in int64 range raises ValueError (such histories keep `Encoded`).  Per key it also keeps what `Encoded` keeps about
+    time: `op_time` (a slot per op of the key's history, None if no op carries :time), `unit`, `n_ops`."""
+
+    def __init__(self, history):
+        self._fill({0: history})
+
+    @classmethod
+    def of_keys(cls, histories):
+        self = cls.__new__(cls)
+        self._fill(histories)
+        return self
+
+    def _fill(self, histories):
+        self.keys = list(histories)
+        index, type_, f_, process, value, val_n, parts = [], [], [], [], [], [], []
+        op_off = [0]
+        self.op_time, self.unit, self.n_ops, self.n_add_invokes, self.n_ok_reads = [], [], [], [], []
+        for k, history in histories.items():
+            n_time = n_client = n_inv = n_ok = 0
+            last = -1
+            times = []
+            for i, op in enumerate(history):
+                if not H.client_op(op):
+                    continue
+                n_client += 1
+                last = i
+                if "time" in op:
+                    n_time += 1
+                    times.append((i, op["time"]))
+                t, f = _TYPE_CODE.get(op.get("type")), _F_CODE.get(op.get("f"), N.SETFULL_OP_OTHER)
+                if t is None:
+                    t, f = N.SETFULL_T_INFO, N.SETFULL_OP_OTHER
+                v, nv = 0, 0
+                if f == N.SETFULL_OP_ADD:
+                    v = op.get("value")
+                    if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or not _I64[0] <= v < _I64[1]:
+                        raise ValueError(f"key {k!r} op {i}: the element {v!r} is not an int in int64 range (use Encoded)")
+                    v = int(v)
+                    n_inv += t == N.SETFULL_T_INVOKE
+                elif f == N.SETFULL_OP_READ and t == N.SETFULL_T_OK:
+                    rv = op.get("value")
+                    if rv is None:
+                        t |= N.SETFULL_T_NIL
+                    else:
+                        n_ok += 1
+                        try:
+                            arr = np.asarray(rv if isinstance(rv, (list, tuple, np.ndarray)) else list(rv))
+                        except OverflowError:
+                            arr = np.zeros(1, object)
+                        if arr.size and (arr.ndim != 1 or arr.dtype.kind not in "iu" or (arr.dtype.kind == "u" and arr.size and int(arr.max()) >= _I64[1])):
+                            raise ValueError(f"key {k!r} op {i}: a read value is not an int in int64 range (use Encoded)")
+                        nv = int(arr.size)
+                        if nv:
+                            parts.append(arr.astype(np.int64, copy=False))
+                index.append(i); type_.append(t); f_.append(f); process.append(op["process"]); value.append(v); val_n.append(nv)
+            op_off.append(len(index))
+            n_ops = last + 1
+            self.n_ops.append(n_ops)
+            self.unit.append(1_000_000 if n_client and n_time == n_client else 1)
+            self.n_add_invokes.append(int(n_inv)); self.n_ok_reads.append(n_ok)
+            col = None
+            if n_time:                                   # as Encoded: an op without :time counts as its index
+                col = np.zeros(n_ops, np.int64)
+                if n_time != n_client:
+                    col[index[op_off[-2]:]] = index[op_off[-2]:]
+                col[[i for i, _ in times]] = [t for _, t in times]
+            self.op_time.append(col)
+        try:
+            self.process = np.array(process, np.int64).reshape(-1)
+        except OverflowError:
+            raise ValueError("a process number is not in int64 range") from None
+        self.op_off = np.array(op_off, np.uint64)
+        self.index, self.type, self.f = np.array(index, np.uint32), np.array(type_, np.uint8), np.array(f_, np.uint8)
+        self.value = np.array(value, np.int64).reshape(-1)
+        self.val_off = np.concatenate([[0], np.cumsum(np.array(val_n, np.int64))]).astype(np.uint64)
+        self.vals = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.int64)
+
+    def take(self, positions):
+        """The columns of the keys at `positions` (in that order) as an OpColumns of their own."""
+        positions = list(positions)
+        if positions == list(range(len(self.keys))):
+            return self
+        c = OpColumns.__new__(OpColumns)
+        c.keys = [self.keys[p] for p in positions]
+        for f in ("op_time", "unit", "n_ops", "n_add_invokes", "n_ok_reads"):
+            setattr(c, f, [getattr(self, f)[p] for p in positions])
+        lo, hi = self.op_off[positions].astype(np.int64), self.op_off[[p + 1 for p in positions]].astype(np.int64)
+        rows = np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)] + [np.zeros(0, np.int64)]).astype(np.int64)
+        for f in ("index", "type", "f", "process", "value"):
+            setattr(c, f, np.ascontiguousarray(getattr(self, f)[rows]))
+        c.op_off = np.concatenate([[0], np.cumsum(hi - lo)]).astype(np.uint64)
+        vo = self.val_off.astype(np.int64)
+        c.val_off = np.concatenate([[0], np.cumsum(vo[rows + 1] - vo[rows])]).astype(np.uint64)
+        c.vals = np.ascontiguousarray(np.concatenate([self.vals[vo[a]:vo[b]] for a, b in zip(lo, hi)] + [np.zeros(0, np.int64)]))
+        return c
+
+
+class _Named:
+    """What `result_from_device` asks of an encoding: the elements' names and the duplicates."""
+
+    def __init__(self, elements, duplicated):
+        self.elements, self.duplicated = elements, duplicated
+
+
+class _Bound:
+    """The matrix a key of the columns can make at most: (:ok reads) x (add invocations)."""
+
+    def __init__(self, n_add_invokes, n_ok_reads):
+        self.E, self.R, self.wpr = n_add_invokes, n_ok_reads, max(1, (n_add_invokes + 31) // 32)
+
+
+def unknown_duplicates(cols, k, elements, read_ok):
+    """jepsen's `frequencies` over the whole read for the values the library does not see: {value: its greatest multiplicity within
+    one read} over the values of key k's reads (`read_ok`: their :ok ops) that name none of `elements`.  One vectorised pass."""
+    o0, o1 = int(cols.op_off[k]), int(cols.op_off[k + 1])
+    rows = o0 + np.searchsorted(cols.index[o0:o1], read_ok)
+    vo = cols.val_off.astype(np.int64)
+    starts, lens = vo[rows], vo[rows + 1] - vo[rows]
+    total = int(lens.sum())
+    if total < 2:
+        return {}
+    at = np.repeat(starts - (np.cumsum(lens) - lens), lens) + np.arange(total)
+    v, rid = cols.vals[at], np.repeat(np.arange(len(rows)), lens)
+    m = ~np.isin(v, elements)
+    v, rid = v[m], rid[m]
+    if len(v) < 2:
+        return {}
+    order = np.lexsort((v, rid))
+    v, rid = v[order], rid[order]
+    first = np.concatenate([[True], (v[1:] != v[:-1]) | (rid[1:] != rid[:-1])])
+    counts = np.diff(np.concatenate([np.nonzero(first)[0], [len(v)]]))
+    vv = v[first]
+    u, inv = np.unique(vv[counts > 1], return_inverse=True)
+    mx = np.zeros(len(u), np.int64)
+    np.maximum.at(mx, inv, counts[counts > 1])
+    return dict(zip(u.tolist(), mx.tolist()))
+
+
+def duplicated_of_key(cols, k, element, dup_max, unknown_values, read_ok):
+    """jepsen's `duplicated` of key k of `cols` from the library's encoding of it (tbc_setfull_encoding, the key's slices): the elements
+    with dup_max > 1, and -- only if the key has unknown values at all -- the duplicates among those."""
+    dups = dict(zip(element[dup_max > 1].tolist(), dup_max[dup_max > 1].tolist()))
+    if unknown_values:
+        dups.update(unknown_duplicates(cols, k, element, read_ok))
+    return dups
+
+
+def check_keys_columns(histories, linearizable=False, device=0):
+    """{k: history} -> {k: set-full result}, exactly what `check_keys` returns, with the ENCODING done by the library: the histories are
+    copied into op columns (`OpColumns`), each budget group of keys becomes one object (`KeyedScan.from_ops`), and the result maps name
+    their elements from the library's encoding.  `duplicated` comes from the library's dup_max; duplicates among values that name no
+    element (which the library only counts) are added here, for the keys that have such values."""
+    if not histories:
+        return {}
+    cols = OpColumns.of_keys(histories)
+    out = {}
+    for unit in sorted(set(cols.unit)):
+        part = [(p, _Bound(cols.n_add_invokes[p], cols.n_ok_reads[p])) for p in range(len(cols.keys)) if cols.unit[p] == unit]
+        for grp in groups_within_budget(part):
+            pos = [p for p, _ in grp]
+            sub = cols.take(pos)
+            times = None if all(t is None for t in sub.op_time) else [t if t is not None else np.arange(n, dtype=np.int64)
+                                                                        for t, n in zip(sub.op_time, sub.n_ops)]
+            with KeyedScan.from_ops(sub, device) as ks:
+                enc = ks.encoding()
+                per, _ = ks.results(times, unit, linearizable)
+            ce = np.concatenate([[0], np.cumsum(enc["n_elements"], dtype=np.int64)])
+            cr = np.concatenate([[0], np.cumsum(enc["n_reads"], dtype=np.int64)])
+            for j, p in enumerate(pos):
+                el = enc["element"][ce[j]:ce[j + 1]]
+                dm = enc["dup_max"][ce[j]:ce[j + 1]]
+                dups = duplicated_of_key(sub, j, el, dm, enc["unknown_values"][j], enc["read_ok"][cr[j]:cr[j + 1]])
+                out[cols.keys[p]] = result_from_device(_Named(el.tolist(), dups), per[j])
+    return {k: out[k] for k in cols.keys}
+
+
+def check_columns(history, linearizable=False, device=0):
+    """`check` with the encoding done by the library (`check_keys_columns` of one key)."""
+    return check_keys_columns({0: history}, linearizable, device)[0]
 
 
 # ---------------------------------------------------------------------------------------------------- read-all-invoked-adds
