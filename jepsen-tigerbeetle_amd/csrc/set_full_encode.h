@@ -1,6 +1,7 @@
 // set_full_encode.h -- the O(values) part of tbc_setfull_keys_create_ops on the MI355X (gfx950): from the raw values of every read to
-// the reads x elements membership matrix the scan loads, and the duplicates.  Included by set_full.hip; the host part (which value is
-// which column, which read is which row, where a row's values lie) is set_full_encode_plan.h.
+// the reads x elements membership matrix the scan loads, and the duplicates.  Included by set_full_host.hip; the host part (which value is
+// which column, which read is which row, where a row's values lie) is set_full_encode_plan.h, the tables' slots and each key's share of
+// them (SfEncSlot, SfEncKey) set_full_plan.h.
 //
 //   sf_table_build_kernel  a thread per element of every key: the element's value goes into its key's open-addressing table (16 B
 //                          slots {value, column + 1}; capacity the power of two at or above 2 E, linear probing).  A thread claims the
@@ -27,9 +28,6 @@
 #include "set_full_plan.h"
 
 namespace {
-
-struct alignas(16) SfEncSlot { long long value; uint32_t col1, pad; };       // col1 = column + 1, 0 = free
-struct SfEncKey { unsigned long long tab_off; uint32_t mask, pad; };         // the key's table: slots tab_off .. tab_off + mask (E = 0: none)
 
 struct SfEncArgs {
   const SfKeyPlan* plan; const uint32_t* first; const SfEncKey* enc; uint32_t n_keys, R_all, E_all, grid;

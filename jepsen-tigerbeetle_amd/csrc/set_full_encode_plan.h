@@ -1,5 +1,5 @@
 // set_full_encode_plan.h -- jepsen.checker/set-full's encoding of a history given as op columns (tbc_setfull_keys_create_ops): the
-// O(ops) part, on the host.  Plain C++ (no HIP): set_full.hip includes it, and so does the emulator program of the encoding kernels
+// O(ops) part, on the host.  Plain C++ (no HIP): set_full_host.hip includes it, and so does the emulator program of the encoding kernels
 // (tests/emu/emu_setfull_encode.cpp), so the rules below have one statement in C.
 //
 // From a key's columns (tbc_setfull_ops_in: index, type, f, process, value per client op, in history order) the plan makes what

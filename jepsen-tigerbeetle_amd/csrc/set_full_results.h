@@ -1,5 +1,6 @@
 // set_full_results.h -- jepsen.checker/set-full's verdict from the scan's three indices, on the MI355X (gfx950).  Included by
-// set_full.hip; tbc_setfull_results / tbc_setfull_keys_results run these kernels behind the scan.
+// set_full_host.hip; tbc_setfull_results / tbc_setfull_keys_results run these kernels behind the scan.  (kSelTile, the elements a
+// workgroup takes, is the plan's: set_full_plan.h.)
 //
 // The scan leaves known / last_present / last_absent per element on the device.  What follows is a fixed sequence of launches over
 // the elements of ALL keys (the key of a workgroup found through the plan table, as in the scan), whatever n_keys is:
@@ -31,7 +32,6 @@
 
 namespace {
 
-constexpr uint32_t kSelTile = 2048;          // elements per workgroup of 256: a wavefront takes 512 consecutive ones, 64 a step
 constexpr uint32_t kSelTargets = 7;          // 0-2: stable .5 .95 .99; 3: the 8th greatest stable latency; 4-6: lost .5 .95 .99
 constexpr uint32_t kSelBins = 256;
 constexpr uint32_t kWorst = TBC_SETFULL_WORST;

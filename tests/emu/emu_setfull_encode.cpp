@@ -1,5 +1,6 @@
 // TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  emu_setfull_encode.cpp: tbc_setfull_keys_create_ops's encoding on the CPU -- the host plan of
-// csrc/set_full_encode_plan.h and the kernels of csrc/set_full_encode.h (the very files hipcc compiles into libtbcheck.so) under the
+// csrc/set_full_encode_plan.h, the layout of csrc/set_full_plan.h (sf_make_layout, as set_full_host.hip calls it for an object made from
+// ops) and the kernels of csrc/set_full_encode.h (the very files hipcc compiles into libtbcheck.so) under the
 // wavefront / workgroup emulator, in the library's order: plan, table build, values kernel, and the dups kernel if the repeat counter is
 // not zero.  The window of the values kernel is EMU_W words here (the library's is TBC_SETFULL_ENCODE_WINDOW_WORDS), so that rows of a
 // few hundred elements span several windows.  Built as a shared object by tests/test_set_full_encode_emu.py, which compares what it
@@ -58,25 +59,13 @@ extern "C" int emu_sfe_encode(const tbc_setfull_ops_in* in, uint32_t grid, uint6
   sfenc::plan(in, g.P);
   const sfenc::Plan& P = g.P;
   const uint32_t n = in->n_keys, sumE = (uint32_t)P.element.size(), sumR = (uint32_t)P.read_ok.size();
-  // the plan table as sf_create lays it out, as far as these kernels read it
-  g.plan.assign(n, SfKeyPlan{});
-  std::vector<uint32_t> first((size_t)kFirsts * (n + 1), 0u);
-  std::vector<SfEncKey> enc(n, SfEncKey{});
-  uint64_t m_words = 0, slots = 0;
-  uint32_t eb = 0, rb = 0;
-  for (uint32_t k = 0; k < n; k++) {
-    SfKeyPlan& p = g.plan[k];
-    p.E = P.n_elements[k]; p.R = P.n_reads[k]; p.elem_base = eb; p.row_base = rb;
-    p.WPR = (p.E + 31u) / 32u; p.PITCH = (p.WPR + 3u) / 4u * 4u;
-    m_words = (m_words + 63) / 64 * 64; p.m_off = m_words; m_words += (uint64_t)p.R * p.PITCH;
-    first[kFirstRows * (n + 1) + k] = rb;
-    const uint64_t cap = sfenc::table_slots(p.E);
-    enc[k].tab_off = slots; enc[k].mask = cap ? (uint32_t)(cap - 1u) : 0u; slots += cap;
-    eb += p.E; rb += p.R;
-  }
-  first[kFirstRows * (n + 1) + n] = rb;
-  g.M.assign(m_words + 4, 0xA5A5A5A5u);                       // (what the kernel does not write shows)
-  std::vector<SfEncSlot> tab(slots + 1, SfEncSlot{0, 0u, 0u});
+  // the library's own plan (csrc/set_full_plan.h): the plan table, the first rows, the keys' tables
+  const SfLayout L = sf_make_layout(n, P.n_elements.data(), P.n_reads.data(), SfSource::Ops, 0u, 0u);
+  g.plan = L.plan;
+  const std::vector<uint32_t>& first = L.first;
+  const std::vector<SfEncKey>& enc = L.enc_keys;
+  g.M.assign(L.m_words + 4, 0xA5A5A5A5u);                     // (what the kernel does not write shows)
+  std::vector<SfEncSlot> tab(L.tab_slots + 1, SfEncSlot{0, 0u, 0u});
   std::vector<uint8_t> row_flag(sumR + 1, 0);
   std::vector<uint32_t> key_flag(n, 0u), cnt(sumE + 1, 0u);
   g.dup_max.assign(sumE + 1, 0u); g.dup_count.assign(n, 0u); g.unknown.assign(n, 0ull);

@@ -44,15 +44,12 @@ void launch(Call c, uint32_t grid, int waves, uint64_t seed) {
 extern "C" int emu_setfull_results(uint32_t n_keys, const uint32_t* E, const uint32_t* known, const uint32_t* lp, const uint32_t* la,
                                    const int64_t* op_time, const uint64_t* time_off, uint64_t unit, uint32_t flags, uint8_t* outcome,
                                    int64_t* slat, int64_t* llat, tbc_setfull_key_summary* summary, uint64_t seed) {
-  std::vector<SfKeyPlan> plan(n_keys);
-  std::vector<uint32_t> first((size_t)kFirsts * (n_keys + 1), 0u);
-  uint32_t eb = 0, tiles = 0;
-  for (uint32_t k = 0; k < n_keys; k++) {
-    plan[k] = SfKeyPlan{};
-    plan[k].E = E[k]; plan[k].elem_base = eb; eb += E[k];
-    first[kFirstSelect * (n_keys + 1) + k] = tiles; tiles += (E[k] + kSelTile - 1u) / kSelTile;
-  }
-  first[kFirstSelect * (n_keys + 1) + n_keys] = tiles;
+  // the library's own plan (csrc/set_full_plan.h) of these keys -- without reads: the results' passes look at the elements only
+  const std::vector<uint32_t> no_reads(n_keys, 0u);
+  const SfLayout L = sf_make_layout(n_keys, E, no_reads.data(), SfSource::Rows, 0u, 0u);
+  const std::vector<SfKeyPlan>& plan = L.plan;
+  const std::vector<uint32_t>& first = L.first;
+  const uint32_t tiles = (uint32_t)L.tiles[kFirstSelect];
   std::vector<SfKeyAcc> acc(n_keys);
   std::vector<SfSel> sel((size_t)n_keys * kSelTargets, SfSel{0ull, 0u, 0u});
   std::vector<uint32_t> hist((size_t)n_keys * kSelTargets * kSelBins, 0u);

@@ -38,7 +38,8 @@ TALL_SHAPE = (96, 256 * 130)
 
 
 def _chunks(E, R):
-    """(chunks, rows per chunk) of a key: sf_chunks and the two lines of sf_create that call it (csrc/set_full.hip), restated."""
+    """(chunks, rows per chunk) of a key: what the planner gives it (csrc/set_full_plan.h: sf_chunks and the two lines of sf_make_layout
+    that call it), restated so that the generator can aim at chunk boundaries; tests/test_set_full_plan.py holds the planner to it."""
     if not (E and R):
         return 1, max(1, R)
     col_blocks = max(1, ((E + 31) // 32 + 255) // 256)
