@@ -34,6 +34,22 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 // group flags
 enum : uint32_t { F_ACTIVE = 1u, F_NEED_POP = 2u, F_LOOK = 4u, F_NEED_GROW = 8u, F_CAND = 16u };
 
+// wv::stat ids of the dependent memory trips a wave iteration makes beyond its two (nothing on the device; tests/test_narrow_trips_emu.py
+// reads them from the emulator).  Per wave iteration unless a lane-event is named.
+enum : uint32_t {
+  S_ITER = 29,          // wave iterations
+  S_NN16 = 30,          // ... with more than 16 / 24 / 32 viable children in the wavefront
+  S_NN24 = 31,
+  S_NN32 = 32,
+  S_LOOK_LATE = 33,     // lookahead batches loaded after the first lookahead wait (each one a trip of its own)
+  S_CLAIM_PASS = 34,    // passes of the claim loop, the first included
+  S_CLAIM_AGAIN = 35,   // ... of them second and later ones (wait for the stores, read the bucket again)
+  S_LOSE_TRUE = 36,     // lane-events: lost the entry to a lower lane of the group that wanted the same one
+  S_LOSE_FALSE = 37,    // lane-events: lost an entry although no lower lane of the group wanted one of the same bucket
+  S_NEXT_BUCKET = 38,   // lane-events: the bucket was full, on to the next one
+  S_WINDOW = 39         // lane-events: the front advanced past the window in hand (one more load, decided before the next)
+};
+
 // LDS words of a group: counters and results, then the ring of the most recent pushes
 enum : uint32_t {
   G_DSTACK = 0, G_PROBES = 2, G_EXPANDED = 4, G_ROUNDS = 6, G_VERDICT = 8, G_CAUSE = 9, G_MAXF = 10, G_MAXSP = 11,
@@ -43,7 +59,7 @@ enum : uint32_t {
   G_T0 = 52,        // 2 words: when the history was taken up (time limit)
   G_NEXT = 54,      // the work item a finished group takes next
   G_PF = 16,        // 4 words: front, list offset, live and all open calls of the child whose candidates are fetched ahead
-  G_CLAIM = 20,     // 32 words: who takes the empty entry of a bucket (by bucket number mod 32) this round
+  G_CLAIM = 20,     // 32 words, the first L in use: the empty entry each lane of the group wants in this pass of the claim loop (kNone: none)
   G_RING = 56
 };
 WV_HD constexpr uint32_t ring_size(uint32_t L) { return L <= 8u ? 8u : L; }      // (>= L: a round's pushes never clash.  Round 5: 8 entries for 8 lanes, not 16: 5.9 KB of LDS a wavefront instead of 8.7 -- the same rate on the device, alone and beside another batch's pack: profiles/r05_ring8_ab.txt)
@@ -446,8 +462,7 @@ WV_DEV void narrow_wave(const BeamArgs& A, const uint32_t wave_idx, uint32_t* ld
     }
   };
 
-  uint32_t iter = 0, arb = 0;
-  for (uint32_t i = li; i < 32u; i += L) GS[G_CLAIM + i] = 0u;
+  uint32_t iter = 0;
 
   for (;;) {
     wv::barrier();                                 // ring writes of the last round, LDS results
@@ -462,6 +477,7 @@ WV_DEV void narrow_wave(const BeamArgs& A, const uint32_t wave_idx, uint32_t* ld
     }
     if (!wv::ballot((flags & F_ACTIVE) != 0u)) break;
     iter++;
+    if (lane == 0) wv::stat(S_ITER, 1);
 
     // ---- cold: visited sets that must grow first (the parent that did not fit is still on the stack)
     const uint64_t gb = wv::ballot((flags & F_NEED_GROW) != 0u);
@@ -607,7 +623,7 @@ WV_DEV void narrow_wave(const BeamArgs& A, const uint32_t wave_idx, uint32_t* ld
     // of the next ranks came with the candidate: no memory access here.  The reads the rule takes that are still open at
     // the child's front are one row entry (the trip below).
     int32_t st2 = st;
-    uint32_t fi2 = fi;
+    uint32_t fi2 = fi, n_window = 0;
     uint64_t M2[MW];
     WV_UNROLL
     for (int j = 0; j < MW; j++) M2[j] = Mp[j];
@@ -627,12 +643,16 @@ WV_DEV void narrow_wave(const BeamArgs& A, const uint32_t wave_idx, uint32_t* ld
         }
       }
       const uint32_t vis = eager ? rdm_index(st2, vpad) : 0xFFFFu;
+      uint32_t wb = wbase;                  // compact records: the window in hand and the rank it starts at
+      uint64_t ww = w0;
       for (;;) {
         uint32_t pp, rk;
         if constexpr (CF) {
-          const uint32_t d = fi2 - wbase;
-          if (d < kFrontCompactRanks) { const uint32_t e = (uint32_t)(w0 >> (9u * d)) & 0x1FFu; pp = e & 63u; rk = e >> 6; }
-          else { pp = (uint32_t)A.slot8[slot8_lo + fi2]; rk = (uint32_t)A.rk8[slot8_lo + fi2]; }
+          // past the window the parent came with: the window of the rank reached (word 7 of its front record, the form of w0)
+          // covers that rank and the six behind it -- one aligned load for seven ranks
+          if (fi2 - wb >= kFrontCompactRanks) { ww = A.rdm[((uint64_t)op_off + fi2) * FW + 7u]; wb = fi2; n_window++; }
+          const uint32_t e = (uint32_t)(ww >> (9u * (fi2 - wb))) & 0x1FFu;
+          pp = e & 63u; rk = e >> 6;
         } else {
           pp = byte_at(w0, w1, A.slot8, fi2);
           rk = eager ? byte_at(k0w, k1w, A.rk8, fi2) : 0xFFu;
@@ -648,6 +668,7 @@ WV_DEV void narrow_wave(const BeamArgs& A, const uint32_t wave_idx, uint32_t* ld
       }
     }
     if (inround && li == 0) wv::lds_add64(GS + G_ROUNDS, 1ull);
+    wv::stat(S_WINDOW, n_window);
     // linearizable: the group's lowest pair wins, nothing of this round is inserted
     const uint32_t gsucc = grp(wv::ballot(viable && fi2 >= RT));        // (RT = R unless the count form checks a prefix)
     if (gsucc) {
@@ -669,25 +690,45 @@ WV_DEV void narrow_wave(const BeamArgs& A, const uint32_t wave_idx, uint32_t* ld
     const bool lkme = go && (flags & F_LOOK);
     const uint64_t lk = wv::ballot(lkme);
     const uint32_t ci = (uint32_t)__builtin_popcountll(lk & ((1ull << lane) - 1ull)), nn0 = (uint32_t)__builtin_popcountll(lk);
+    if (lane == 0) { if (nn0 > 16u) wv::stat(S_NN16, 1); if (nn0 > 24u) wv::stat(S_NN24, 1); if (nn0 > 32u) wv::stat(S_NN32, 1); }
     if (lkme) { c_fi[ci] = fi2; c_lo[ci] = look_lo; if constexpr (CNT) c_rt[ci] = RT; }
     wv::barrier();
     const uint32_t f3 = go ? fi2 : 0u;
     const uint64_t* const fr = A.rdm + ((uint64_t)op_off + f3) * FW;
     uint32_t co0, cnl, ccnt;
     uint64_t cw[WN];
-    uint64_t lw0[2], lpm[2][MW];
+    // batches of 8 children whose records are asked for in trip 1: with one mask word the registers hold four (32 children); wider
+    // masks keep two, as their kernels spill already (two more cost <2,*> 21 to 37 more spilled registers, reloaded in the round)
+    constexpr int NB = MW == 1 ? 4 : 2;
+    uint64_t lw0[NB], lpm[NB][MW];
+    // the lookahead record of (child cb + lane / 8, rank lane % 8)
+    const auto look_load = [&](uint32_t cb, uint64_t& w_0, uint64_t (&pm)[MW]) {
+      const uint32_t cc = cb + (lane >> 3), jr = lane & 7u;
+      const bool val = cc < nn0;
+      const uint32_t lo_ = val ? c_lo[cc] : (look_avail ? look_lo : 0u), fr_ = val ? c_fi[cc] + jr : 0u;
+      const uint64_t* rec = lk_base + (uint64_t)lo_ + (uint64_t)fr_ * (MW + 1);
+      w_0 = rec[0];
+      WV_UNROLL
+      for (int w = 0; w < MW; w++) pm[w] = rec[1 + w];
+    };
     {
       const uint32_t vi = (eager && go) ? rdm_index(st2, vpad) : 0u;
       uint64_t r0[MW], rv[MW];
-      WV_UNROLL
-      for (int bt = 0; bt < 2; bt++) {
-        const uint32_t cc = 8u * bt + (lane >> 3), jr = lane & 7u;
-        const bool val = cc < nn0;
-        const uint32_t lo_ = val ? c_lo[cc] : (look_avail ? look_lo : 0u), fr_ = val ? c_fi[cc] + jr : 0u;
-        const uint64_t* rec = lk_base + (uint64_t)lo_ + (uint64_t)fr_ * (MW + 1);
-        lw0[bt] = rec[0];
+      look_load(0u, lw0[0], lpm[0]);
+      look_load(8u, lw0[1], lpm[1]);
+      // children 16 .. 31 are no exception (a wavefront of eight busy groups has 18 viable children on average): their
+      // records are asked for in this same trip, behind branches on the wave-uniform count, before anything is waited for
+      if constexpr (NB == 4) {
         WV_UNROLL
-        for (int w = 0; w < MW; w++) lpm[bt][w] = rec[1 + w];
+        for (int bt = 2; bt < 4; bt++) {
+          lw0[bt] = 0ull;
+          WV_UNROLL
+          for (int w = 0; w < MW; w++) lpm[bt][w] = 0ull;
+        }
+        if (nn0 > 16u) {
+          look_load(16u, lw0[2], lpm[2]);
+          if (nn0 > 24u) look_load(24u, lw0[3], lpm[3]);
+        }
       }
       uint64_t m0, m1 = 0;
       if constexpr (CF) { m0 = fr[6]; cw[0] = fr[7]; }
@@ -755,15 +796,18 @@ WV_DEV void narrow_wave(const BeamArgs& A, const uint32_t wave_idx, uint32_t* ld
         const uint64_t bad1 = look_batch(8u, lw0[1], lpm[1]);
         if (lkme && ci >= 8u && ci < 16u) dead = ((bad1 >> (8u * (ci - 8u))) & 0xFFull) != 0ull;
       }
-      for (uint32_t cb = 16u; cb < nn0; cb += 8u) {          // more than 16 viable children in the wavefront: rare
-        const uint32_t cc = cb + (lane >> 3), jr = lane & 7u;
-        const bool val = cc < nn0;
-        const uint32_t lo_ = val ? c_lo[cc] : (look_avail ? look_lo : 0u), fr_ = val ? c_fi[cc] + jr : 0u;
-        const uint64_t* rec = lk_base + (uint64_t)lo_ + (uint64_t)fr_ * (MW + 1);
-        uint64_t xpm[MW];
-        const uint64_t xw0 = rec[0];
-        WV_UNROLL
-        for (int w = 0; w < MW; w++) xpm[w] = rec[1 + w];
+      if constexpr (NB == 4) if (nn0 > 16u) {
+        const uint64_t bad2 = look_batch(16u, lw0[2], lpm[2]);
+        if (lkme && ci >= 16u && ci < 24u) dead = ((bad2 >> (8u * (ci - 16u))) & 0xFFull) != 0ull;
+        if (nn0 > 24u) {
+          const uint64_t bad3 = look_batch(24u, lw0[3], lpm[3]);
+          if (lkme && ci >= 24u && ci < 32u) dead = ((bad3 >> (8u * (ci - 24u))) & 0xFFull) != 0ull;
+        }
+      }
+      for (uint32_t cb = 8u * NB; cb < nn0; cb += 8u) {      // more children than trip 1 asked for: a trip per batch of 8
+        if (lane == 0) wv::stat(S_LOOK_LATE, 1);
+        uint64_t xw0, xpm[MW];
+        look_load(cb, xw0, xpm);
         const uint64_t badx = look_batch(cb, xw0, xpm);
         if (lkme && ci >= cb && ci < cb + 8u) dead = ((badx >> (8u * (ci - cb))) & 0xFFull) != 0ull;
       }
@@ -814,8 +858,9 @@ WV_DEV void narrow_wave(const BeamArgs& A, const uint32_t wave_idx, uint32_t* ld
     // ---- trip 2, consume.  Visited set: find the key in its bucket chain, else take the first empty entry met.  Lanes of
     // different groups never meet (one table per history); two lanes of a group can want the same empty entry (two keys of
     // one bucket, or -- at the root only -- one key twice): they settle it in LDS, the loser looks again.
-    for (;;) {
+    for (uint32_t pass = 0;; pass++) {
       bool want = false;
+      if (lane == 0) { wv::stat(S_CLAIM_PASS, 1); if (pass) wv::stat(S_CLAIM_AGAIN, 1); }
       if (pending) {
         uint32_t match = 0, empty = 0;
         if constexpr (MW == 1 && !CNT) {
@@ -850,32 +895,34 @@ WV_DEV void narrow_wave(const BeamArgs& A, const uint32_t wave_idx, uint32_t* ld
         else if (empty) { idx = b * 4u + (uint32_t)__builtin_ctz(empty); want = true; }
         else {
           b = (b + 1u) & bmask;
+          wv::stat(S_NEXT_BUCKET, 1);
           if (++full_buckets > bmask) pending = false;       // every bucket full: cannot happen below the 3/4 fill bound
         }
       }
       if (wv::ballot(want)) {
-        // the LOWEST lane that wants an entry of this bucket gets it (so two pairs of a round that produce one and the same
-        // config -- the root's nil reads under the eager rule -- resolve as the oracle's pair order does): an LDS max over
-        // {arbitration number, 255 - lane}; words of earlier arbitrations hold smaller numbers
-        arb++;
-        if ((arb & 0xFFFFFFu) == 0u) {                         // the number wraps: clear the claim words (every ~10^7 rounds)
-          arb++;
-          wv::barrier();
-          for (uint32_t i = li; i < 32u; i += L) GS[G_CLAIM + i] = 0u;
-          wv::barrier();
-        }
-        uint32_t* const claim = GS + G_CLAIM + (b & 31u);
-        const uint32_t ticket = (arb << 8) | (255u - li);
-        if (want) wv::lds_max32(claim, ticket);
+        // a lane loses an entry only to a LOWER lane of its group that wants the very same one (so two pairs of a round that
+        // produce one and the same config -- the root's nil reads under the eager rule -- resolve as the oracle's pair order
+        // does): every lane posts the entry it wants in the group's slice of LDS and reads what the lanes below it posted.
+        // Two buckets of one group never get in each other's way, and nothing is kept from pass to pass.
+        static_assert(L <= 32, "a claim word per lane of the group");
+        wv::barrier();                                         // (the words' readers of an earlier pass are done)
+        GS[G_CLAIM + li] = want ? idx : kNone;
         wv::barrier();
-        if (want && *claim == ticket) {
+        bool mine = want, neighbour = false;                   // (neighbour: a lower lane wants an entry of my bucket -- for the counters only)
+        WV_UNROLL
+        for (uint32_t j = 0; j + 1u < (uint32_t)L; j++) {
+          const uint32_t theirs = GS[G_CLAIM + j];
+          mine = mine && !(j < li && theirs == idx);
+          neighbour = neighbour || (j < li && (theirs >> 2) == b);
+        }
+        if (mine) {
           gu64* e = tab + (uint64_t)idx * KW;
           wv::own_st64(e, k0c);
           WV_UNROLL
           for (int j = 0; j < MW; j++) wv::own_st64(e + 1 + j, M2[j]);
           if constexpr (CNT) { wv::own_st64(e + 1 + MW, C2[0]); wv::own_st64(e + 2 + MW, C2[1]); }
           fresh = true; pending = false;
-        }
+        } else if (want) wv::stat(neighbour ? S_LOSE_TRUE : S_LOSE_FALSE, 1);
       }
       if (!wv::ballot(pending)) break;
       wv::wait_stores();                                      // a loser must see the winner's entry
