@@ -818,6 +818,86 @@ typedef struct tbc_setfull_encoding {          /* every pointer optional (NULL =
 } tbc_setfull_encoding;
 tbc_status tbc_setfull_keys_encoding(tbc_setfull_keys* h, tbc_setfull_encoding* out);
 
+/* ----------------------------------------------------------------- ledger */
+/* The ledger workload's checkers (the reference's tests/ledger.clj:154-282, composed at :363-367) from the history as op columns, in ONE
+ * call: the bank checker (:SI), lookup-all-invoked-transfers and final-reads.  (unexpected-ops returns ops and is O(ops): the caller's.)
+ * The caller flattens the client ops (integer :process, history order) and their micro-ops [f id {..}]; the host plans the O(ops) part
+ * (csrc/ledger_plan.h: which op is which row, the distinct invoked transfer ids), the device does everything that is O(micro-ops)
+ * (csrc/ledger_kernels.h).  All arithmetic is in 64-bit integers; the caller keeps a read's sum of |credits| + |debits| plus
+ * |total_amount| below 2^63 (jepsen/ledger.py LedgerColumns refuses more), so no sum wraps.
+ *
+ * Rows.  Reads are numbered in history order among the ops with type == OK && kind == READ; final reads and final lookups likewise
+ * among the ops that are OK, of their kind, and FINAL.  The caller sizes the output arrays from its own columns.
+ *
+ * SI, per OK read: the balance of a micro-op is a - b (credits-posted - debits-posted), nil under TBC_LEDGER_M_NIL;
+ *   unexpected = its micro-ops whose id is no account, nil = those whose balance is nil, total = the sum of the non-nil balances of ALL
+ *   its micro-ops.  read_error is the first that holds, in check-op's cond order: 1 unexpected-key (unexpected > 0), 2 nil-balance,
+ *   3 wrong-total (total != total_amount), 4 negative-value (!negative_balances and some balance < 0), else 0.  read_badness by type:
+ *   1 unexpected, 2 nil, 3 |total - total_amount|, 4 -(the sum of the negative balances).
+ *   THIS DEPARTS FROM THE REFERENCE ON PURPOSE: its err-badness of a wrong total is (float (/ (- total expected) expected)), which throws
+ *   with the reference's own default :total-amount 0 and collapses near values to equal floats; the integer distance picks the same
+ *   worst op wherever that float is defined and distinct.
+ *   Per type: count, first and last (read numbers), worst = the read of the greatest badness; for wrong-total also lowest / highest =
+ *   the reads of the least / greatest total.  Ties go to the EARLIEST read (jepsen.util/max-by, min-by: only a strictly greater element
+ *   replaces the held one).  first_error = the least read number with an error; valid_si = no error.
+ * lookup-transfers: T = the distinct ids of all micro-ops of the ops with INVOKE && kind == TRANSFER.  lookup_missing[l] = |T| - |T and
+ *   the ids of final lookup l| (repeated ids count once, ids nobody invoked not at all); suspect_lookups = the rows with missing > 0;
+ *   valid_lookups = none.
+ * final-reads: a final row is UNLIKE when its micro-ops are not the first final row's: the same count and, position by position, the
+ *   same id, a, b, c, flags (vector equality: order matters).  valid_final_reads = n_final_reads >= 1 && n_final_lookups >= 1 && nothing
+ *   unlike (no final row at all is the reference's (not= 1 (count ...))).
+ *
+ * Every rule of the struct is checked on the host before any device call -- non-null pointers, mop_off ascending from 0, index strictly
+ * ascending (and never TBC_NO_OP), type, kind and the op flags in range, accounts distinct, and within each OK read the micro-op flags
+ * in range and the ids distinct: TBC_ERR_INVALID_ARG, the message names the entry point and the op.  The micro-ops of transfers and
+ * lookups are never looked at on the host: their flag bytes are compared as they are (final-reads) and otherwise not read.  Valid input without a gfx950 device: TBC_ERR_NO_DEVICE (no CPU
+ * fallback).  One-shot and re-entrant: one device allocation, a stream and events of its own, all gone on every path out, and the
+ * calling thread's current device as it was; columns that do not fit the device: TBC_ERR_OOM. */
+enum { TBC_LEDGER_T_INVOKE = 0, TBC_LEDGER_T_OK = 1, TBC_LEDGER_T_FAIL = 2, TBC_LEDGER_T_INFO = 3 };
+enum { TBC_LEDGER_K_OTHER = 0, TBC_LEDGER_K_TRANSFER = 1, TBC_LEDGER_K_READ = 2, TBC_LEDGER_K_LOOKUP = 3 }; /* f of the op's FIRST micro-op (op->txn-f) */
+#define TBC_LEDGER_F_FINAL 1u   /* op flag: :final? */
+#define TBC_LEDGER_M_NIL   1u   /* micro-op flag: its third element is nil */
+enum { TBC_LEDGER_E_NONE = 0, TBC_LEDGER_E_UNEXPECTED_KEY = 1, TBC_LEDGER_E_NIL_BALANCE = 2, TBC_LEDGER_E_WRONG_TOTAL = 3, TBC_LEDGER_E_NEGATIVE_VALUE = 4 };
+/* A final lookup's transfer numbers are gathered in a window of this many 32-bit words of LDS (csrc/ledger_kernels.h); more than 32 x
+ * this many invoked transfers take one pass over the lookup's ids per window. */
+#define TBC_LEDGER_LOOKUP_WINDOW_WORDS 8192u
+
+typedef struct tbc_ledger_in {
+  uint32_t n_ops, device;                 /* client ops (integer :process) in history order */
+  const uint32_t* index;                  /* strictly ascending, never TBC_NO_OP */
+  const uint8_t *type, *kind, *flags;
+  const uint64_t* mop_off;                /* [n_ops + 1] ascending from 0 */
+  const int64_t *mop_id, *mop_a, *mop_b, *mop_c;  /* :r  a = credits-posted, b = debits-posted;  :t / :l-t  a = debit-acct, b = credit-acct, c = amount */
+  const uint8_t* mop_flags;
+  const int64_t* accounts; uint32_t n_accounts; uint32_t negative_balances;   /* accounts in any order, distinct */
+  int64_t total_amount;
+} tbc_ledger_in;
+
+typedef struct tbc_ledger_errors {        /* one error type: read numbers, TBC_NO_OP where there is none */
+  uint32_t count, first, last, worst;
+} tbc_ledger_errors;
+
+typedef struct tbc_ledger_summary {
+  uint32_t read_count, error_count, first_error;      /* first_error: a read number, TBC_NO_OP if none */
+  uint32_t lowest, highest;                           /* wrong-total: the reads of the least / greatest total */
+  uint32_t n_transfers;                               /* |T| */
+  tbc_ledger_errors errors[5];                        /* [TBC_LEDGER_E_*]; [0] is not used */
+  uint32_t n_final_reads, final_reads_unlike;
+  uint32_t n_final_lookups, final_lookups_unlike, suspect_lookups;
+  uint8_t valid_si, valid_lookups, valid_final_reads, reserved0;
+  uint64_t ns_device;                                 /* the kernels, between HIP events */
+  uint64_t bytes_in;                                  /* copied to the device */
+} tbc_ledger_summary;
+
+typedef struct tbc_ledger_out {           /* arrays caller-allocated, each optional (NULL = not wanted) */
+  uint8_t* read_error;                    /* [n_ok_reads] TBC_LEDGER_E_* */
+  int64_t *read_total, *read_badness;     /* [n_ok_reads] (badness: 0 where there is no error) */
+  uint32_t* lookup_missing;               /* [n_final_lookups] */
+  uint8_t *final_read_unlike, *final_lookup_unlike;   /* [n_final_reads], [n_final_lookups]: 1 = not the first row's micro-ops */
+  tbc_ledger_summary summary;
+} tbc_ledger_out;
+tbc_status tbc_ledger_check(const tbc_ledger_in* in, tbc_ledger_out* out);
+
 /* ------------------------------------------------------------------- misc */
 uint32_t tbc_version(void);             /* TBC_ABI_VERSION                       */
 const char* tbc_strerror(int status);

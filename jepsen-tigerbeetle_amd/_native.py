@@ -200,6 +200,41 @@ class SetFullEncoding(C.Structure):
                 ("unknown_values", C.POINTER(C.c_uint64)), ("ns_encode", C.c_uint64)]
 
 
+# tbc_ledger_check: the ledger workload's checkers from op columns (include/tbcheck.h TBC_LEDGER_*)
+LEDGER_T_INVOKE, LEDGER_T_OK, LEDGER_T_FAIL, LEDGER_T_INFO = 0, 1, 2, 3
+LEDGER_K_OTHER, LEDGER_K_TRANSFER, LEDGER_K_READ, LEDGER_K_LOOKUP = 0, 1, 2, 3
+LEDGER_F_FINAL = 1
+LEDGER_M_NIL = 1
+LEDGER_E_NONE, LEDGER_E_UNEXPECTED_KEY, LEDGER_E_NIL_BALANCE, LEDGER_E_WRONG_TOTAL, LEDGER_E_NEGATIVE_VALUE = range(5)
+LEDGER_LOOKUP_WINDOW_WORDS = 8192
+
+
+class LedgerIn(C.Structure):
+    _fields_ = [("n_ops", C.c_uint32), ("device", C.c_uint32), ("index", C.POINTER(C.c_uint32)), ("type", C.POINTER(C.c_uint8)),
+                ("kind", C.POINTER(C.c_uint8)), ("flags", C.POINTER(C.c_uint8)), ("mop_off", C.POINTER(C.c_uint64)),
+                ("mop_id", C.POINTER(C.c_int64)), ("mop_a", C.POINTER(C.c_int64)), ("mop_b", C.POINTER(C.c_int64)),
+                ("mop_c", C.POINTER(C.c_int64)), ("mop_flags", C.POINTER(C.c_uint8)), ("accounts", C.POINTER(C.c_int64)),
+                ("n_accounts", C.c_uint32), ("negative_balances", C.c_uint32), ("total_amount", C.c_int64)]
+
+
+class LedgerErrors(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("worst", C.c_uint32)]
+
+
+class LedgerSummary(C.Structure):
+    _fields_ = [("read_count", C.c_uint32), ("error_count", C.c_uint32), ("first_error", C.c_uint32), ("lowest", C.c_uint32),
+                ("highest", C.c_uint32), ("n_transfers", C.c_uint32), ("errors", LedgerErrors * 5), ("n_final_reads", C.c_uint32),
+                ("final_reads_unlike", C.c_uint32), ("n_final_lookups", C.c_uint32), ("final_lookups_unlike", C.c_uint32),
+                ("suspect_lookups", C.c_uint32), ("valid_si", C.c_uint8), ("valid_lookups", C.c_uint8), ("valid_final_reads", C.c_uint8),
+                ("reserved0", C.c_uint8), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64)]
+
+
+class LedgerOut(C.Structure):
+    _fields_ = [("read_error", C.POINTER(C.c_uint8)), ("read_total", C.POINTER(C.c_int64)), ("read_badness", C.POINTER(C.c_int64)),
+                ("lookup_missing", C.POINTER(C.c_uint32)), ("final_read_unlike", C.POINTER(C.c_uint8)),
+                ("final_lookup_unlike", C.POINTER(C.c_uint8)), ("summary", LedgerSummary)]
+
+
 class BatchInput(C.Structure):
     """tbc_batch_input: pointers into one pinned slot of a batch (tbc_batch_map_input)."""
     _fields_ = [("n_hist_cap", C.c_uint32), ("reserved0", C.c_uint32), ("ops_cap", C.c_uint64),
@@ -270,6 +305,7 @@ SYMBOLS = {
     "tbc_setfull_keys_create_ops": (C.c_int, [C.POINTER(SetFullOpsIn), C.POINTER(C.c_void_p)]),
     "tbc_setfull_keys_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "tbc_setfull_keys_encoding": (C.c_int, [C.c_void_p, C.POINTER(SetFullEncoding)]),
+    "tbc_ledger_check": (C.c_int, [C.POINTER(LedgerIn), C.POINTER(LedgerOut)]),
     "tbc_batch_destroy": (None, [C.c_void_p]),
     "tbc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "tbc_comm_init": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),

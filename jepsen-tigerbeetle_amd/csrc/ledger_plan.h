@@ -1,0 +1,209 @@
+// ledger_plan.h -- the host plan of tbc_ledger_check (the ledger workload's checkers, include/tbcheck.h): plain C++ with no HIP call in
+// it.  ledger_host.hip runs every call through it, and so do the emulator program of the kernels (tests/emu/emu_ledger.cpp) and the
+// stand-alone program of the plan (tests/emu/ledger_plan.cpp), so the rules below have one statement in C.
+//
+//   validate   every rule of tbc_ledger_in that the kernels trust, O(ops) + O(read micro-ops)
+//   plan       O(ops) + O(invoked transfer micro-ops): the row tables -- for each OK read, final read and final lookup its slice of
+//              the micro-op columns (where it starts, and a running sum of the lengths: a lane finds its row by a binary search of
+//              that) --, the RUNS the SI kernel's workgroups take (consecutive reads of at most kLgRunMops micro-ops and kLgRunReads
+//              reads together; a longer read is a run of its own), the distinct invoked transfer ids, the sorted accounts, and the
+//              arena as named regions with 256 B starts.  The lookups' micro-ops -- the big part -- are never looked at here.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <unordered_set>
+#include <vector>
+#include "../../include/tbcheck.h"
+#include "enc_table.h"
+#include "set_full_encode_plan.h"          // sfenc::table_slots
+
+namespace lg {
+
+constexpr uint32_t kLgRunMops = 256;        // micro-ops a run's reads have together (one step of a workgroup of 256), unless it is one long read
+constexpr uint32_t kLgRunReads = 256;       // reads per run at most: their accumulators are LDS words, a thread per read classifies
+constexpr uint32_t kLgAcctLds = 1024;       // accounts kept in LDS at most (more: the binary search reads global memory)
+
+// what the kernels add up, in device memory (the head of the arena; the host writes the start values).  Read numbers; a `last` is
+// kept as number + 1 (0: none), the extremes' values as order-preserving unsigned keys (lg_key)
+struct LgAcc {
+  uint32_t count[5], first[5], last1[5], worst[5];
+  uint32_t lowest, highest, first_error, error_count;
+  unsigned long long worst_key[5], lowest_key, highest_key;
+  uint32_t reads_unlike, lookups_unlike, suspect, pad;
+};
+
+// what the kernels take (ledger_kernels.h), every pointer into the arena
+struct LgArgs {
+  LgAcc* acc; tbc_ledger_summary* summary;
+  const long long *mop_id, *mop_a, *mop_b, *mop_c; const uint8_t* mop_flags;
+  const long long* accounts; uint32_t n_accounts, negative_balances; long long total_amount;
+  const unsigned long long *read_lo, *read_cum; const uint32_t* run_first; uint32_t n_reads, n_runs, grid_si;
+  uint8_t* read_error; long long *read_total, *read_badness;
+  const long long* transfer; void* slots /* SfEncSlot[] */; uint32_t n_transfers, tab_mask;
+  const unsigned long long *fl_lo, *fl_cum; uint32_t n_final_lookups, grid_lookup; uint32_t* missing;
+  const unsigned long long *fr_lo, *fr_cum; uint32_t n_final_reads;
+  uint32_t *fr_unlike, *fl_unlike;          // a byte per row, in whole words
+};
+
+// the final rows of one kind, as lg_rows_equal_kernel takes them
+struct LgRows { const unsigned long long *lo, *cum; uint32_t n, grid; uint32_t* unlike; };
+
+// Every kernel of the call on `stream` (a hipStream_t: this header names no HIP type), in the order ledger_kernels.h gives; defined in
+// ledger.hip, the unit that holds the kernels.  fr_mops / fl_mops: the micro-ops of all final reads / final lookups.  The grids are its
+// to choose (grid_si, grid_lookup of `A` are ignored).
+void launch(void* stream, LgArgs A, unsigned long long fr_mops, unsigned long long fl_mops);
+
+struct LgRegion { size_t at = 0, bytes = 0; };
+struct LgCursor { size_t at = 0; LgRegion take(size_t bytes) { const LgRegion r{at, bytes}; at += (bytes + 255) & ~(size_t)255; return r; } };
+
+// The call's one arena, in order: the head the host makes (ONE image, one copy), the caller's micro-op columns, what the device
+// makes (zeroed before the kernels: the table's slots, the unlike bytes, the lookups' missing counts), the per-read results.
+struct LgArena {
+  LgRegion acc, summary, accounts, transfer, read_lo, read_cum, run_first, fr_lo, fr_cum, fl_lo, fl_cum;        // the head
+  LgRegion mop_id, mop_a, mop_b, mop_c, mop_flags;                                                              // the caller's
+  LgRegion slots, fr_unlike, fl_unlike, missing;                                                                // zeroed
+  LgRegion read_error, read_total, read_badness;
+  size_t bytes = 0;
+  size_t head_bytes() const { return mop_id.at; }
+  size_t zero_bytes() const { return read_error.at - slots.at; }
+};
+
+struct Plan {
+  uint32_t n_reads = 0, n_runs = 0, n_final_reads = 0, n_final_lookups = 0, n_transfers = 0, tab_mask = 0;
+  uint64_t n_mops = 0, tab_slots = 0;
+  std::vector<uint64_t> read_lo, read_cum;            // [n_reads], [n_reads + 1]: read r's micro-ops start at read_lo[r]; read_cum: the lengths summed
+  std::vector<uint32_t> run_first;                    // [n_runs + 1]: run k is reads run_first[k] .. run_first[k + 1]
+  std::vector<uint64_t> fr_lo, fr_cum, fl_lo, fl_cum; // the final reads and the final lookups likewise
+  std::vector<int64_t> transfer;                      // [n_transfers] the distinct invoked transfer ids, in order of first invocation
+  std::vector<int64_t> accounts;                      // sorted
+  LgArena arena;
+};
+
+// false: `err` names the entry point and the op (by its row and its index)
+inline bool validate(const char* fn, const tbc_ledger_in* in, std::string& err) {
+  char buf[256];
+  const auto say = [&](const char* what) { std::snprintf(buf, sizeof buf, "%s: %s", fn, what); err = buf; return false; };
+  const auto fail = [&](const char* what, uint32_t i) {
+    std::snprintf(buf, sizeof buf, "%s: op %u (index %u): %s", fn, i, in->index[i], what);
+    err = buf;
+    return false;
+  };
+  if (!in->mop_off) return say("null argument (mop_off)");
+  if (in->n_ops && (!in->index || !in->type || !in->kind || !in->flags)) return say("null argument (index, type, kind, flags)");
+  if (in->n_accounts && !in->accounts) return say("null argument (accounts)");
+  if (in->negative_balances > 1u) return say("negative_balances is 0 or 1");
+  if (in->mop_off[0] != 0) return say("mop_off[0] must be 0");
+  for (uint32_t i = 0; i < in->n_ops; i++) {
+    if (i && in->index[i] <= in->index[i - 1]) return fail("index must be strictly ascending", i);
+    if (in->index[i] == 0xFFFFFFFFu) return fail("index 2^32 - 1 is TBC_NO_OP", i);
+    if (in->type[i] > TBC_LEDGER_T_INFO) return fail("type is not a TBC_LEDGER_T_*", i);
+    if (in->kind[i] > TBC_LEDGER_K_LOOKUP) return fail("kind is not a TBC_LEDGER_K_*", i);
+    if (in->flags[i] & ~TBC_LEDGER_F_FINAL) return fail("unknown op flags", i);
+    if (in->mop_off[i + 1] < in->mop_off[i]) return fail("mop_off must be ascending", i);
+  }
+  if (in->mop_off[in->n_ops] && (!in->mop_id || !in->mop_a || !in->mop_b || !in->mop_c || !in->mop_flags)) return say("null argument (the micro-op columns)");
+  {
+    std::vector<int64_t> a(in->accounts, in->accounts + in->n_accounts);
+    std::sort(a.begin(), a.end());
+    for (size_t k = 1; k < a.size(); k++)
+      if (a[k] == a[k - 1]) { std::snprintf(buf, sizeof buf, "%s: account %lld is listed twice (accounts must be distinct)", fn, (long long)a[k]); err = buf; return false; }
+  }
+  std::vector<int64_t> ids;
+  for (uint32_t i = 0; i < in->n_ops; i++) {
+    if (in->type[i] != TBC_LEDGER_T_OK || in->kind[i] != TBC_LEDGER_K_READ) continue;
+    const uint64_t lo = in->mop_off[i], hi = in->mop_off[i + 1];
+    bool ascending = true;
+    for (uint64_t m = lo; m < hi; m++) {
+      if (in->mop_flags[m] & ~TBC_LEDGER_M_NIL) return fail("unknown micro-op flags", i);
+      if (m > lo && in->mop_id[m] <= in->mop_id[m - 1]) ascending = false;
+    }
+    if (ascending) continue;                  // (what a read of the accounts in order gives: seen to be distinct in the one pass)
+    ids.assign(in->mop_id + lo, in->mop_id + hi);
+    std::sort(ids.begin(), ids.end());
+    for (size_t k = 1; k < ids.size(); k++)
+      if (ids[k] == ids[k - 1]) return fail("an :ok read names an id twice (ids must be distinct within a read)", i);
+  }
+  return true;
+}
+
+// (the input has passed `validate`.)  false: too much for one call (`err` says what)
+inline bool plan(const char* fn, const tbc_ledger_in* in, Plan& P, std::string& err) {
+  P = Plan{};
+  P.n_mops = in->mop_off[in->n_ops];
+  P.read_cum.push_back(0); P.fr_cum.push_back(0); P.fl_cum.push_back(0);
+  std::unordered_set<int64_t> seen;
+  for (uint32_t i = 0; i < in->n_ops; i++) {
+    const uint64_t lo = in->mop_off[i], n = in->mop_off[i + 1] - lo;
+    const bool final = (in->flags[i] & TBC_LEDGER_F_FINAL) != 0;
+    if (in->type[i] == TBC_LEDGER_T_INVOKE && in->kind[i] == TBC_LEDGER_K_TRANSFER) {
+      for (uint64_t m = lo; m < lo + n; m++)
+        if (seen.insert(in->mop_id[m]).second) P.transfer.push_back(in->mop_id[m]);
+    } else if (in->type[i] == TBC_LEDGER_T_OK && in->kind[i] == TBC_LEDGER_K_READ) {
+      P.read_lo.push_back(lo); P.read_cum.push_back(P.read_cum.back() + n);
+      if (final) { P.fr_lo.push_back(lo); P.fr_cum.push_back(P.fr_cum.back() + n); }
+    } else if (in->type[i] == TBC_LEDGER_T_OK && in->kind[i] == TBC_LEDGER_K_LOOKUP && final) {
+      P.fl_lo.push_back(lo); P.fl_cum.push_back(P.fl_cum.back() + n);
+    }
+  }
+  if (P.transfer.size() >= 0x40000000ull) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "%s: more than 2^30 - 1 distinct invoked transfers in one call", fn);
+    err = buf;
+    return false;
+  }
+  P.n_reads = (uint32_t)P.read_lo.size(); P.n_final_reads = (uint32_t)P.fr_lo.size(); P.n_final_lookups = (uint32_t)P.fl_lo.size();
+  P.n_transfers = (uint32_t)P.transfer.size();
+  P.tab_slots = sfenc::table_slots(P.n_transfers); P.tab_mask = P.tab_slots ? (uint32_t)(P.tab_slots - 1u) : 0u;
+  // the runs: as many consecutive reads as stay within kLgRunMops micro-ops and kLgRunReads reads; a read of more is alone in its run
+  P.run_first.push_back(0);
+  for (uint32_t r = 0; r < P.n_reads;) {
+    uint32_t e = r + 1;
+    while (e < P.n_reads && e - r < kLgRunReads && P.read_cum[e + 1] - P.read_cum[r] <= kLgRunMops) e++;
+    P.run_first.push_back(e);
+    r = e;
+  }
+  P.n_runs = (uint32_t)P.run_first.size() - 1u;
+  P.accounts.assign(in->accounts, in->accounts + in->n_accounts);
+  std::sort(P.accounts.begin(), P.accounts.end());
+  LgArena& A = P.arena;
+  LgCursor c;
+  const size_t nm = (size_t)P.n_mops, R = P.n_reads, FR = P.n_final_reads, FL = P.n_final_lookups;
+  A.acc = c.take(sizeof(LgAcc)); A.summary = c.take(sizeof(tbc_ledger_summary));
+  A.accounts = c.take(P.accounts.size() * 8); A.transfer = c.take((size_t)P.n_transfers * 8);
+  A.read_lo = c.take(R * 8); A.read_cum = c.take((R + 1) * 8); A.run_first = c.take(P.run_first.size() * 4);
+  A.fr_lo = c.take(FR * 8); A.fr_cum = c.take((FR + 1) * 8); A.fl_lo = c.take(FL * 8); A.fl_cum = c.take((FL + 1) * 8);
+  A.mop_id = c.take(nm * 8); A.mop_a = c.take(nm * 8); A.mop_b = c.take(nm * 8); A.mop_c = c.take(nm * 8); A.mop_flags = c.take(nm);
+  A.slots = c.take((size_t)P.tab_slots * sizeof(SfEncSlot));
+  A.fr_unlike = c.take((FR + 3) / 4 * 4); A.fl_unlike = c.take((FL + 3) / 4 * 4);      // (whole 32-bit words: a byte is set by an atomic OR on its word)
+  A.missing = c.take(FL * 4);
+  A.read_error = c.take(R); A.read_total = c.take(R * 8); A.read_badness = c.take(R * 8);
+  A.bytes = c.at;
+  return true;
+}
+
+// the accumulators' start values
+inline LgAcc acc_start() {
+  LgAcc a{};
+  for (int k = 0; k < 5; k++) { a.first[k] = 0xFFFFFFFFu; a.worst[k] = 0xFFFFFFFFu; }
+  a.lowest = a.highest = a.first_error = 0xFFFFFFFFu;
+  a.lowest_key = ~0ull;
+  return a;
+}
+
+// the head of the arena as one image
+inline std::vector<unsigned char> head_image(const Plan& P) {
+  const LgArena& A = P.arena;
+  std::vector<unsigned char> img(A.head_bytes(), 0);
+  const LgAcc a = acc_start();
+  const auto put = [&](const LgRegion& r, const void* src) { if (r.bytes) std::copy((const unsigned char*)src, (const unsigned char*)src + r.bytes, img.begin() + r.at); };
+  put(A.acc, &a);
+  put(A.accounts, P.accounts.data()); put(A.transfer, P.transfer.data());
+  put(A.read_lo, P.read_lo.data()); put(A.read_cum, P.read_cum.data()); put(A.run_first, P.run_first.data());
+  put(A.fr_lo, P.fr_lo.data()); put(A.fr_cum, P.fr_cum.data()); put(A.fl_lo, P.fl_lo.data()); put(A.fl_cum, P.fl_cum.data());
+  return img;
+}
+
+}  // namespace lg

@@ -44,22 +44,7 @@ struct SfEncArgs {
   uint32_t* dup_count;                       // [n_keys]
 };
 
-__device__ __forceinline__ uint32_t sf_enc_hash(long long v) {               // (the finaliser of splitmix64)
-  unsigned long long x = (unsigned long long)v;
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-  return (uint32_t)x;
-}
-
-// the column of value v in a key's table, kNoneU if the key has no such element.  The table is at most half full: a probe sequence ends.
-__device__ __forceinline__ uint32_t sf_enc_lookup(const SfEncSlot* __restrict__ tab, uint32_t mask, long long v) {
-  uint32_t s = sf_enc_hash(v) & mask;
-  for (;;) {
-    const SfEncSlot e = tab[s];
-    if (e.col1 == 0u) return kNoneU;
-    if (e.value == v) return e.col1 - 1u;
-    s = (s + 1u) & mask;
-  }
-}
+// (sf_enc_hash and sf_enc_lookup, the probe of a table, are enc_table.h's: the ledger checkers probe a table of the same slots)
 
 // the key that holds element g of the object (elements lie key after key): the last key whose elem_base is <= g -- a key without
 // elements shares its successor's base and is never picked

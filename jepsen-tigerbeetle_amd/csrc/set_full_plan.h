@@ -9,10 +9,10 @@
 #include <cstdint>
 #include <vector>
 #include "set_full_encode_plan.h"          // sfenc::table_slots: the capacity of a key's element table (Ops)
+#include "enc_table.h"                     // kNoneU, SfEncSlot and the probe of an element table (shared with the ledger checkers)
 
 namespace {
 
-constexpr uint32_t kNoneU = 0xFFFFFFFFu;
 constexpr uint32_t kSetFullRows = 2048;      // rows per chunk at most (their metadata is staged in LDS)
 constexpr uint32_t kWordCounters = 256;      // the words-loaded statistic: a wavefront adds to counter (its workgroup mod 256), 128 B apart -- thousands of
                                              // atomics on ONE address queue up in one L2 channel; the host adds the counters up
@@ -33,7 +33,6 @@ enum { kFirstRows = 0, kFirstPrefix, kFirstAny, kFirstResolve, kFirstSelect, kFi
                                                                                          // (kFirstSelect: the results' passes, set_full_results.h)
 
 // tbc_setfull_keys_create_ops: a key's open-addressing table of element values (set_full_encode.h)
-struct alignas(16) SfEncSlot { long long value; uint32_t col1, pad; };       // col1 = column + 1, 0 = free
 struct SfEncKey { unsigned long long tab_off; uint32_t mask, pad; };         // the key's table: slots tab_off .. tab_off + mask (E = 0: none)
 
 #if defined(__HIPCC__) || defined(TBC_EMU)
