@@ -898,6 +898,79 @@ typedef struct tbc_ledger_out {           /* arrays caller-allocated, each optio
 } tbc_ledger_out;
 tbc_status tbc_ledger_check(const tbc_ledger_in* in, tbc_ledger_out* out);
 
+/* ------------------------------------------------------------------- perf: the series behind the reference's perf plots
+ * checker/perf.clj composes latency-graph, rate-graph and open-ops-graph into every test.  What it PLOTS is out of scope (gnuplot,
+ * ranges, nemesis shading); the SERIES it plots are computed here from op columns, decided on the device (csrc/perf_*.h;
+ * jepsen/perf.py is the host statement and says every rule in full).  One row per op of the history, ALL ops, in history order:
+ *   time     the op's :time in ns, 0 <= time < 2^52 (below that the reference's long(double(t) / 1e9) is t / 10^9 on integers)
+ *   process  the client's :process; INT32_MIN where the op is not a client's (the nemesis): such an op enters t_max and nothing else
+ *   type     TBC_PERF_T_*
+ *   f        for a client op the number of its :f, numbered from 0 by first appearance among the client ops; n_f of them
+ *   flags    TBC_PERF_F_CLIENT on exactly the ops whose process is not INT32_MIN
+ * Pairing is the host plan's (knossos.history/pair-index: an invocation is completed by its process's next completion; a process's
+ * second invocation leaves the first unmatched; a completion with nothing open is paired with nothing).  The OUTCOME of an
+ * invocation is its completion's type (TBC_PERF_T_OK / FAIL / INFO), TBC_PERF_O_NONE if it has none; of a completion, its own type.
+ *   t_max   = the greatest time of all ops, 0 if there is none;  nb_all = t_max / 10^9 + 1 one-second buckets;
+ *   n_plot  = the buckets whose midpoint b + 0.5 is <= t_max / 1e9 compared as doubles (nb_all or nb_all - 1): the buckets plotted
+ *   op_latency[i]     time[partner] - time[i] of a matched invocation, INT64_MIN for every other op
+ *   op_outcome[i]     the outcome as above; TBC_PERF_O_NONE for an op that is not a client's
+ *   op_open_after[i]  client ops with an outcome, per class (f, outcome): the running count in history order, +1 at an invocation,
+ *                     -1 at a completion, as it stands after op i; 0 for every other op
+ *   q_count[f][b]     the matched invocations of f whose OWN time is in bucket b (all outcomes together)
+ *   q_value[f][b][j]  of their latencies in ascending order the one at min(n - 1, floor(n * q_j)), q = .5 .95 .99 1, n * q in
+ *                     double; 0 where q_count is 0
+ *   rate_count[f][o][b]  the client completions of f and type o + 1 (o = 0 OK, 1 FAIL, 2 INFO) whose own time is in bucket b
+ *   open_last[f][o][b]   op_open_after of the LAST op in history order of class (f, o + 1) whose own time is in b; INT32_MIN: none
+ *   open_fill[f][o][b]   b < n_plot: open_last carried forward over the buckets that have none, from 0
+ * The caller sizes the arrays from tbc_perf_plan_sizes on the same input: the host plan alone, no device work.  n_f * 4 * nb_all
+ * must stay below 2^31 (TBC_ERR_UNSUPPORTED).  A time out of range (an op without :time is passed as INT64_MIN) is
+ * TBC_ERR_BAD_HISTORY; every other rule of the struct TBC_ERR_INVALID_ARG; the message names the entry point and the op.  Valid
+ * input without a gfx950 device: TBC_ERR_NO_DEVICE (no CPU fallback).  One-shot and re-entrant as tbc_ledger_check is. */
+enum { TBC_PERF_T_INVOKE = 0, TBC_PERF_T_OK = 1, TBC_PERF_T_FAIL = 2, TBC_PERF_T_INFO = 3 };
+#define TBC_PERF_O_NONE   0u    /* op_outcome: none (otherwise a TBC_PERF_T_*) */
+#define TBC_PERF_F_CLIENT 1u
+#define TBC_PERF_NO_PROCESS INT32_MIN
+#define TBC_PERF_QUANTILES 4u   /* .5 .95 .99 1 */
+/* A (f, bucket) cell of at most this many latencies is sorted in LDS by one workgroup; a larger one takes the radix select. */
+#define TBC_PERF_SELECT_TILE 2048u
+
+typedef struct tbc_perf_in {
+  uint32_t n_ops, device;
+  const int64_t* time;
+  const int32_t* process;
+  const uint8_t *type, *flags;
+  const uint16_t* f;
+  uint32_t n_f, reserved0;
+} tbc_perf_in;
+
+typedef struct tbc_perf_sizes {
+  uint32_t n_ops, n_f, nb_all, n_plot;
+  int64_t t_max;
+} tbc_perf_sizes;
+
+typedef struct tbc_perf_summary {
+  uint32_t n_ops, n_client, n_invocations, n_matched;   /* n_matched: invocations with a completion = latencies */
+  uint32_t n_completions, n_f, nb_all, n_plot;          /* n_completions: client ops that are no invocation */
+  uint32_t max_cell, reserved0;                         /* the greatest q_count */
+  int64_t t_max;
+  uint64_t ns_device;                                   /* the kernels, between HIP events */
+  uint64_t bytes_in;                                    /* copied to the device */
+} tbc_perf_summary;
+
+typedef struct tbc_perf_out {             /* arrays caller-allocated, each optional (NULL = not wanted) */
+  int64_t* op_latency;                    /* [n_ops] */
+  uint8_t* op_outcome;                    /* [n_ops] */
+  int32_t* op_open_after;                 /* [n_ops] */
+  uint32_t* q_count;                      /* [n_f][nb_all] */
+  int64_t* q_value;                       /* [n_f][nb_all][4] ns */
+  uint32_t* rate_count;                   /* [n_f][3][nb_all] */
+  int32_t* open_last;                     /* [n_f][3][nb_all] */
+  int32_t* open_fill;                     /* [n_f][3][n_plot] */
+  tbc_perf_summary summary;
+} tbc_perf_out;
+tbc_status tbc_perf_plan_sizes(const tbc_perf_in* in, tbc_perf_sizes* sizes);
+tbc_status tbc_perf_series(const tbc_perf_in* in, tbc_perf_out* out);
+
 /* ------------------------------------------------------------------- misc */
 uint32_t tbc_version(void);             /* TBC_ABI_VERSION                       */
 const char* tbc_strerror(int status);

@@ -235,6 +235,36 @@ class LedgerOut(C.Structure):
                 ("final_lookup_unlike", C.POINTER(C.c_uint8)), ("summary", LedgerSummary)]
 
 
+# tbc_perf_series: the series behind the reference's perf plots from op columns (include/tbcheck.h TBC_PERF_*)
+PERF_T_INVOKE, PERF_T_OK, PERF_T_FAIL, PERF_T_INFO = 0, 1, 2, 3
+PERF_O_NONE = 0
+PERF_F_CLIENT = 1
+PERF_SELECT_TILE = 2048
+
+
+class PerfIn(C.Structure):
+    _fields_ = [("n_ops", C.c_uint32), ("device", C.c_uint32), ("time", C.POINTER(C.c_int64)), ("process", C.POINTER(C.c_int32)),
+                ("type", C.POINTER(C.c_uint8)), ("flags", C.POINTER(C.c_uint8)), ("f", C.POINTER(C.c_uint16)), ("n_f", C.c_uint32),
+                ("reserved0", C.c_uint32)]
+
+
+class PerfSizes(C.Structure):
+    _fields_ = [("n_ops", C.c_uint32), ("n_f", C.c_uint32), ("nb_all", C.c_uint32), ("n_plot", C.c_uint32), ("t_max", C.c_int64)]
+
+
+class PerfSummary(C.Structure):
+    _fields_ = [("n_ops", C.c_uint32), ("n_client", C.c_uint32), ("n_invocations", C.c_uint32), ("n_matched", C.c_uint32),
+                ("n_completions", C.c_uint32), ("n_f", C.c_uint32), ("nb_all", C.c_uint32), ("n_plot", C.c_uint32),
+                ("max_cell", C.c_uint32), ("reserved0", C.c_uint32), ("t_max", C.c_int64), ("ns_device", C.c_uint64),
+                ("bytes_in", C.c_uint64)]
+
+
+class PerfOut(C.Structure):
+    _fields_ = [("op_latency", C.POINTER(C.c_int64)), ("op_outcome", C.POINTER(C.c_uint8)), ("op_open_after", C.POINTER(C.c_int32)),
+                ("q_count", C.POINTER(C.c_uint32)), ("q_value", C.POINTER(C.c_int64)), ("rate_count", C.POINTER(C.c_uint32)),
+                ("open_last", C.POINTER(C.c_int32)), ("open_fill", C.POINTER(C.c_int32)), ("summary", PerfSummary)]
+
+
 class BatchInput(C.Structure):
     """tbc_batch_input: pointers into one pinned slot of a batch (tbc_batch_map_input)."""
     _fields_ = [("n_hist_cap", C.c_uint32), ("reserved0", C.c_uint32), ("ops_cap", C.c_uint64),
@@ -306,6 +336,8 @@ SYMBOLS = {
     "tbc_setfull_keys_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "tbc_setfull_keys_encoding": (C.c_int, [C.c_void_p, C.POINTER(SetFullEncoding)]),
     "tbc_ledger_check": (C.c_int, [C.POINTER(LedgerIn), C.POINTER(LedgerOut)]),
+    "tbc_perf_plan_sizes": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfSizes)]),
+    "tbc_perf_series": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfOut)]),
     "tbc_batch_destroy": (None, [C.c_void_p]),
     "tbc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "tbc_comm_init": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -9,51 +9,23 @@
 #include <new>
 #include <string>
 #include <vector>
-#include "tbc_internal.h"
+#include "oneshot_call.h"
 #include "ledger_plan.h"
 
 using namespace tbc;
 
-#define LG_TRY(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);  \
-      return e_ == hipErrorOutOfMemory ? TBC_ERR_OOM : TBC_ERR_HIP;                          \
-    }                                                                                        \
-  } while (0)
+#define LG_TRY TBC_ONESHOT_TRY
 
 namespace {
 
-// what one call makes on the device: released in this order whichever way the call ends
-struct LgCall {
-  int device_before = -1;                                   // the calling thread's current device, put back on the way out
-  void* arena = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~LgCall() {
-    if (stream) (void)hipStreamSynchronize(stream);       // (a call that failed half way may have left a copy or a kernel in flight)
-    if (arena) (void)hipFree(arena);
-    for (hipEvent_t e : {ev0, ev1}) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (device_before >= 0) (void)hipSetDevice(device_before);
-  }
-};
-
-tbc_status lg_check_device(uint32_t device) {
-  int ndev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || (int)device >= ndev) { set_error("no usable HIP device; libtbcheck has no CPU fallback"); return TBC_ERR_NO_DEVICE; }
-  if (hipGetDeviceProperties(&prop, (int)device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) { set_error("device %u is not a gfx950 (MI355X) device", device); return TBC_ERR_NO_DEVICE; }
-  return TBC_OK;
-}
+using LgCall = OneShotCall;
 
 tbc_status lg_check(const char* fn, const tbc_ledger_in* in, tbc_ledger_out* out) {
   std::string err;
   if (!lg::validate(fn, in, err)) { set_error("%s", err.c_str()); return TBC_ERR_INVALID_ARG; }
   lg::Plan P;
   if (!lg::plan(fn, in, P, err)) { set_error("%s", err.c_str()); return TBC_ERR_INVALID_ARG; }
-  const tbc_status dev = lg_check_device(in->device);
+  const tbc_status dev = oneshot_check_device(in->device);
   if (dev != TBC_OK) return dev;
   const lg::LgArena& L = P.arena;
   const std::vector<unsigned char> img = lg::head_image(P);

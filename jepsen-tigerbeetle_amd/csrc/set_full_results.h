@@ -29,11 +29,11 @@
 #pragma once
 #include "wave_env_wg.h"
 #include "set_full_plan.h"
+#include "radix_select.h"                    // sf_rank, sf_level_used, rs_pick: shared with perf_kernels.h
 
 namespace {
 
 constexpr uint32_t kSelTargets = 7;          // 0-2: stable .5 .95 .99; 3: the 8th greatest stable latency; 4-6: lost .5 .95 .99
-constexpr uint32_t kSelBins = 256;
 constexpr uint32_t kWorst = TBC_SETFULL_WORST;
 
 struct SfKeyAcc {                            // per key; reset by sf_results_init_kernel
@@ -53,10 +53,6 @@ struct SfResArgs {
   SfKeyAcc* acc; SfSel* sel; uint32_t* hist; tbc_setfull_key_summary* summary;
 };
 
-__device__ __forceinline__ uint32_t sf_rank(uint32_t n, double p) {          // Python's min(n - 1, int(n * p))
-  const unsigned long long r = (unsigned long long)((double)n * p);
-  return r < (unsigned long long)(n - 1u) ? (uint32_t)r : n - 1u;
-}
 // how many values target t selects among and the rank it wants (n = 0: the target is off)
 __device__ __forceinline__ void sf_target(const SfKeyAcc& a, uint32_t E, uint32_t t, uint32_t& n, uint32_t& rank) {
   const uint32_t n_stable = E - a.n_lost - a.n_never;
@@ -65,7 +61,6 @@ __device__ __forceinline__ void sf_target(const SfKeyAcc& a, uint32_t E, uint32_
   n = t < 3u ? n_stable : a.n_lost;
   rank = n ? sf_rank(n, p) : 0u;
 }
-__device__ __forceinline__ bool sf_level_used(unsigned long long maxv, uint32_t level) { return (maxv >> (8u * level)) != 0ull; }
 
 __global__ __launch_bounds__(256) void sf_results_init_kernel(SfResArgs A) {
   const uint32_t k = wv::wg_index() * 256u + wv::wg_thread();
@@ -221,16 +216,10 @@ __global__ __launch_bounds__(kSelTargets * 64) void sf_select_pick_kernel(SfResA
   uint4* const g = reinterpret_cast<uint4*>(A.hist + ((uint64_t)key * kSelTargets + t) * kSelBins) + lane;
   const uint4 h = *g;
   *g = make_uint4(0u, 0u, 0u, 0u);
-  const uint32_t mine = h.x + h.y + h.z + h.w;
-  uint32_t incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)incl, d); if (lane >= (uint32_t)d) incl += o; }
-  const uint64_t at = wv::ballot(k < incl);
-  if (lane != (at ? (uint32_t)__builtin_ctzll(at) : 63u)) return;       // (the rank is below the count: some lane holds it)
-  uint32_t left = k - (incl - mine), b = 0u;
-  if (left >= h.x) { left -= h.x; b = 1u; if (left >= h.y) { left -= h.y; b = 2u; if (left >= h.z) { left -= h.z; b = 3u; } } }
+  uint32_t bin = 0u, left = 0u;
+  if (!rs_pick(h, lane, k, bin, left)) return;                          // (one lane goes on: the one whose bins hold the rank)
   const unsigned long long prefix = level == 7u ? 0ull : s->prefix;
-  s->prefix = prefix | ((unsigned long long)(4u * lane + b) << (8u * level));
+  s->prefix = prefix | ((unsigned long long)bin << (8u * level));
   s->k = left;
 }
 

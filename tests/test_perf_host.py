@@ -1,0 +1,163 @@
+"""jepsen/perf.py without a GPU: the host statement against the hand-derived fixtures of tests/golden/perf (README.md there works every
+value), the integer bucket against the reference's float formula at the bucket edges, PerfColumns against the history, the plan's
+rejections through the library's own entry points (they answer before any device call), the composed checker, and the host plan
+(csrc/perf_plan.h) in its stand-alone program, tests/emu/perf_plan.cpp, built with -fsanitize=address,undefined."""
+import ctypes as C
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import perf_histories as G
+from conftest import ROOT
+from jepsen_tigerbeetle_amd import _native as N
+from jepsen_tigerbeetle_amd.jepsen import edn
+from jepsen_tigerbeetle_amd.jepsen import perf as PF
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "perf")
+S = G.S
+
+
+def _keyed(d, quantile=False):
+    return {(k.rsplit(" ", 1)[0], float(k.rsplit(" ", 1)[1]) if quantile else k.rsplit(" ", 1)[1]): [tuple(p) for p in v] for k, v in d.items()}
+
+
+@pytest.mark.parametrize("name", ["basic", "quantiles", "open", "orphan"])
+def test_host_statement_gives_the_hand_derived_series(name):
+    h = edn.read_history(os.path.join(GOLDEN, name + ".edn"))
+    want = json.load(open(os.path.join(GOLDEN, name + ".json")))
+    assert len(h) <= 30
+    a = PF.analyse(h)
+    assert (a["t_max"], a["nb_all"], a["n_plot"]) == (want["t_max"], want["nb_all"], want["n_plot"])
+    got = PF.series_host(h)
+    assert got == PF.series(h, device_route=False)
+    assert set(got) == {"latency_raw", "latency_quantiles", "rate", "open_ops"}
+    for k in got:
+        assert got[k] == _keyed(want[k], quantile=k == "latency_quantiles"), k
+    # y of open_ops is an integer, of rate a float; the f's come in polysort order, the types as ok info fail
+    assert all(isinstance(y, int) for pts in got["open_ops"].values() for _, y in pts)
+    assert all(isinstance(y, float) for pts in got["rate"].values() for _, y in pts)
+    order = [(PF.polysort(a["fs"]).index(f), PF.TYPES.index(t)) for f, t in got["rate"]]
+    assert order == sorted(order)
+
+
+def test_integer_bucket_equals_the_float_formula_at_the_edges():
+    for k in (0, 1, 2, 3, 7, 1000, 2 ** 22 - 1, 2 ** 22, 2 ** 22 + 1, 4503598):
+        for d in (-1, 0, S // 2 - 1, S // 2, S // 2 + 1):
+            t = k * S + d
+            if not 0 <= t < PF.TIME_END:
+                continue
+            assert PF.bucket(t) == PF.bucket_float(t) == (k - 1 if d < 0 else k), t
+            # as t_max: the last bucket is plotted iff its midpoint is <= t_max in the reference's float comparison
+            nb = PF.bucket(t) + 1
+            plotted = sum(1 for b in range(max(0, nb - 3), nb + 2) if b + 0.5 <= float(t) / 1e9) + max(0, nb - 3)
+            assert PF.plotted_buckets(t) == plotted == (nb if (d < 0 or d >= S // 2) else nb - 1), t
+    assert PF.bucket(PF.TIME_END - 1) == PF.bucket_float(PF.TIME_END - 1) == 4503599
+    assert PF.plotted_buckets(0) == 0 and PF.analyse([])["nb_all"] == 1
+    for n in range(1, 131):                                                   # the rank, beside the float product it is defined by
+        assert [PF.rank(n, q) for q in PF.QS] == [min(n - 1, int(n * 0.5)), min(n - 1, int(n * 0.95)), min(n - 1, int(n * 0.99)), n - 1]
+
+
+def test_columns_round_trip():
+    h = G.random_history(5, 300, workers=6, fs=("read", "write", "cas"), info=0.2)
+    cols = PF.PerfColumns(h)
+    assert len(cols) == len(h) and cols.time.dtype == np.int64 and cols.process.dtype == np.int32 and cols.f.dtype == np.uint16
+    seen = []
+    for i, op in enumerate(h):
+        assert cols.time[i] == op["time"]
+        if PF.H.client_op(op):
+            if op["f"] not in seen:
+                seen.append(op["f"])
+            back = {"type": PF.OUTCOMES[cols.type[i]] or "invoke", "f": cols.fs[cols.f[i]], "process": int(cols.process[i]), "time": int(cols.time[i])}
+            assert back == {k: op[k] for k in back} and cols.flags[i] == N.PERF_F_CLIENT
+        else:
+            assert cols.process[i] == PF.INT32_MIN and cols.flags[i] == 0
+    assert cols.fs == seen == PF.analyse(h)["fs"]
+    assert PF.plan_sizes(cols) == {"n_ops": 300, "n_f": 3, "nb_all": PF.analyse(h)["nb_all"], "n_plot": PF.analyse(h)["n_plot"], "t_max": PF.analyse(h)["t_max"]}
+    for bad in ({"process": 2 ** 31}, {"process": PF.INT32_MIN}, {"type": "sleep"}):
+        with pytest.raises(ValueError):
+            PF.PerfColumns([dict(h[0], **bad)])
+    e = PF.PerfColumns([])
+    assert len(e) == 0 and e.fs == [] and PF.plan_sizes(e) == {"n_ops": 0, "n_f": 0, "nb_all": 1, "n_plot": 0, "t_max": 0}
+
+
+@pytest.mark.parametrize("entry", ["plan_sizes", "check_native"])
+def test_the_plan_rejects(entry, native):
+    call = getattr(PF, entry)
+    h = G.Builder().pair("read", 0, 10, 100).pair("write", 1, 200, 100).nemesis(900).h
+
+    def status(history):
+        with pytest.raises(N.TbcError) as e:
+            call(PF.PerfColumns(history))
+        assert not isinstance(e.value, N.NoDeviceError)
+        return e.value.status, str(e.value)
+
+    no_time = [dict(op) for op in h]
+    del no_time[4]["time"]
+    assert status(no_time)[0] == N.ERR_BAD_HISTORY and "op 4: the op has no :time" in status(no_time)[1]
+    assert status([dict(h[0], time=None)] + h[1:])[0] == N.ERR_BAD_HISTORY
+    st, msg = status(h[:2] + [dict(h[2], time=-1)] + h[3:])
+    assert st == N.ERR_BAD_HISTORY and "op 2: negative :time" in msg and msg.count("tbc_perf_") == 1
+    st, msg = status(h[:3] + [dict(h[3], time=2 ** 52)] + h[4:])
+    assert st == N.ERR_BAD_HISTORY and "op 3: :time is 2^52 ns or more" in msg
+    call_ok = h[:3] + [dict(h[3], time=2 ** 52 - 1)]                          # the largest time there is: 4,503,600 buckets x 2 f's x 4 is fine ...
+    if entry == "plan_sizes":
+        assert PF.plan_sizes(PF.PerfColumns(call_ok))["nb_all"] == 4503600
+    many = [dict(op) for op in call_ok]
+    for i in range(150):                                                      # ... x 152 f's is not
+        many.append({"type": "invoke", "f": f"f{i}", "value": None, "process": 10 + i, "time": 5})
+    st, msg = status(many)
+    assert st == N.ERR_UNSUPPORTED and "2^31 cells or more" in msg
+    # the host statement refuses the same times
+    for bad in (no_time, h[:2] + [dict(h[2], time=-1)], h[:3] + [dict(h[3], time=2 ** 52)]):
+        with pytest.raises(ValueError):
+            PF.series(bad, device_route=False)
+
+
+def test_structs_and_symbols(native, tmp_path):
+    for name in ("tbc_perf_plan_sizes", "tbc_perf_series"):
+        assert name in native.SYMBOLS and hasattr(native.lib(), name)
+    assert native.lib().tbc_version() == 2
+    structs = {"tbc_perf_in": N.PerfIn, "tbc_perf_sizes": N.PerfSizes, "tbc_perf_summary": N.PerfSummary, "tbc_perf_out": N.PerfOut}
+    lines = []
+    for name, cls in structs.items():
+        lines.append('printf("%%zu", sizeof(%s));' % name)
+        lines += ['printf(" %%zu", offsetof(%s, %s));' % (name, f) for f, _ in cls._fields_]
+        lines.append('printf("\\n");')
+    lines.append('printf("%u %u %u %u\\n", TBC_PERF_T_INVOKE, TBC_PERF_T_OK, TBC_PERF_T_FAIL, TBC_PERF_T_INFO);')
+    lines.append('printf("%u %u %u %d\\n", TBC_PERF_O_NONE, TBC_PERF_F_CLIENT, TBC_PERF_SELECT_TILE, TBC_PERF_NO_PROCESS);')
+    src = tmp_path / "s.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "tbcheck.h"\nint main(void){ %s return 0; }\n' % "\n".join(lines))
+    exe = str(tmp_path / "s")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    rows = [[int(x) for x in line.split()] for line in subprocess.check_output([exe], text=True).splitlines()]
+    for (name, cls), row in zip(structs.items(), rows):
+        assert [C.sizeof(cls)] + [getattr(cls, f).offset for f, _ in cls._fields_] == row, name
+    assert rows[4] == [N.PERF_T_INVOKE, N.PERF_T_OK, N.PERF_T_FAIL, N.PERF_T_INFO]
+    assert rows[5] == [N.PERF_O_NONE, N.PERF_F_CLIENT, N.PERF_SELECT_TILE, PF.INT32_MIN]
+
+
+def test_perf_composes_three_members_that_answer_valid():
+    h = edn.read_history(os.path.join(GOLDEN, "open.edn"))
+    res = PF.perf({"device_route": False}).check({}, h, {})
+    assert res == {"latency-graph": {"valid?": True}, "rate-graph": {"valid?": True}, "open-ops-graph": {"valid?": True}, "valid?": True}
+    seen = []
+    real, PF.series = PF.series, lambda *a, **k: seen.append(a[1:]) or real(*a, **k)
+    try:
+        assert PF.perf({"device_route": False, "device": 0}).check({}, h, {})["valid?"] is True
+    finally:
+        PF.series = real
+    assert seen == [(False, 0)]                                               # ONE computation for the three members, by the route asked for
+    with pytest.raises(ValueError):                                           # a history the series cannot be made from raises
+        PF.perf({"device_route": False}).check({}, [dict(h[0], time=None)], {})
+
+
+def test_the_plan_program_under_address_and_undefined_sanitizers(tmp_path):
+    exe = str(tmp_path / "perf_plan")
+    subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "jepsen-tigerbeetle_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "emu", "perf_plan.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "planned and checked" in out.stdout and not out.stderr, (out.stdout, out.stderr)
