@@ -898,6 +898,56 @@ typedef struct tbc_ledger_out {           /* arrays caller-allocated, each optio
 } tbc_ledger_out;
 tbc_status tbc_ledger_check(const tbc_ledger_in* in, tbc_ledger_out* out);
 
+/* ------------------------------------------------------------------- ledger: realtime bounds on the posted counters
+ * credits-posted and debits-posted of an account only grow, so every counter an :ok read returns has three bounds in real time: at least
+ * what the transfers that had completed :ok before the read was invoked add up to (else the read is STALE), at most what the transfers
+ * invoked before the read completed add up to (FUTURE), at least what any read that completed before its invocation saw (REGRESSED) --
+ * a necessary condition for strict serializability in O(n log n).  THE RULES ARE STATED ONCE, in the docstring of jepsen/ledger.py
+ * ("Realtime bounds"): transfers, reads, checked micro-ops, lo / hi / floor, the bits, the misses, the summary, the ranges.
+ * Input: a tbc_ledger_in (total_amount and negative_balances are not used) plus
+ *   process             [n_ops] the op's :process: pairing is knossos.history/pair-index, by process, as tbc_perf_series pairs
+ *   init_credits/debits [n_accounts] the counters' initial values in the order of `accounts`, |x| < 2^61; NULL = zeros
+ *   ok_transfers_apply  0 or 1: whether an :ok transfer is known to have been applied (the lower bound counts it)
+ * Rows: reads are numbered as for tbc_ledger_check; read micro-ops in the order of the columns, over the OK reads.
+ *   rt_bits[r]       1 stale credits, 2 stale debits, 4 future credits, 8 future debits, 16 regressed credits, 32 regressed debits
+ *   rt_miss[r][k]    k = TBC_LEDGER_RT_STALE / FUTURE / REGRESSED: the greatest miss of that kind over the read's micro-ops and both
+ *                    fields, saturating at INT64_MAX; 0 if there is none
+ *   mop_lo/hi/floor[m][x]  x = 0 credits-posted, 1 debits-posted: the bounds of read micro-op m, all INT64_MIN where it is not checked
+ *                    (nil, or its id no account); floor is INT64_MIN where no earlier read checked the account
+ * The host plans what is O(ops) (csrc/ledger_rt_plan.h) and never reads a transfer's micro-ops; the device does the rest
+ * (csrc/ledger_rt_kernels.h).  Every rule of tbc_ledger_in, and process non-null, |init| < 2^61, ok_transfers_apply in range, fewer
+ * than 2^31 micro-ops of transfers and of reads: TBC_ERR_INVALID_ARG before any device call, the message names the entry point and the
+ * op.  An amount outside [0, 2^31) among the micro-ops of the transfers that did not fail is counted ON THE DEVICE:
+ * TBC_ERR_UNSUPPORTED, no results, summary.bad_amounts says how many.  No gfx950 device: TBC_ERR_NO_DEVICE.  One-shot and
+ * re-entrant as tbc_ledger_check is. */
+enum { TBC_LEDGER_RT_STALE = 0, TBC_LEDGER_RT_FUTURE = 1, TBC_LEDGER_RT_REGRESSED = 2 };
+
+typedef struct tbc_ledger_rt_in {
+  tbc_ledger_in ledger;
+  const int32_t* process;                 /* [n_ops] */
+  const int64_t *init_credits, *init_debits;  /* [n_accounts], NULL = zeros */
+  uint32_t ok_transfers_apply, reserved0;
+} tbc_ledger_rt_in;
+
+typedef struct tbc_ledger_rt_summary {
+  uint32_t read_count, error_count, first_error, valid;   /* error_count: reads with any bit; first_error: TBC_NO_OP if none */
+  tbc_ledger_errors errors[3];                            /* [TBC_LEDGER_RT_*]: read numbers; worst = the greatest miss, ties the earliest */
+  uint32_t n_definite, n_possible;                        /* transfers that completed :ok; transfers that did not fail */
+  uint32_t foreign_sides;                                 /* sides of the micro-ops of the transfers that did not fail that name no account (a nil micro-op: both); skipped */
+  uint32_t bad_amounts;                                   /* amounts outside [0, 2^31) among them */
+  uint64_t n_checked;                                     /* read micro-ops checked */
+  uint64_t ns_device;                                     /* the kernels, between HIP events */
+  uint64_t bytes_in;                                      /* copied to the device */
+} tbc_ledger_rt_summary;
+
+typedef struct tbc_ledger_rt_out {        /* arrays caller-allocated, each optional (NULL = not wanted) */
+  uint8_t* rt_bits;                       /* [n_ok_reads] */
+  int64_t* rt_miss;                       /* [n_ok_reads][3] */
+  int64_t *mop_lo, *mop_hi, *mop_floor;   /* [n_read_mops][2] */
+  tbc_ledger_rt_summary summary;
+} tbc_ledger_rt_out;
+tbc_status tbc_ledger_realtime(const tbc_ledger_rt_in* in, tbc_ledger_rt_out* out);
+
 /* ------------------------------------------------------------------- perf: the series behind the reference's perf plots
  * checker/perf.clj composes latency-graph, rate-graph and open-ops-graph into every test.  What it PLOTS is out of scope (gnuplot,
  * ranges, nemesis shading); the SERIES it plots are computed here from op columns, decided on the device (csrc/perf_*.h;

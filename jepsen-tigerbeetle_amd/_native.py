@@ -235,6 +235,26 @@ class LedgerOut(C.Structure):
                 ("final_lookup_unlike", C.POINTER(C.c_uint8)), ("summary", LedgerSummary)]
 
 
+# tbc_ledger_realtime: realtime bounds on the posted counters of the ledger's reads (include/tbcheck.h)
+LEDGER_RT_STALE, LEDGER_RT_FUTURE, LEDGER_RT_REGRESSED = 0, 1, 2
+
+
+class LedgerRtIn(C.Structure):
+    _fields_ = [("ledger", LedgerIn), ("process", C.POINTER(C.c_int32)), ("init_credits", C.POINTER(C.c_int64)),
+                ("init_debits", C.POINTER(C.c_int64)), ("ok_transfers_apply", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+class LedgerRtSummary(C.Structure):
+    _fields_ = [("read_count", C.c_uint32), ("error_count", C.c_uint32), ("first_error", C.c_uint32), ("valid", C.c_uint32),
+                ("errors", LedgerErrors * 3), ("n_definite", C.c_uint32), ("n_possible", C.c_uint32), ("foreign_sides", C.c_uint32),
+                ("bad_amounts", C.c_uint32), ("n_checked", C.c_uint64), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64)]
+
+
+class LedgerRtOut(C.Structure):
+    _fields_ = [("rt_bits", C.POINTER(C.c_uint8)), ("rt_miss", C.POINTER(C.c_int64)), ("mop_lo", C.POINTER(C.c_int64)),
+                ("mop_hi", C.POINTER(C.c_int64)), ("mop_floor", C.POINTER(C.c_int64)), ("summary", LedgerRtSummary)]
+
+
 # tbc_perf_series: the series behind the reference's perf plots from op columns (include/tbcheck.h TBC_PERF_*)
 PERF_T_INVOKE, PERF_T_OK, PERF_T_FAIL, PERF_T_INFO = 0, 1, 2, 3
 PERF_O_NONE = 0
@@ -336,6 +356,7 @@ SYMBOLS = {
     "tbc_setfull_keys_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "tbc_setfull_keys_encoding": (C.c_int, [C.c_void_p, C.POINTER(SetFullEncoding)]),
     "tbc_ledger_check": (C.c_int, [C.POINTER(LedgerIn), C.POINTER(LedgerOut)]),
+    "tbc_ledger_realtime": (C.c_int, [C.POINTER(LedgerRtIn), C.POINTER(LedgerRtOut)]),
     "tbc_perf_plan_sizes": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfSizes)]),
     "tbc_perf_series": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfOut)]),
     "tbc_batch_destroy": (None, [C.c_void_p]),

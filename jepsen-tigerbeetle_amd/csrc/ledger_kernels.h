@@ -29,28 +29,12 @@
 #pragma once
 #include "wave_env_wg.h"
 #include "ledger_plan.h"
+#include "ledger_search.h"
 
 namespace {
 
 using lg::LgArgs;
 using lg::LgRows;
-
-// signed order as unsigned order
-__device__ __forceinline__ unsigned long long lg_key(long long v) { return (unsigned long long)v ^ 0x8000000000000000ull; }
-
-// the last row whose running sum is <= g (rows of no micro-ops share their successor's and are never picked)
-template <class T>
-__device__ __forceinline__ uint32_t lg_row_of(const T* __restrict__ cum, uint32_t n, unsigned long long g) {
-  uint32_t lo = 0, hi = n;
-  while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (cum[mid] <= g) lo = mid; else hi = mid; }
-  return lo;
-}
-
-__device__ __forceinline__ bool lg_is_account(const long long* __restrict__ acct, uint32_t n, long long id) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (acct[mid] < id) lo = mid + 1u; else hi = mid; }
-  return lo < n && acct[lo] == id;
-}
 
 __global__ __launch_bounds__(256) void lg_si_kernel(LgArgs A) {
   __shared__ long long s_acct[lg::kLgAcctLds];

@@ -1,5 +1,5 @@
-// oneshot_call.h -- what the one-shot entry points that take op columns (tbc_ledger_check, tbc_perf_series) share on the host: the HIP
-// error macro, the device check, and what one call makes on the device, released on every path out.
+// oneshot_call.h -- what the one-shot entry points that take op columns (tbc_ledger_check, tbc_ledger_realtime, tbc_perf_series) share
+// on the host: the HIP error macro, the device check, and what one call makes on the device, released on every path out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -42,6 +42,7 @@
 #include "wave_env_wg.h"
 #include "perf_plan.h"
 #include "radix_select.h"
+#include "wg_scan.h"
 
 namespace {
 
@@ -135,18 +136,7 @@ __global__ __launch_bounds__(64) void pf_open_totals_kernel(PfArgs A) {
 
 // exclusive prefix sums over the workgroup's 256 threads (s: 256 words of LDS); `total`: the sum of all
 __device__ __forceinline__ uint32_t pf_wg_scan(uint32_t v, uint32_t* s, uint32_t t, uint32_t& total) {
-  s[t] = v;
-  wv::wg_barrier();
-  for (uint32_t d = 1; d < 256u; d <<= 1) {
-    const uint32_t o = t >= d ? s[t - d] : 0u;
-    wv::wg_barrier();
-    s[t] += o;
-    wv::wg_barrier();
-  }
-  const uint32_t incl = s[t];
-  total = s[255];
-  wv::wg_barrier();                                                         // (s is written again only when everybody has read it)
-  return incl - v;
+  return wg_scan_excl(v, s, t, 0u, total, [](uint32_t a, uint32_t b) { return a + b; });
 }
 
 __global__ __launch_bounds__(256) void pf_open_carry_kernel(PfArgs A) {

@@ -11,6 +11,40 @@ Two statements of the same checkers:
 `test()` gives the workload's map with the composed checker; with `device_route=True` its SI, lookup-transfers and final-reads members
 answer from ONE `check_columns` call.  :plot is not built.
 
+Realtime bounds (`realtime_host` the specification, `realtime_numpy` the same in O(n log n), `RealtimeBounds` the checker,
+`check_realtime_native` / `realtime_result_map` the device route over tbc_ledger_realtime; `test(realtime=True)` composes the member
+"realtime").  Not in the reference: its :SI passes a read that is consistent but stale, one that shows a transfer nobody has invoked
+yet, and two reads that go backwards in time.  credits-posted and debits-posted of an account only grow, so real time bounds every
+counter a read returns -- a NECESSARY condition for strict serializability ("Ledger, Assumed Strict Serializable", the reference's
+doc/LASS.md: its "compare w r" and "compare r r'" rules).  THE RULES, stated once here:
+
+  Positions are indexes into the history.  Only client ops count (knossos.history.client_op); pairing is knossos.history.pair_index.
+  A TRANSFER is a client invocation whose op_txn_f is "t": its micro-ops are the invocation's; inv(T) its index; its status the type
+    of its completion (ok / fail / info, any other type reads as info), open if it has none; ret(T) the completion's index.  A transfer
+    completion without an invocation is ignored.
+  A READ is an :ok completion whose op_txn_f is "r" (the rows LedgerColumns.read_ops numbers): ret(R) its index, inv(R) its
+    invocation's index, -1 if it has none (such a read gets no lower bound beyond the initial value).  Its micro-ops are the columns'
+    ones: after ledger->bank's last-wins, nil maps flagged.  A micro-op that is nil, or whose id is no account, is NOT CHECKED (:SI
+    reports those).
+  BOUNDS of a checked micro-op of account a, per field x -- credits-posted: the transfer micro-ops with credit-acct = a;
+    debits-posted: those with debit-acct = a; a self-transfer counts on both:
+      lo    = init_x[a] + the amounts of the micro-ops of transfers with status ok and ret(T) < inv(R); 0 of them when the option
+              "ok-transfers-apply?" is false (default true: what the Bank model assumes)
+      hi    = init_x[a] + the amounts of the micro-ops of transfers with status /= fail and inv(T) < ret(R)
+      floor = the greatest value of field x of account a over the reads R' with ret(R') < inv(R) that checked a; INT64_MIN if none
+    A transfer micro-op that is nil, or a side of one that names no account, is skipped (the summary counts such sides, over the
+    transfers that did not fail: `foreign_sides`, a nil micro-op counting as two).
+  VIOLATIONS have a miss m > 0: stale m = lo - v, future m = v - hi, regressed m = floor - v.  A read's BITS: 1 stale credits,
+    2 stale debits, 4 future credits, 8 future debits, 16 regressed credits, 32 regressed debits.  Its MISS per kind is the greatest
+    over its micro-ops and both fields, 0 if none; misses saturate at INT64_MAX.
+  SUMMARY: per kind count, first, last, worst as read numbers (worst: the greatest miss; ties go to the earliest read, as in
+    tbc_ledger_errors); error_count = the reads with any bit, first_error the first of them, valid = none; n_definite = the
+    transfers with status ok, n_possible = those that did not fail; n_checked = the read micro-ops checked.
+  RANGES, so that no sum can wrap: every amount of a transfer that did not fail in [0, 2^31); fewer than 2^31 transfer micro-ops;
+    |init| < 2^61.  ValueError here; tbc_ledger_realtime counts offending amounts on the device and answers TBC_ERR_UNSUPPORTED.
+  OPTIONS: "accounts"; "initial" {account: {"credits-posted": c, "debits-posted": d}}, 0 where an account is not named (the test
+    generators fund accounts with credits: they need it); "ok-transfers-apply?".
+
 History ops are the dicts `edn.read_history` gives: "type" "f" "value" "process" "index" "time" "final?", keywords as strings; a
 :value is a vector of micro-ops [f id m] with f in "t" "r" "l-t".
 
@@ -263,13 +297,15 @@ class LedgerColumns:
     micro-op, so its kind is OTHER.  Only the ops a checker looks at -- :ok reads, invoked transfers, :ok lookups -- have their
     micro-ops copied; the others keep their kind and no micro-ops.
 
-    ValueError: an id, an account, an amount or a posted sum that is not an int in int64 range (nil included); a micro-op map with other
+    `process` is the ops' :process (realtime pairs by it).
+
+    ValueError: a :process outside int32 range; an id, an account, an amount or a posted sum that is not an int in int64 range (nil included); a micro-op map with other
     keys than the ones the columns hold; a :final? read that names an id twice (its raw vector and its map differ); a read whose
     sum of |credits| + |debits|, plus |total_amount|, reaches 2^63 (no device sum can wrap below that)."""
 
     def __init__(self, history, total_amount=0):
         total_amount = _i64(total_amount, "total-amount", -1)
-        pos, type_, kind, flags, mop_n = [], [], [], [], []
+        pos, type_, kind, flags, mop_n, proc = [], [], [], [], [], []
         ids, a_, b_, c_, mf = [], [], [], [], []
         chunks, n_mops = [], 0                      # the micro-ops so far as (id, a, b, c, flags) arrays; `ids` ... `mf` hold the tail
 
@@ -324,10 +360,14 @@ class LedgerColumns:
                     a_.append(_i64(m["debit-acct"], "debit-acct", i)); b_.append(_i64(m["credit-acct"], "credit-acct", i))
                     c_.append(_i64(m["amount"], "amount", i)); mf.append(0)
             pos.append(i); type_.append(t); kind.append(k); flags.append(N.LEDGER_F_FINAL if final else 0); mop_n.append(n_mops + len(ids) - n0)
+            proc.append(op["process"])
         flush()
         self.total_amount = total_amount
         self.index = np.array(pos, np.uint32)
         self.type, self.kind, self.flags = np.array(type_, np.uint8), np.array(kind, np.uint8), np.array(flags, np.uint8)
+        if any(not -(2 ** 31) <= p < 2 ** 31 for p in proc):
+            raise ValueError("a :process is not an int in int32 range")
+        self.process = np.array(proc, np.int32).reshape(-1)     # (pairing is by process: realtime)
         self.mop_off = np.concatenate([[0], np.cumsum(np.array(mop_n, np.int64))]).astype(np.uint64)
         cat = lambda j, dt: np.ascontiguousarray(np.concatenate([c[j] for c in chunks])) if chunks else np.zeros(0, dt)
         self.mop_id, self.mop_a, self.mop_b, self.mop_c = (cat(j, np.int64) for j in range(4))
@@ -483,9 +523,381 @@ class _Linear(jc.Checker):
         return self.inner.check(test, bank, opts)
 
 
-def test(opts=None, linear=False, device_route=True):
+# ---------------------------------------------------------------- realtime bounds on posted counters
+
+RT_KINDS = ("stale", "future", "regressed")
+RT_FIELDS = ("credits-posted", "debits-posted")
+_I64_MIN, _I64_MAX = -(2 ** 63), 2 ** 63 - 1
+
+
+def _rt_opts(test, opts):
+    """(accounts, {account: (init credits, init debits)}, ok-transfers-apply?) of a test map and the checker's options"""
+    t = dict(opts or {})
+    t.update({k: v for k, v in (test or {}).items() if k in ("accounts", "initial")})
+    accounts = list(t.get("accounts") or range(1, 9))
+    initial = t.get("initial") or {}
+    init = {a: (initial.get(a, {}).get("credits-posted", 0), initial.get(a, {}).get("debits-posted", 0)) for a in accounts}
+    apply_ok = (opts or {}).get("ok-transfers-apply?", True)
+    return accounts, init, bool(True if apply_ok is None else apply_ok)
+
+
+def _sat(x):
+    return max(_I64_MIN, min(_I64_MAX, x))
+
+
+def _read_mops(op):
+    """the micro-ops of an :ok read as the columns hold them: (id, credits-posted, debits-posted, nil?), after ledger->bank's last-wins"""
+    row = {}
+    for _r, ident, m in op["value"]:
+        row[ident] = (0, 0, True) if m is None else (m["credits-posted"], m["debits-posted"], False)
+    return [(ident,) + v for ident, v in row.items()]
+
+
+def _rt_model(history):
+    """(transfers, reads) of a history.  A transfer: {"inv", "ret", "status", "mops": [(debit-acct, credit-acct, amount) | None]};
+    a read: {"inv", "ret", "mops": [(id, credits, debits, nil?)]}."""
+    pairs = H.pair_index(history)
+    transfers, reads = [], []
+    for i, op in enumerate(history):
+        if not H.client_op(op):
+            continue
+        f = op_txn_f(op)
+        if f == "t" and op["type"] == "invoke":
+            j = pairs.get(i)
+            status = "open" if j is None else (history[j]["type"] if history[j]["type"] in ("ok", "fail") else "info")
+            mops = [None if m[2] is None else (m[2]["debit-acct"], m[2]["credit-acct"], m[2]["amount"]) for m in op["value"]]
+            transfers.append({"inv": i, "ret": j, "status": status, "mops": mops})
+        elif f == "r" and op["type"] == "ok":
+            j = pairs.get(i)
+            reads.append({"inv": -1 if j is None else j, "ret": i, "mops": _read_mops(op)})
+    return transfers, reads
+
+
+def _rt_ranges(amounts, n_transfer_mops, init):
+    """the ranges under which no 64-bit sum can wrap (the module docstring's Ranges)"""
+    for amount in amounts:
+        if not 0 <= amount < 2 ** 31:
+            raise ValueError(f"realtime: a transfer amount {amount!r} is not in [0, 2^31)")
+    if n_transfer_mops >= 2 ** 31:
+        raise ValueError("realtime: 2^31 or more transfer micro-ops")
+    for a, cd in init.items():
+        for x in cd:
+            if not isinstance(x, (int, np.integer)) or isinstance(x, (bool, np.bool_)) or not abs(x) < 2 ** 61:
+                raise ValueError(f"realtime: initial value {x!r} of account {a!r} is not an int with |x| < 2^61")
+
+
+def _rt_bounds_of(transfers, reads, accts, init, apply_ok, r):
+    """Read r, micro-op by micro-op: None where it is not checked, else [(lo, hi, floor) of credits-posted, ... of debits-posted] --
+    the three bounds exactly as the module docstring quantifies them."""
+    R = reads[r]
+    out = []
+    for ident, cr, db, nil in R["mops"]:
+        if nil or ident not in accts:
+            out.append(None)
+            continue
+        per_field = []
+        for x in (0, 1):                                      # credits-posted: the transfer's credit-acct; debits-posted: its debit-acct
+            side = 1 if x == 0 else 0
+            lo = hi = init[ident][x]
+            for T in transfers:
+                amount = sum(m[2] for m in T["mops"] if m is not None and m[side] == ident)
+                if apply_ok and T["status"] == "ok" and T["ret"] < R["inv"]:
+                    lo += amount
+                if T["status"] != "fail" and T["inv"] < R["ret"]:
+                    hi += amount
+            floor = _I64_MIN
+            for Q in reads:
+                if Q["ret"] < R["inv"]:
+                    for ident2, cr2, db2, nil2 in Q["mops"]:
+                        if ident2 == ident and not nil2:
+                            floor = max(floor, (cr2, db2)[x])
+            per_field.append((lo, hi, floor))
+        out.append(per_field)
+    return out
+
+
+def _rt_violations(R, bounds):
+    """the violations of one read in the order the result map names them, as (micro-op, field, kind, miss, bound)"""
+    out = []
+    for j, (mop, b) in enumerate(zip(R["mops"], bounds)):
+        if b is None:
+            continue
+        for x in (0, 1):
+            v, (lo, hi, floor) = mop[1 + x], b[x]
+            for k, (miss, bound) in enumerate(((lo - v, lo), (v - hi, hi), (floor - v, floor))):
+                if miss > 0:
+                    out.append((j, x, k, _sat(miss), bound))
+    return out
+
+
+def _rt_summary(bits, miss, foreign_sides, n_definite, n_possible, n_checked):
+    """the summary of tbc_ledger_rt_summary (without ns_device and bytes_in) from the per-read arrays"""
+    s = {"read_count": len(bits), "error_count": int(np.count_nonzero(bits)), "first_error": N.NO_OP, "valid": int(not bits.any()),
+         "n_definite": n_definite, "n_possible": n_possible, "foreign_sides": foreign_sides, "bad_amounts": 0, "n_checked": n_checked, "errors": {}}
+    if bits.any():
+        s["first_error"] = int(np.flatnonzero(bits)[0])
+    for k, kind in enumerate(RT_KINDS):
+        has = np.flatnonzero(bits & (3 << (2 * k)))
+        e = {"count": len(has), "first": N.NO_OP, "last": N.NO_OP, "worst": N.NO_OP}
+        if len(has):
+            e.update({"first": int(has[0]), "last": int(has[-1]), "worst": int(has[np.argmax(miss[has, k])])})      # (argmax: the earliest of equals)
+        s["errors"][kind] = e
+    return s
+
+
+def realtime_host(history, opts=None):
+    """The specification of the realtime bounds (module docstring), quantifier by quantifier; quadratic.  Per :ok read (LedgerColumns'
+    read_ops numbering) "bits" and "miss" [stale, future, regressed]; per read micro-op "lo" "hi" "floor" [credits, debits], INT64_MIN where
+    it is not checked; and the "summary" tbc_ledger_realtime gives."""
+    accounts, init, apply_ok = _rt_opts(None, opts)
+    accts = set(accounts)
+    transfers, reads = _rt_model(history)
+    counted = [T for T in transfers if T["status"] != "fail"]
+    _rt_ranges([m[2] for T in counted for m in T["mops"] if m is not None], sum(len(T["mops"]) for T in counted), init)
+    n_mops = sum(len(R["mops"]) for R in reads)
+    bits, miss = np.zeros(len(reads), np.uint8), np.zeros((len(reads), 3), np.int64)
+    lo, hi, floor = (np.full((n_mops, 2), _I64_MIN, np.int64) for _ in range(3))
+    at = n_checked = 0
+    for r, R in enumerate(reads):
+        bounds = _rt_bounds_of(transfers, reads, accts, init, apply_ok, r)
+        for j, b in enumerate(bounds):
+            if b is not None:
+                n_checked += 1
+                for x in (0, 1):
+                    lo[at + j, x], hi[at + j, x], floor[at + j, x] = b[x]
+        for _j, x, k, m, _bound in _rt_violations(R, bounds):
+            bits[r] |= 1 << (2 * k + x)
+            miss[r, k] = max(miss[r, k], m)
+        at += len(R["mops"])
+    foreign = sum(2 if m is None else (m[0] not in accts) + (m[1] not in accts) for T in counted for m in T["mops"])
+    return {"bits": bits, "miss": miss, "lo": lo, "hi": hi, "floor": floor,
+            "summary": _rt_summary(bits, miss, foreign, sum(T["status"] == "ok" for T in transfers), len(counted), n_checked)}
+
+
+def _rt_init_arrays(accounts, init):
+    try:
+        acct = np.array(list(accounts), np.int64).reshape(-1)
+    except (OverflowError, TypeError, ValueError):
+        raise ValueError("an account is not an int in int64 range") from None
+    return acct, np.array([init[a][0] for a in accounts], np.int64).reshape(-1), np.array([init[a][1] for a in accounts], np.int64).reshape(-1)
+
+
+def _expand(lo, n):
+    """the micro-op numbers lo[k] .. lo[k] + n[k] - 1 of every row k in turn, and each one's row"""
+    row = np.repeat(np.arange(len(n)), n)
+    start = np.cumsum(n) - n
+    return (lo[row] + (np.arange(len(row)) - start[row])).astype(np.int64), row
+
+
+def _sat_sub(a, b):
+    """a - b on int64 arrays, saturating"""
+    with np.errstate(over="ignore"):
+        d = a - b
+    over = ((a < 0) != (b < 0)) & ((d < 0) != (a < 0))
+    return np.where(over, np.where(a < 0, _I64_MIN, _I64_MAX), d)
+
+
+def realtime_numpy_columns(cols, accounts, init, apply_ok=True):
+    """realtime_host's arrays from a LedgerColumns in O(n log n): a stable sort by (account, position), cumsum / maximum.accumulate along it,
+    and searchsorted for every read micro-op.  The reference at sizes the quadratic statement cannot reach."""
+    T_INV, T_OK, T_FAIL = N.LEDGER_T_INVOKE, N.LEDGER_T_OK, N.LEDGER_T_FAIL
+    _rt_ranges([], 0, init)
+    acct, init_c, init_d = _rt_init_arrays(accounts, init)
+    n = len(cols)
+    index, typ, kind = cols.index.astype(np.int64), cols.type, cols.kind
+    off = cols.mop_off.astype(np.int64)
+    # pairing (knossos.history.pair_index): along one process an invocation is completed by the very next op when that is a completion
+    order = np.argsort(cols.process, kind="stable")
+    p, t = cols.process[order], typ[order]
+    match = (p[1:] == p[:-1]) & (t[:-1] == T_INV) & (t[1:] != T_INV) if n > 1 else np.zeros(0, bool)
+    partner = np.full(n, -1, np.int64)
+    partner[order[1:][match]] = order[:-1][match]
+    partner[order[:-1][match]] = order[1:][match]
+    tr = np.flatnonzero((typ == T_INV) & (kind == N.LEDGER_K_TRANSFER))
+    status = np.where(partner[tr] >= 0, typ[partner[tr]], T_INV)                 # (T_INV: open)
+    ret = np.where(partner[tr] >= 0, index[partner[tr]], -1)
+    poss = tr[status != T_FAIL]
+    keep = status == T_OK
+    defi, defi_pos = tr[keep][np.argsort(ret[keep], kind="stable")], np.sort(ret[keep])
+    sort_acct = np.sort(acct)
+    perm = np.argsort(acct, kind="stable")
+    init_x = (init_c[perm], init_d[perm])
+    A = len(acct)
+
+    def number(ids):
+        k = np.searchsorted(sort_acct, ids)
+        k[k == A] = 0
+        return np.where(sort_acct[k] == ids, k, -1) if A else np.full(len(ids), -1, np.int64)
+
+    def entries(rows, pos):
+        """per field x (credits, debits) the entries (account number, position, amount) of the transfers `rows`, sorted by (account, position)"""
+        m, row = _expand(off[rows], off[rows + 1] - off[rows])
+        nil = (cols.mop_flags[m] & N.LEDGER_M_NIL) != 0
+        out, foreign = [], 0
+        for ids in (cols.mop_b[m], cols.mop_a[m]):
+            a = np.where(nil, -1, number(ids))
+            ok = a >= 0
+            foreign += int(np.count_nonzero(~ok))
+            comp = a[ok] * (1 << 32) + pos[row][ok]
+            o = np.argsort(comp, kind="stable")
+            out.append((comp[o], np.concatenate([[0], np.cumsum(cols.mop_c[m][ok][o])])))
+        return out, foreign, m[~nil]
+
+    def prefix(lists, x, a, position):
+        comp, cs = lists[x]
+        return cs[np.searchsorted(comp, a * (1 << 32) + position, "left")] - cs[np.searchsorted(comp, a * (1 << 32), "left")]
+
+    poss_lists, foreign, poss_m = entries(poss, index[poss])
+    _rt_ranges(cols.mop_c[poss_m][(cols.mop_c[poss_m] < 0) | (cols.mop_c[poss_m] >= 2 ** 31)][:1].tolist(), int((off[poss + 1] - off[poss]).sum()), {})
+    defi_lists, _, _ = entries(defi, defi_pos)
+    # the reads
+    rd = np.flatnonzero((typ == T_OK) & (kind == N.LEDGER_K_READ))
+    r_ret, r_inv = index[rd], np.where(partner[rd] >= 0, index[np.maximum(partner[rd], 0)], -1)
+    m, row = _expand(off[rd], off[rd + 1] - off[rd])
+    a = np.where((cols.mop_flags[m] & N.LEDGER_M_NIL) != 0, -1, number(cols.mop_id[m]))
+    chk = a >= 0
+    ac, inv, rt = a[chk], r_inv[row][chk], r_ret[row][chk]
+    lo, hi, floor = (np.full((len(m), 2), _I64_MIN, np.int64) for _ in range(3))
+    bits, miss = np.zeros(len(rd), np.uint8), np.zeros((len(rd), 3), np.int64)
+    comp = ac * (1 << 32) + rt
+    o = np.argsort(comp, kind="stable")
+    comp_s = comp[o]
+    for x, vals in enumerate((cols.mop_a[m][chk], cols.mop_b[m][chk])):
+        lo_x = init_x[x][ac] + (prefix(defi_lists, x, ac, np.maximum(inv, 0)) if apply_ok else 0)
+        hi_x = init_x[x][ac] + prefix(poss_lists, x, ac, rt)
+        # running maximum per account: values as ranks, an account's ranks above every earlier account's
+        fl_x = np.full(len(ac), _I64_MIN, np.int64)
+        if len(ac):
+            sorted_vals = np.sort(vals)
+            rank = np.searchsorted(sorted_vals, vals[o], "left")
+            run = np.maximum.accumulate(ac[o] * len(ac) + rank) - ac[o] * len(ac)
+            k, k0 = np.searchsorted(comp_s, ac * (1 << 32) + np.maximum(inv, 0), "left"), np.searchsorted(comp_s, ac * (1 << 32), "left")
+            fl_x = np.where(k > k0, sorted_vals[run[np.maximum(k, 1) - 1]], _I64_MIN)
+        lo[chk, x], hi[chk, x], floor[chk, x] = lo_x, hi_x, fl_x
+        for k, ms in enumerate((_sat_sub(lo_x, vals), _sat_sub(vals, hi_x), _sat_sub(fl_x, vals))):
+            bad = ms > 0
+            np.bitwise_or.at(bits, row[chk][bad], np.uint8(1 << (2 * k + x)))
+            np.maximum.at(miss[:, k], row[chk][bad], ms[bad])
+    return {"bits": bits, "miss": miss, "lo": lo, "hi": hi, "floor": floor,
+            "summary": _rt_summary(bits, miss, foreign, len(defi), len(poss), int(np.count_nonzero(chk)))}
+
+
+def realtime_numpy(history, opts=None):
+    """realtime_host(history, opts), in O(n log n) (realtime_numpy_columns over the history's LedgerColumns)."""
+    accounts, init, apply_ok = _rt_opts(None, opts)
+    return realtime_numpy_columns(LedgerColumns(history), accounts, init, apply_ok)
+
+
+def _rt_named(hist, model, accts, init, apply_ok, r):
+    """{"op", "violations"} of read r"""
+    transfers, reads = model
+    R = reads[r]
+    vs = _rt_violations(R, _rt_bounds_of(transfers, reads, accts, init, apply_ok, r))
+    return {"op": hist[R["ret"]], "violations": [{"type": RT_KINDS[k], "account": R["mops"][j][0], "field": RT_FIELDS[x], "value": R["mops"][j][1 + x], "bound": b}
+                                                for j, x, k, _m, b in vs]}
+
+
+def _rt_map(history, summary, accounts, init, apply_ok):
+    """the realtime result map from a summary (the host statement's or the device's): the named reads recomputed from the history"""
+    if not summary["error_count"]:                      # (no read to name: no pass over the history)
+        return {"valid?": True, "read-count": summary["read_count"], "error-count": 0, "first-error": None, "errors": {}}
+    hist = _indexed(history) if any("index" not in op for op in history) else history
+    model, accts = _rt_model(history), set(accounts)
+    named = lambda r: _rt_named(hist, model, accts, init, apply_ok, r)
+    errors = {kind: {"count": e["count"], "first": named(e["first"]), "worst": named(e["worst"]), "last": named(e["last"])}
+              for kind, e in summary["errors"].items() if e["count"]}
+    return {"valid?": bool(summary["valid"]), "read-count": summary["read_count"], "error-count": summary["error_count"],
+            "first-error": named(summary["first_error"]) if summary["error_count"] else None, "errors": errors}
+
+
+class RealtimeBounds(jc.Checker):
+    """realtime: every counter an :ok read returns lies within what real time allows (module docstring) -- a necessary condition for
+    strict serializability.  opts: "accounts", "initial" {account: {"credits-posted": c, "debits-posted": d}}, "ok-transfers-apply?"."""
+
+    def __init__(self, opts=None):
+        self.opts = dict(opts or {})
+
+    def check(self, test, history, opts=None):
+        accounts, init, apply_ok = _rt_opts(test, self.opts)
+        o = dict(self.opts, accounts=accounts, initial={a: dict(zip(RT_FIELDS, cd)) for a, cd in init.items()})
+        return _rt_map(history, realtime_host(history, o)["summary"], accounts, init, apply_ok)
+
+
+def ledger_rt_in(cols, accounts, init, apply_ok=True, device=0):
+    """A tbc_ledger_rt_in over a LedgerColumns (and the arrays it points into).  ValueError: the Ranges of the module docstring that the
+    columns show -- an amount of a transfer that did not fail outside [0, 2^31), 2^31 transfer micro-ops, an initial value of 2^61."""
+    T = (cols.type == N.LEDGER_T_INVOKE) & (cols.kind == N.LEDGER_K_TRANSFER)
+    _rt_ranges([], int((cols.mop_off[1:][T].astype(np.int64) - cols.mop_off[:-1][T].astype(np.int64)).sum()), init)
+    s, keep = ledger_in(cols, accounts, False, device)
+    pad = lambda a: a if len(a) else np.zeros(1, a.dtype)
+    _acct, init_c, init_d = _rt_init_arrays(accounts, init)
+    keep.update({"process": pad(np.ascontiguousarray(cols.process)), "init_c": pad(init_c), "init_d": pad(init_d)})
+    r = N.LedgerRtIn()
+    r.ledger = s
+    r.process = _ptr(keep["process"], C.c_int32)
+    r.init_credits, r.init_debits = _ptr(keep["init_c"], C.c_int64), _ptr(keep["init_d"], C.c_int64)
+    r.ok_transfers_apply = int(bool(apply_ok))
+    return r, keep
+
+
+def rt_summary_dict(s):
+    d = {f: int(getattr(s, f)) for f, _ in N.LedgerRtSummary._fields_ if f != "errors"}
+    d["errors"] = {RT_KINDS[k]: {f: int(getattr(s.errors[k], f)) for f in ("count", "first", "last", "worst")} for k in range(3)}
+    return d
+
+
+def check_realtime_native(cols, accounts, init, apply_ok=True, device=0, call=None):
+    """tbc_ledger_realtime over the columns -> realtime_host's arrays and the summary (with ns_device and bytes_in).  call(in, out): another
+    implementation of the entry point (the tests' emulator build of the same kernels).  An amount out of range is the device's to find
+    (TBC_ERR_UNSUPPORTED): ValueError here too."""
+    s, keep = ledger_rt_in(cols, accounts, init, apply_ok, device)
+    R = len(cols.read_ops)
+    rd = (cols.type == N.LEDGER_T_OK) & (cols.kind == N.LEDGER_K_READ)
+    M = int((cols.mop_off[1:][rd].astype(np.int64) - cols.mop_off[:-1][rd].astype(np.int64)).sum())
+    arr = {"rt_bits": np.zeros(max(1, R), np.uint8), "rt_miss": np.zeros((max(1, R), 3), np.int64)}
+    arr.update({f: np.zeros((max(1, M), 2), np.int64) for f in ("mop_lo", "mop_hi", "mop_floor")})
+    out = N.LedgerRtOut()
+    out.rt_bits = _ptr(arr["rt_bits"], C.c_uint8)
+    for f in ("rt_miss", "mop_lo", "mop_hi", "mop_floor"):
+        setattr(out, f, _ptr(arr[f], C.c_int64))
+    if call is None:
+        st = N.lib().tbc_ledger_realtime(C.byref(s), C.byref(out))
+        if st == N.ERR_UNSUPPORTED:
+            raise ValueError("realtime: " + N.lib().tbc_last_error().decode())
+        N.check_status(st)
+    else:
+        call(s, out)
+    del keep
+    return {"bits": arr["rt_bits"][:R], "miss": arr["rt_miss"][:R], "lo": arr["mop_lo"][:M], "hi": arr["mop_hi"][:M], "floor": arr["mop_floor"][:M],
+            "summary": rt_summary_dict(out.summary)}
+
+
+def realtime_result_map(history, cols, dev, accounts, init, apply_ok=True):
+    """RealtimeBounds' result map from tbc_ledger_realtime's summary; only the handful of reads it names are recomputed on the host (a
+    valid history: none, and no pass over it).  `cols` names the reads the summary numbers -- cols.read_ops, which _rt_model restates --
+    and is taken for the symmetry with result_maps; the map needs nothing else of it."""
+    assert dev["summary"]["read_count"] == len(cols.read_ops)
+    return _rt_map(history, dev["summary"], accounts, init, apply_ok)
+
+
+class _RealtimeDevice(jc.Checker):
+    """the realtime member on the device route: columns -> tbc_ledger_realtime -> RealtimeBounds' map.  No host route behind it."""
+
+    def __init__(self, opts):
+        self.opts = dict(opts or {})
+
+    def check(self, test, history, opts=None):
+        accounts, init, apply_ok = _rt_opts(test, self.opts)
+        cols = LedgerColumns(history)
+        dev = check_realtime_native(cols, accounts, init, apply_ok, device=(opts or {}).get("device", 0))
+        return realtime_result_map(history, cols, dev, accounts, init, apply_ok)
+
+
+def test(opts=None, linear=False, realtime=False, device_route=True):
     """The ledger test map (tests/ledger.clj:341-369) without generators: accounts, max-transfer, total-amount and the composed checker
-    -- SI, lookup-transfers, final-reads, unexpected-ops, and with linear=True the member clj/patches/ledger.patch adds.
+    -- SI, lookup-transfers, final-reads, unexpected-ops, with linear=True the member clj/patches/ledger.patch adds, and with
+    realtime=True the member "realtime" (RealtimeBounds; opts "initial", "ok-transfers-apply?"), on the device or as the host statement
+    according to device_route.
     device_route=True (the default: the whole call measured 1.7-1.8 s against the host statement's 6.6-6.7 s on a ledger of 64 workers and 50k
     transfers, profiles/NOTES_ledger.md) answers the first three from one check_columns call; False runs the host statement."""
     opts = dict(opts if opts is not None else {"negative-balances?": False})
@@ -498,6 +910,8 @@ def test(opts=None, linear=False, device_route=True):
     else:
         members = {"SI": BankChecker(opts), "lookup-transfers": LookupAllInvokedTransfers(), "final-reads": FinalReads()}
     members["unexpected-ops"] = UnexpectedOps()
+    if realtime:
+        members["realtime"] = _RealtimeDevice(opts) if device_route else RealtimeBounds(opts)
     if linear:
         members["linear"] = _Linear(opts["accounts"], bool(opts.get("negative-balances?", False)))
     return dict(opts, checker=jc.compose(members))
