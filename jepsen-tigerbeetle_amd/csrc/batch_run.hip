@@ -497,6 +497,18 @@ tbc_status queue_pack(RunState& R) {
   return TBC_OK;
 }
 
+// Zero the words of the growth pool that the searches since its last zeroing were handed: [0, min(*cursor, pool_words)) -- nothing at
+// all in a pass whose visited sets did not grow (pool_plan.h).  Launched in front of the memset that puts the cursor back to zero.
+constexpr uint32_t kPoolZeroBlocks = 1024, kPoolZeroThreads = 256;
+__global__ __launch_bounds__(kPoolZeroThreads) void pool_zero_written_kernel(uint64_t* __restrict__ pool, const unsigned long long* __restrict__ cursor, uint64_t pool_words) {
+  const uint64_t n = pool_written(*cursor, pool_words);
+  const uint64_t stride = (uint64_t)gridDim.x * kPoolZeroThreads * 2u;
+  for (uint64_t i = ((uint64_t)blockIdx.x * kPoolZeroThreads + threadIdx.x) * 2u; i < n; i += stride) {      // 16 B a thread (the pool starts on a 256 B boundary)
+    if (i + 1u < n) *reinterpret_cast<ulonglong2*>(pool + i) = make_ulonglong2(0ull, 0ull);
+    else pool[i] = 0ull;
+  }
+}
+
 // memsets, pack, the search (or the sweep) launched, the relaxed sweep beside a count-form search, everything read back
 tbc_status first_pass(RunState& R) {
   tbc_batch* B = R.B; hipStream_t s = R.s; const uint32_t nh = R.nh; const bool beam = R.beam; const int phase = R.phase;
@@ -522,7 +534,16 @@ tbc_status first_pass(RunState& R) {
     // (a sweep batch has no visited sets and no growth pool of its own -- one-element stand-ins nobody reads: what the sweep hands
     // to the depth-first search runs in scratch arenas, scratch_pass)
     if (!B->sweep && (!use_epoch || B->epoch == 1u)) HIP_TRY(hipMemsetAsync(B->d_btab.p, 0, B->d_btab.bytes(), s));
-    if (!B->sweep) HIP_TRY(hipMemsetAsync(B->d_pool.p, 0, B->d_pool.bytes(), s));
+    // the growth pool: all of it where its memory is new or the visited sets start over, else the words the searches since the last
+    // zeroing were handed -- found on the device, from the cursor the memsets around this line put back to zero (pool_plan.h)
+    if (!B->sweep) {
+      const bool whole = pool_zero_whole(B->pool_state, use_epoch, B->epoch);
+      if (whole || zero_block) HIP_TRY(hipMemsetAsync(B->d_pool.p, 0, B->d_pool.bytes(), s));      // (zero_block: the cursor is zero already)
+      else {
+        hipLaunchKernelGGL(pool_zero_written_kernel, dim3(kPoolZeroBlocks), dim3(kPoolZeroThreads), 0, s, B->d_pool.p, B->d_pool_cursor.p, (uint64_t)B->d_pool.n);
+        HIP_TRY(hipGetLastError());
+      }
+    }
     if (!zero_block) {
       HIP_TRY(hipMemsetAsync(B->d_pool_cursor.p, 0, sizeof(unsigned long long), s));
       HIP_TRY(hipMemsetAsync(B->d_off.p, 0, B->d_off.bytes(), s));

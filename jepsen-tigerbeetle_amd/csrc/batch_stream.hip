@@ -191,7 +191,7 @@ tbc_status ensure_arenas(tbc_batch* B, const LayoutTotals& t) {
     B->epoch = 0;          // (a new visited-set arena: zeroed by the run before its first pass, as a batch's first arena is)
     // ... and the growth pool keeps its share of it (alloc_arenas' rule)
     const uint64_t words = std::min<uint64_t>(t.btab_n * B->tab_stride() * (B->lanes ? 1u : 3u) / 10, (32ull << 30) / 8);
-    if (words > B->d_pool.n && (s = B->d_pool.regrow(words))) return s;
+    if (words > B->d_pool.n) { B->pool_state.replaced(); if ((s = B->d_pool.regrow(words))) return s; }
   }
   (void)grew;
   return TBC_OK;

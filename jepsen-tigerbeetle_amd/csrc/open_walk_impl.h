@@ -32,6 +32,8 @@ namespace walk {
 constexpr uint32_t kCandCap = 136;          // 71 completions (ranks F_lo - 7 .. F_hi - 1) + one more call per slot (64 slots), rounded up
 constexpr uint32_t kCandWords = 8;          // inv_rank, ret_rank, opidx, f | slot << 8;  a, b, flags (below), effect key
 constexpr uint32_t kAuxWords = 80;          // the scan of the per-slot counts; later the rank codes of the chunk + 6
+constexpr uint32_t kKeyWords = 32, kKeyBits = 32 * kKeyWords;       // A2's map of the live candidates' keys and its prefix, over the same words
+static_assert(2 * kKeyWords <= kAuxWords && kKeyWords == 32, "the map and its prefix fit the scratch; two rows of 16 lanes scan it");
 WV_HD constexpr uint32_t walk_lds_words() { return kCandCap * kCandWords + kAuxWords; }
 
 // candidate word 6: what the loop does with the call, decided once when the table is filled
@@ -172,7 +174,16 @@ WV_DEV void walk_wave(const PackOpenArgs& A, uint32_t wid, uint32_t* lds, uint32
   // no list -- and what the loop does for an unlisted candidate (a bit of a read row, of the lookahead mask, the producer distance)
   // does not depend on when it meets it: they take keys above every live one, by table position.  The keys stay in registers, one
   // candidate per lane (three sets); candidate j's key reaches the lanes by a lane read (j is uniform), and every lane counts the
-  // smaller keys for each of its candidates: 1 + 2 vector instructions per set instead of a dozen with two LDS reads.
+  // smaller keys for each of its candidates: 1 + 2 vector instructions per set instead of a dozen with two LDS reads.  That is
+  // NC x 3 .. 5 instructions a chunk, and it is the fallback now:
+  //
+  // BY COUNTING.  A live candidate completes at ret_from or later (phase A's search), and all but a slot's last one before F_hi: the live
+  // keys sit in a window above ret_from's that is a few hundred wide unless a call stays open for hundreds of ranks.  Key - base is then a
+  // bit of a kKeyBits-bit map in LDS (the keys are unique: adding the bit is setting it), 32 lanes prefix the words' popcounts, and a
+  // place is the bits below the candidate's own; the crashed calls follow the live ones by table position (ballots).  list_order 2 is
+  // two windows of half the bits, the writes' after the others'.  A chunk with a live key outside its window -- decided per chunk, so
+  // this covers a race's per-history order_of and any W -- takes the compare loop; so does a list_order whose write offset alone
+  // exceeds the window.
   const uint32_t list_order = A.order_of ? A.order_of[h] : A.list_order;          // (the history's own order, if the batch says one)
   const bool by_ret = list_order != 0u;
   const uint32_t wr_last = list_order == 2u ? 0x40000000u : list_order >= 16u ? 2u * (list_order - 16u) + 1u : 0u;
@@ -180,15 +191,52 @@ WV_DEV void walk_wave(const PackOpenArgs& A, uint32_t wid, uint32_t* lds, uint32
   uint16_t* const perm = reinterpret_cast<uint16_t*>(aux);
   if (by_ret) {
     uint32_t my[3], place[3] = {0u, 0u, 0u};
+    uint32_t d[3];                                                  // key - base of a live candidate inside the window, else kInf
+    const uint32_t wr_ofs = list_order == 2u ? kKeyBits / 2u : wr_last, lim_other = list_order == 2u ? kKeyBits / 2u : kKeyBits;
+    bool outside = false;
     WV_UNROLL
     for (int s = 0; s < 3; s++) {
       const uint32_t idx = lane + 64u * (uint32_t)s;
       const uint32_t* e = cand + (idx < NC ? idx : 0u) * kCandWords;
       const uint32_t rt = e[1];
-      my[s] = idx >= NC ? 0xFFFFFFFFu : rt == kInf ? (0xFFFFFF00u | idx) : rt * rk_mul + ((e[3] & 0xFFu) == TBC_F_WRITE ? wr_last : 0u);
+      const bool wr = (e[3] & 0xFFu) == TBC_F_WRITE;
+      my[s] = idx >= NC ? 0xFFFFFFFFu : rt == kInf ? (0xFFFFFF00u | idx) : rt * rk_mul + (wr ? wr_last : 0u);
+      const bool live = idx < NC && rt != kInf;
+      const uint32_t x = rt - ret_from;                             // (a live call's: below 2^30)
+      const bool inside = x < kKeyBits && x * rk_mul + (wr ? wr_ofs : 0u) < (wr ? kKeyBits : lim_other);
+      d[s] = (live && inside) ? x * rk_mul + (wr ? wr_ofs : 0u) : kInf;
+      outside = outside || (live && !inside);
     }
     const uint32_t n0 = NC < 64u ? NC : 64u, n1 = NC <= 64u ? 0u : (NC < 128u ? NC - 64u : 64u), n2 = NC <= 128u ? 0u : NC - 128u;
-    if (NC <= 64u) {
+    if (wr_ofs < kKeyBits && wv::ballot(outside) == 0ull) {
+      if (lane < kKeyWords) aux[lane] = 0u;
+      wv::barrier();
+      WV_UNROLL
+      for (int s = 0; s < 3; s++) if (d[s] != kInf) wv::lds_add32(&aux[d[s] >> 5], 1u << (d[s] & 31u));
+      wv::barrier();
+      const uint32_t wc = lane < kKeyWords ? (uint32_t)__builtin_popcount(aux[lane]) : 0u;
+      uint32_t y = wc;                                              // inclusive scan over lanes 0 .. 31: two rows of 16
+      y += wv::row_shr0<1>(y); y += wv::row_shr0<2>(y); y += wv::row_shr0<4>(y); y += wv::row_shr0<8>(y);
+      const uint32_t row0 = wv::readlane(y, 15u);
+      y += lane >= 16u ? row0 : 0u;
+      const uint32_t n_live = wv::readlane(y, kKeyWords - 1u);
+      if (lane < kKeyWords) aux[kKeyWords + lane] = y - wc;
+      // the crashed candidates (in no list): after the live ones, by table position
+      const uint64_t below = (1ull << lane) - 1ull;
+      uint32_t cr_before = n_live;
+      WV_UNROLL
+      for (int s = 0; s < 3; s++) {
+        const uint32_t idx = lane + 64u * (uint32_t)s;
+        const uint64_t cr = wv::ballot(idx < NC && d[s] == kInf);
+        if (d[s] == kInf) place[s] = cr_before + (uint32_t)__builtin_popcountll(cr & below);
+        cr_before += (uint32_t)__builtin_popcountll(cr);
+      }
+      wv::barrier();
+      WV_UNROLL
+      for (int s = 0; s < 3; s++)
+        if (d[s] != kInf) place[s] = aux[kKeyWords + (d[s] >> 5)] + (uint32_t)__builtin_popcount(aux[d[s] >> 5] & ((1u << (d[s] & 31u)) - 1u));
+      wv::barrier();                                                // (the places go over the words of the map)
+    } else if (NC <= 64u) {
       for (uint32_t j = 0; j < n0; j++) place[0] += wv::readlane(my[0], j) < my[0] ? 1u : 0u;
     } else if (NC <= 128u) {
       for (uint32_t j = 0; j < n0; j++) { const uint32_t kj = wv::readlane(my[0], j); place[0] += kj < my[0] ? 1u : 0u; place[1] += kj < my[1] ? 1u : 0u; }

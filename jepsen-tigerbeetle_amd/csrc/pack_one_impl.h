@@ -45,11 +45,14 @@ namespace packone {
 // A geometry: wavefronts per workgroup, the history rows the LDS bitmap holds, process slots, and (COUNTS) completions
 // HBITS_: bits of a rank's entry in the histogram of the listed calls' invocation ranks (at most one call per process slot is invoked
 // between two completions: an entry holds MAXW_)
+WV_HD constexpr uint32_t slot_bits(uint32_t max_w) { uint32_t b = 0; while (b < 32u && (1ull << b) < max_w) b++; return b; }
+
 template <uint32_t NW_, uint32_t MAXEV_, uint32_t MAXW_, uint32_t MAXR_, uint32_t HBITS_ = 16>
 struct Geo {
   static constexpr uint32_t kNW = NW_, kT = 64 * NW_, kMaxEvents = MAXEV_, kMaxW = MAXW_, kMaxR = MAXR_, kHBits = HBITS_, kHPer = 32 / HBITS_;
   static_assert((HBITS_ == 8 || HBITS_ == 16) && MAXW_ < (1u << HBITS_), "a histogram entry counts up to one call per slot");
   static constexpr bool kCounts = MAXR_ != 0;
+  static constexpr uint32_t kSlotBits = slot_bits(MAXW_);     // the bits of a slot number 0 .. MAXW_ - 1 (phase 4 matches lanes by them)
   static constexpr uint32_t kBmWords = MAXEV_ / 32 + 32;      // (+ the word E / 32 itself and padding)
   // LDS words: bitmap | prefix | (block, process) counts | list starts | per-wavefront scan totals | flags | (COUNTS) histogram of
   // invocation ranks, two (or four) ranks a word | (COUNTS) the ranks at which a read completes, one bit each
@@ -240,7 +243,7 @@ WV_DEV void history(const PackArgs& A, const PackOpenArgs& O, uint32_t* lds) {
 
   // ---- phase 4: every wavefront walks its block, 64 ops at a time.  An op's place in its process's list = the list's first
   // record + 1 + the ops of the process placed by earlier blocks and earlier chunks of this block (cnt) + the lower lanes of this
-  // chunk holding an op of the same process (64 lane reads, counted in registers).  Ranks come from the LDS bitmap; the record
+  // chunk holding an op of the same process (match-any by ballots over the slot's bits).  Ranks come from the LDS bitmap; the record
   // goes out at once.  The next chunk's columns are requested before this one's are used.
   // COUNTS: with the ranks in hand, what open_counts_kernel would fetch them again for -- the completion's slot and read kind as
   // bytes, the call's invocation rank into the histogram of the listed calls (branch lists: a live read is not listed, its
@@ -263,12 +266,17 @@ WV_DEV void history(const PackArgs& A, const PackOpenArgs& O, uint32_t* lds) {
       n_p = in ? proc[i] : 0; n_a = in ? a[i] : 0; n_b = in ? b[i] : 0;
       const bool live = here && rt != TBC_POS_CRASHED;
       const uint32_t p = (here && !(cf && rt == TBC_POS_CRASHED)) ? (uint32_t)pp : 0xFFFFFFFFu;     // 0xFFFFFFFF: equal to no process
-      uint32_t before = 0u;
-      for (uint32_t l = 0; l < 64u; l++) {
-        const uint32_t pl = wv::readlane(p, l);
-        before += (pl == p && l < lane) ? 1u : 0u;
-      }
       const bool slotted = p != 0xFFFFFFFFu;
+      // the lanes holding the same slot number: one ballot per bit of it (a slot is below W <= G::kMaxW, phase 1 checked), each lane
+      // taking the ballot or its complement, all of them anded; a slotless lane is in no ballot, so it matches nobody
+      uint64_t same = wv::ballot(slotted);
+      WV_UNROLL
+      for (uint32_t bit = 0; bit < G::kSlotBits; bit++) {
+        const bool set = ((p >> bit) & 1u) != 0u;
+        const uint64_t m = wv::ballot(slotted && set);
+        same &= set ? m : ~m;
+      }
+      const uint32_t before = (uint32_t)__builtin_popcountll(same & ((1ull << lane) - 1ull));
       uint32_t dst = kInf;
       if (slotted) dst = seg[p] + 1u + mycnt[p] + before;
       wv::barrier();

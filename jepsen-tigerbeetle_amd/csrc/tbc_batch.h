@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 #include "tbc_internal.h"
+#include "pool_plan.h"
 
 namespace tbc {
 
@@ -311,6 +312,7 @@ struct tbc_batch {
   uint32_t tab_stride() const { return entry_words() - ((lanes && !opts.want_witness) ? 1u : 0u); }
   uint32_t entry_words() const { return mask_words + 2u + (count_form ? tbc::kCountWords : 0u); }   // u64 words per wide-schedule entry
   tbc::DevBuf<unsigned long long> d_pool_cursor;
+  tbc::PoolState pool_state;        // what the next pass zeroes of d_pool: all of it, or what the searches were handed (pool_plan.h)
   // last run
   std::vector<tbc::DevResult> res_host;
   std::vector<uint32_t> witness_host;
