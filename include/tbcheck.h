@@ -42,7 +42,8 @@ extern "C" {
  * gained TBC_DOM_NO_COUNT_FORM.  A caller built against another version must refuse the library (tbc_version()).
  * Still 2, additive: the word that was reserved0 (must be 0) is tbc_opts.list_order, 0 = the library's choice; tbc_batch_list_order().
  * Still 2, additive (round 6): tbc_batch_map_input / _submit_input / _reload / _input_info (fresh histories into a batch's arenas),
- * tbc_comm_* (the sharded sweep's exchange behind the C-ABI); tbc_setfull_create_rows takes its exception lists in any order again. */
+ * tbc_comm_* (the sharded sweep's exchange behind the C-ABI); tbc_setfull_create_rows takes its exception lists in any order again.
+ * Still 2, additive: tbc_ledger_snapshots and its structs. */
 #define TBC_ABI_VERSION 2u
 
 /* ------------------------------------------------------------------ status */
@@ -947,6 +948,48 @@ typedef struct tbc_ledger_rt_out {        /* arrays caller-allocated, each optio
   tbc_ledger_rt_summary summary;
 } tbc_ledger_rt_out;
 tbc_status tbc_ledger_realtime(const tbc_ledger_rt_in* in, tbc_ledger_rt_out* out);
+
+/* ------------------------------------------------------------------- ledger: reads as snapshots in one order
+ * credits-posted and debits-posted only grow and the workload's reads read every account, so under serializability the reads of a
+ * history are a CHAIN under component-wise <=.  Two reads are SKEWED when each is below the other on some counter (a long fork: the
+ * 2-cycle of the monotonic-key graph); with every read complete, "no read skewed" plus "no read regressed" (tbc_ledger_realtime) holds
+ * exactly when the graph of monotonic-key and realtime edges over the reads is acyclic.  THE RULES ARE STATED ONCE, in the docstring of
+ * jepsen/ledger.py ("Snapshot order"): reads, checked micro-ops, counters, complete / partial, below, skewed, the summary, the ranges.
+ * Input: a plain tbc_ledger_in (total_amount and negative_balances are not used; no process column: real time is
+ * tbc_ledger_realtime's business).  Rows: reads are numbered as for tbc_ledger_check.  A counter is 2 x (the account's position in
+ * `accounts`) + (0 credits-posted, 1 debits-posted).
+ *   skew_count[r]    the reads r is skewed with
+ *   skew_first[r]    the least read number among them, TBC_NO_OP if none
+ *   skew_key[r][2]   against that first partner: the least counter on which r is below it, the least on which r is above it; TBC_NO_OP
+ *   snap_flags[r]    TBC_LEDGER_SNAP_PARTIAL (the read does not check every account) | TBC_LEDGER_SNAP_SKEWED
+ * The host plans what is O(ops) (csrc/ledger_snap_plan.h) and reads no micro-op beyond the validation of the reads' own; only the reads'
+ * id, a, b and flags are copied (25 bytes a micro-op).  The device lays the reads out densely, sorts them by (sum, read number), scans
+ * prefix maxima and suffix minima per counter to find the CANDIDATES -- the partial reads, and the complete reads skewed with a complete
+ * read -- and compares only those with every read (csrc/ledger_snap_kernels.h): a history without candidates launches no pair kernel.
+ * Every rule of tbc_ledger_in: TBC_ERR_INVALID_ARG before any device call, and so are reads x counters >= 2^31 and 2^31 micro-ops of
+ * reads in one call.  The whole int64 range of a counter works, negative values included; a read whose sum of |v| over its checked
+ * counters reaches 2^63 is counted ON THE DEVICE: TBC_ERR_UNSUPPORTED, no results, summary.bad_values says how many.  No gfx950 device:
+ * TBC_ERR_NO_DEVICE.  One-shot and re-entrant as tbc_ledger_check is. */
+#define TBC_LEDGER_SNAP_PARTIAL 1u
+#define TBC_LEDGER_SNAP_SKEWED  2u
+
+typedef struct tbc_ledger_snap_summary {
+  uint32_t read_count, n_partial, valid, bad_values;      /* valid: no read is skewed; bad_values: reads whose sum of |v| reaches 2^63 */
+  tbc_ledger_errors skewed;                               /* read numbers; worst = the greatest skew_count, ties the earliest */
+  uint32_t n_candidates, reserved0;                       /* the reads the pair kernel took: n_partial + the complete reads skewed with a complete read */
+  uint64_t n_checked;                                     /* read micro-ops checked */
+  uint64_t n_pairs;                                       /* unordered skewed pairs */
+  uint64_t ns_device;                                     /* the kernels, between HIP events */
+  uint64_t bytes_in;                                      /* copied to the device */
+} tbc_ledger_snap_summary;
+
+typedef struct tbc_ledger_snap_out {      /* arrays caller-allocated, each optional (NULL = not wanted) */
+  uint32_t *skew_count, *skew_first;      /* [n_ok_reads] */
+  uint32_t* skew_key;                     /* [n_ok_reads][2] */
+  uint8_t* snap_flags;                    /* [n_ok_reads] */
+  tbc_ledger_snap_summary summary;
+} tbc_ledger_snap_out;
+tbc_status tbc_ledger_snapshots(const tbc_ledger_in* in, tbc_ledger_snap_out* out);
 
 /* ------------------------------------------------------------------- perf: the series behind the reference's perf plots
  * checker/perf.clj composes latency-graph, rate-graph and open-ops-graph into every test.  What it PLOTS is out of scope (gnuplot,

@@ -255,6 +255,21 @@ class LedgerRtOut(C.Structure):
                 ("mop_hi", C.POINTER(C.c_int64)), ("mop_floor", C.POINTER(C.c_int64)), ("summary", LedgerRtSummary)]
 
 
+# tbc_ledger_snapshots: the reads of a ledger as snapshots in one order (include/tbcheck.h); its input is a plain LedgerIn
+LEDGER_SNAP_PARTIAL, LEDGER_SNAP_SKEWED = 1, 2
+
+
+class LedgerSnapSummary(C.Structure):
+    _fields_ = [("read_count", C.c_uint32), ("n_partial", C.c_uint32), ("valid", C.c_uint32), ("bad_values", C.c_uint32),
+                ("skewed", LedgerErrors), ("n_candidates", C.c_uint32), ("reserved0", C.c_uint32), ("n_checked", C.c_uint64),
+                ("n_pairs", C.c_uint64), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64)]
+
+
+class LedgerSnapOut(C.Structure):
+    _fields_ = [("skew_count", C.POINTER(C.c_uint32)), ("skew_first", C.POINTER(C.c_uint32)), ("skew_key", C.POINTER(C.c_uint32)),
+                ("snap_flags", C.POINTER(C.c_uint8)), ("summary", LedgerSnapSummary)]
+
+
 # tbc_perf_series: the series behind the reference's perf plots from op columns (include/tbcheck.h TBC_PERF_*)
 PERF_T_INVOKE, PERF_T_OK, PERF_T_FAIL, PERF_T_INFO = 0, 1, 2, 3
 PERF_O_NONE = 0
@@ -357,6 +372,7 @@ SYMBOLS = {
     "tbc_setfull_keys_encoding": (C.c_int, [C.c_void_p, C.POINTER(SetFullEncoding)]),
     "tbc_ledger_check": (C.c_int, [C.POINTER(LedgerIn), C.POINTER(LedgerOut)]),
     "tbc_ledger_realtime": (C.c_int, [C.POINTER(LedgerRtIn), C.POINTER(LedgerRtOut)]),
+    "tbc_ledger_snapshots": (C.c_int, [C.POINTER(LedgerIn), C.POINTER(LedgerSnapOut)]),
     "tbc_perf_plan_sizes": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfSizes)]),
     "tbc_perf_series": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfOut)]),
     "tbc_batch_destroy": (None, [C.c_void_p]),

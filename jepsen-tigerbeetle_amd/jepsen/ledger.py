@@ -45,6 +45,36 @@ doc/LASS.md: its "compare w r" and "compare r r'" rules).  THE RULES, stated onc
   OPTIONS: "accounts"; "initial" {account: {"credits-posted": c, "debits-posted": d}}, 0 where an account is not named (the test
     generators fund accounts with credits: they need it); "ok-transfers-apply?".
 
+Snapshot order (`snapshots_host` the specification, `snapshots_numpy` the sort-and-scan statement the device is compared with,
+`SnapshotOrder` the checker, `check_snapshots_native` / `snapshots_result_map` the device route over tbc_ledger_snapshots;
+`test(snapshots=True)` composes the member "snapshots").  Not in the reference either: every checker above looks at one read at a time
+(its total) or one counter at a time (its bounds in real time); none compares two reads ACROSS accounts, so a long fork -- R sees
+transfer T1 and not T2, R' sees T2 and not T1, both concurrent -- passes them all.  The posted counters only grow and the workload's
+reads read every account, so under serializability the reads of a history are a CHAIN under component-wise <=.  This is LASS.md's
+discrete anomaly ("r and r' claim to have read some values in common, and in addition, each has read unique values") and the 2-cycle of
+monotonic-key-graph in the reference's unfinished elle/core.clj.  THE RULES, stated once here:
+
+  READS, their numbering and their micro-ops are those of the realtime rules: a read is an :ok completion whose op_txn_f is "r", a row
+    of LedgerColumns.read_ops; its micro-ops are taken after ledger->bank's last-wins; a micro-op that is nil, or whose id is no
+    account, is NOT CHECKED.
+  A COUNTER is c = 2 k + x: k the account's position in `accounts`, x = 0 for credits-posted and 1 for debits-posted.  A read's VECTOR
+    has a value at the counters it checks.  A read is COMPLETE if it checks every account, PARTIAL otherwise.
+  R is BELOW R' on c if both check c and v_R[c] < v_R'[c].  R and R' (R /= R') are SKEWED if R is below R' on some c and R' is below R
+    on some d.
+  PER READ: skew_count the number of reads it is skewed with; skew_first the least read number among them, NO_OP if none; skew_key[2],
+    against that first partner, the least counter on which the read is below it and the least on which it is above it (both NO_OP
+    without a partner: MonotonicKeyExplainer's key, twice); snap_flags bit 1 partial, bit 2 skewed.
+  SUMMARY: read_count, n_partial; n_checked = the read micro-ops checked; over the skewed reads count, first, last, worst (the greatest
+    skew_count; ties go to the earliest read, as everywhere here); n_pairs = the unordered skewed pairs; valid = no read is skewed;
+    n_candidates = n_partial + the complete reads skewed with a complete read (what the device's filter hands to its pair kernel).
+  EXACT: with every read complete, "no two reads skewed" plus "no read regressed" (the realtime rules' bit) holds exactly when the
+    graph of monotonic-key edges plus realtime edges over the reads is acyclic -- no SCC pass is needed.  The result map carries
+    "exact?" = n_partial == 0.  With partial reads the rule is still SOUND (every skewed pair is an anomaly) but no longer the whole
+    cycle search: a 3-cycle through partial reads needs no 2-cycle.
+  RANGES: per read the sum of |v| over its checked counters < 2^63 (what LedgerColumns already refuses to exceed); negative counters are
+    legal.  ValueError here; tbc_ledger_snapshots counts offending reads on the device and answers TBC_ERR_UNSUPPORTED.
+  OPTIONS: "accounts".
+
 History ops are the dicts `edn.read_history` gives: "type" "f" "value" "process" "index" "time" "final?", keywords as strings; a
 :value is a vector of micro-ops [f id m] with f in "t" "r" "l-t".
 
@@ -893,11 +923,233 @@ class _RealtimeDevice(jc.Checker):
         return realtime_result_map(history, cols, dev, accounts, init, apply_ok)
 
 
-def test(opts=None, linear=False, realtime=False, device_route=True):
+# ---------------------------------------------------------------- snapshot order of the reads
+
+SNAP_PARTIAL, SNAP_SKEWED = 1, 2
+
+
+def _snap_accounts(test, opts):
+    t = dict(opts or {})
+    t.update({k: v for k, v in (test or {}).items() if k == "accounts"})
+    return list(t.get("accounts") or range(1, 9))
+
+
+def _snap_vectors(history, accounts):
+    """per :ok read (LedgerColumns' read_ops numbering) its vector {counter: value} over the counters it checks, and their history indexes"""
+    pos = {a: k for k, a in enumerate(accounts)}
+    vectors, index = [], []
+    for i, op in enumerate(history):
+        if H.client_op(op) and op_txn_f(op) == "r" and op["type"] == "ok":
+            v = {}
+            for ident, cr, db, nil in _read_mops(op):
+                if not nil and ident in pos:
+                    v[2 * pos[ident]], v[2 * pos[ident] + 1] = cr, db
+            if sum(abs(x) for x in v.values()) >= 2 ** 63:
+                raise ValueError(f"snapshots: op {i}: the read's |credits| + |debits| reach 2^63")
+            vectors.append(v)
+            index.append(i)
+    return vectors, index
+
+
+def _snap_summary(count, flags, n_checked, n_candidates):
+    """the summary of tbc_ledger_snap_summary (without ns_device and bytes_in) from the per-read arrays"""
+    has = np.flatnonzero(count)
+    e = {"count": len(has), "first": N.NO_OP, "last": N.NO_OP, "worst": N.NO_OP}
+    if len(has):
+        e.update({"first": int(has[0]), "last": int(has[-1]), "worst": int(has[np.argmax(count[has])])})       # (argmax: the earliest of equals)
+    return {"read_count": len(count), "n_partial": int(np.count_nonzero(flags & SNAP_PARTIAL)), "valid": int(not len(has)), "bad_values": 0,
+            "skewed": e, "n_candidates": n_candidates, "n_checked": n_checked, "n_pairs": int(count.astype(np.int64).sum()) // 2}
+
+
+def snapshots_vectors_host(vectors, n_accounts):
+    """The specification of the snapshot order (module docstring) over vectors {counter: value}, pair by pair; O(R^2 C).  Per read "count",
+    "first", "key" [below, above] and "flags", and the "summary" tbc_ledger_snapshots gives."""
+    R = len(vectors)
+    below = lambda a, b: sorted(c for c in a if c in b and a[c] < b[c])
+    complete = [len(v) == 2 * n_accounts for v in vectors]
+    count, first = np.zeros(R, np.uint32), np.full(R, N.NO_OP, np.uint32)
+    key, flags = np.full((R, 2), N.NO_OP, np.uint32), np.zeros(R, np.uint8)
+    with_complete = [False] * R
+    for i in range(R):
+        for j in range(R):
+            if i != j and below(vectors[i], vectors[j]) and below(vectors[j], vectors[i]):
+                count[i] += 1
+                with_complete[i] = with_complete[i] or complete[j]
+                if first[i] == N.NO_OP:
+                    first[i] = j
+                    key[i] = below(vectors[i], vectors[j])[0], below(vectors[j], vectors[i])[0]
+        flags[i] = (0 if complete[i] else SNAP_PARTIAL) | (SNAP_SKEWED if count[i] else 0)
+    n_candidates = sum(1 for i in range(R) if not complete[i] or with_complete[i])
+    return {"count": count, "first": first, "key": key, "flags": flags,
+            "summary": _snap_summary(count, flags, sum(len(v) // 2 for v in vectors), n_candidates)}
+
+
+def snapshots_host(history, opts=None):
+    """snapshots_vectors_host over the history's :ok reads (LedgerColumns' read_ops numbering).  opts: "accounts"."""
+    accounts = _snap_accounts(None, opts)
+    return snapshots_vectors_host(_snap_vectors(history, accounts)[0], len(accounts))
+
+
+def snapshots_dense_numpy(V, K):
+    """The sort-and-scan statement over dense rows: V [R][C] int64 values, K [R][C] bool, which are checked (C = 2 x accounts).  The
+    complete reads sorted by (sum, read number); for i before j in that order skewed(i, j) <=> some v_i[c] > v_j[c], so the exclusive prefix
+    maximum and suffix minimum per counter flag exactly the complete reads skewed with a complete read; those and the partial reads are
+    the candidates, and only they are compared with every read.  What the device is held to, n_candidates included."""
+    R, C = V.shape
+    complete = K.all(axis=1)
+    near = np.flatnonzero((np.abs(V.astype(np.float64)) * K).sum(axis=1) >= 2.0 ** 62)       # (the few rows worth exact arithmetic)
+    if any(sum(abs(int(x)) for x in V[r][K[r]]) >= 2 ** 63 for r in near):
+        raise ValueError("snapshots: a read's |credits| + |debits| reach 2^63")
+    count, first = np.zeros(R, np.int64), np.full(R, N.NO_OP, np.int64)
+    key = np.full((R, 2), N.NO_OP, np.uint32)
+    flagged = np.zeros(R, bool)
+    full = np.flatnonzero(complete)
+    if len(full) and C:
+        order = full[np.lexsort((full, V[full].sum(axis=1)))]
+        S = V[order]
+        before = np.vstack([np.full((1, C), _I64_MIN, np.int64), np.maximum.accumulate(S, axis=0)[:-1]])
+        after = np.vstack([np.minimum.accumulate(S[::-1], axis=0)[::-1][1:], np.full((1, C), _I64_MAX, np.int64)])
+        flagged[order] = (before > S).any(axis=1) | (after < S).any(axis=1)
+    cand = flagged | ~complete
+    for i in np.flatnonzero(cand):
+        both = K & K[i]
+        skewed = (both & (V[i] < V)).any(axis=1) & (both & (V[i] > V)).any(axis=1)
+        partners = np.flatnonzero(skewed)
+        count[i] += len(partners)
+        if len(partners):
+            first[i] = min(first[i], partners[0])
+        others = partners[~cand[partners]]                       # partners that are no candidates: nobody else counts these pairs
+        count[others] += 1
+        first[others] = np.minimum(first[others], i)
+    for i in np.flatnonzero(count):
+        j = first[i]
+        both = K[i] & K[j]
+        key[i] = np.flatnonzero(both & (V[i] < V[j]))[0], np.flatnonzero(both & (V[i] > V[j]))[0]
+    flags = (np.where(complete, 0, SNAP_PARTIAL) | np.where(count > 0, SNAP_SKEWED, 0)).astype(np.uint8)
+    count = count.astype(np.uint32)
+    return {"count": count, "first": first.astype(np.uint32), "key": key, "flags": flags,
+            "summary": _snap_summary(count, flags, int(K.sum()) // 2, int(np.count_nonzero(cand)))}
+
+
+def _snap_dense(cols, accounts):
+    """the :ok reads of a LedgerColumns as dense rows (V, K) over the counters of `accounts`"""
+    try:
+        acct = np.array(list(accounts), np.int64).reshape(-1)
+    except (OverflowError, TypeError, ValueError):
+        raise ValueError("an account is not an int in int64 range") from None
+    A = len(acct)
+    off = cols.mop_off.astype(np.int64)
+    rd = np.flatnonzero((cols.type == N.LEDGER_T_OK) & (cols.kind == N.LEDGER_K_READ))
+    m, row = _expand(off[rd], off[rd + 1] - off[rd])
+    V, K = np.zeros((len(rd), 2 * A), np.int64), np.zeros((len(rd), 2 * A), bool)
+    if A and len(m):
+        perm = np.argsort(acct, kind="stable")
+        k = np.minimum(np.searchsorted(acct[perm], cols.mop_id[m]), A - 1)
+        chk = (acct[perm][k] == cols.mop_id[m]) & ((cols.mop_flags[m] & N.LEDGER_M_NIL) == 0)
+        c = 2 * perm[k][chk]
+        V[row[chk], c], V[row[chk], c + 1] = cols.mop_a[m][chk], cols.mop_b[m][chk]
+        K[row[chk], c] = K[row[chk], c + 1] = True
+    return V, K
+
+
+def snapshots_numpy(history, opts=None):
+    """snapshots_host(history, opts) by sort and scan (snapshots_dense_numpy over the history's LedgerColumns)."""
+    accounts = _snap_accounts(None, opts)
+    return snapshots_dense_numpy(*_snap_dense(LedgerColumns(history), accounts))
+
+
+def _snap_map(history, read_ops, res, accounts):
+    """the snapshots result map from the per-read arrays and the summary (the host statement's or the device's)"""
+    s = res["summary"]
+    out = {"valid?": bool(s["valid"]), "exact?": s["n_partial"] == 0, "read-count": s["read_count"], "partial-count": s["n_partial"],
+           "skewed-count": s["skewed"]["count"], "pair-count": s["n_pairs"], "first": None, "worst": None, "last": None}
+    if not s["skewed"]["count"]:                        # (no read to name: no pass over the history)
+        return out
+    hist = _indexed(history) if any("index" not in op for op in history) else history
+    counter = lambda c: [accounts[int(c) // 2], RT_FIELDS[int(c) % 2]]
+
+    def named(r):
+        return {"op": hist[int(read_ops[r])], "skew-count": int(res["count"][r]), "with": hist[int(read_ops[int(res["first"][r])])],
+                "below": counter(res["key"][r][0]), "above": counter(res["key"][r][1])}
+
+    out.update({k: named(s["skewed"][k]) for k in ("first", "worst", "last")})
+    return out
+
+
+class SnapshotOrder(jc.Checker):
+    """snapshots: no two :ok reads are skewed -- each below the other on some posted counter (module docstring, "Snapshot order").  With
+    every read complete this and RealtimeBounds' regressed bit are the whole cycle search over monotonic-key and realtime edges
+    ("exact?"); with partial reads it is sound but not complete.  opts: "accounts"."""
+
+    def __init__(self, opts=None):
+        self.opts = dict(opts or {})
+
+    def check(self, test, history, opts=None):
+        accounts = _snap_accounts(test, self.opts)
+        vectors, index = _snap_vectors(history, accounts)
+        return _snap_map(history, index, snapshots_vectors_host(vectors, len(accounts)), accounts)
+
+
+def ledger_snap_in(cols, accounts, device=0):
+    """The tbc_ledger_in tbc_ledger_snapshots takes over a LedgerColumns (and the arrays it points into)."""
+    return ledger_in(cols, accounts, False, device)
+
+
+def snap_summary_dict(s):
+    d = {f: int(getattr(s, f)) for f, _ in N.LedgerSnapSummary._fields_ if f not in ("skewed", "reserved0")}
+    d["skewed"] = {f: int(getattr(s.skewed, f)) for f in ("count", "first", "last", "worst")}
+    return d
+
+
+def check_snapshots_native(cols, accounts, device=0, call=None):
+    """tbc_ledger_snapshots over the columns -> snapshots_host's arrays and the summary (with ns_device and bytes_in).  call(in, out): another
+    implementation of the entry point (the tests' emulator build of the same kernels).  A read out of range is the device's to find
+    (TBC_ERR_UNSUPPORTED): ValueError here too."""
+    s, keep = ledger_snap_in(cols, accounts, device)
+    R = len(cols.read_ops)
+    arr = {"skew_count": np.zeros(max(1, R), np.uint32), "skew_first": np.zeros(max(1, R), np.uint32),
+           "skew_key": np.zeros((max(1, R), 2), np.uint32), "snap_flags": np.zeros(max(1, R), np.uint8)}
+    out = N.LedgerSnapOut()
+    for f in ("skew_count", "skew_first", "skew_key"):
+        setattr(out, f, _ptr(arr[f], C.c_uint32))
+    out.snap_flags = _ptr(arr["snap_flags"], C.c_uint8)
+    if call is None:
+        st = N.lib().tbc_ledger_snapshots(C.byref(s), C.byref(out))
+        if st == N.ERR_UNSUPPORTED:
+            raise ValueError("snapshots: " + N.lib().tbc_last_error().decode())
+        N.check_status(st)
+    else:
+        call(s, out)
+    del keep
+    return {"count": arr["skew_count"][:R], "first": arr["skew_first"][:R], "key": arr["skew_key"][:R], "flags": arr["snap_flags"][:R],
+            "summary": snap_summary_dict(out.summary)}
+
+
+def snapshots_result_map(history, cols, dev, accounts):
+    """SnapshotOrder's result map from tbc_ledger_snapshots' arrays and summary: the three reads it names come from the history by index
+    (a valid history: none, and no pass over it)."""
+    assert dev["summary"]["read_count"] == len(cols.read_ops)
+    return _snap_map(history, cols.read_ops, dev, list(accounts))
+
+
+class _SnapshotDevice(jc.Checker):
+    """the snapshots member on the device route: columns -> tbc_ledger_snapshots -> SnapshotOrder's map.  No host route behind it."""
+
+    def __init__(self, opts):
+        self.opts = dict(opts or {})
+
+    def check(self, test, history, opts=None):
+        accounts = _snap_accounts(test, self.opts)
+        cols = LedgerColumns(history)
+        dev = check_snapshots_native(cols, accounts, device=(opts or {}).get("device", 0))
+        return snapshots_result_map(history, cols, dev, accounts)
+
+
+def test(opts=None, linear=False, realtime=False, device_route=True, snapshots=False):
     """The ledger test map (tests/ledger.clj:341-369) without generators: accounts, max-transfer, total-amount and the composed checker
     -- SI, lookup-transfers, final-reads, unexpected-ops, with linear=True the member clj/patches/ledger.patch adds, and with
-    realtime=True the member "realtime" (RealtimeBounds; opts "initial", "ok-transfers-apply?"), on the device or as the host statement
-    according to device_route.
+    realtime=True the member "realtime" (RealtimeBounds; opts "initial", "ok-transfers-apply?") and with snapshots=True the member
+    "snapshots" (SnapshotOrder), each on the device or as the host statement according to device_route.
     device_route=True (the default: the whole call measured 1.7-1.8 s against the host statement's 6.6-6.7 s on a ledger of 64 workers and 50k
     transfers, profiles/NOTES_ledger.md) answers the first three from one check_columns call; False runs the host statement."""
     opts = dict(opts if opts is not None else {"negative-balances?": False})
@@ -912,6 +1164,8 @@ def test(opts=None, linear=False, realtime=False, device_route=True):
     members["unexpected-ops"] = UnexpectedOps()
     if realtime:
         members["realtime"] = _RealtimeDevice(opts) if device_route else RealtimeBounds(opts)
+    if snapshots:
+        members["snapshots"] = _SnapshotDevice(opts) if device_route else SnapshotOrder(opts)
     if linear:
         members["linear"] = _Linear(opts["accounts"], bool(opts.get("negative-balances?", False)))
     return dict(opts, checker=jc.compose(members))
