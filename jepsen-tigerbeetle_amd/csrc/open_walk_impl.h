@@ -20,8 +20,13 @@
 // per lane (three register sets), one ballot per write / cas candidate finds its few static twins, and each of those costs the
 // lanes one membership test.
 //
+// A wavefront of the kernel takes a RUN of kWalkRun consecutive chunks of one history (walk_run), one after the other: the first
+// chunk finds each slot's first candidate by a binary search of the slot's records, the others carry the cursor on from the chunk
+// before (phase A).  walk_wave is one chunk from nothing; both forms share the body, walk_chunk.
+//
 // The body is written against wave_env.h like the narrow search kernel, so tests/emu runs it on the CPU (lane-accurate
-// emulator) and compares every word with tables built on the host from the definitions (tests/test_walk_emu.py).
+// emulator) and compares every word with tables built on the host from the definitions (tests/test_walk_emu.py: walk_wave;
+// tests/test_walk_runs_emu.py: walk_run, where the emulated build also searches and counts a carried cursor that differs).
 #pragma once
 #include "wave_env.h"
 #include "tbc_internal.h"
@@ -34,7 +39,10 @@ constexpr uint32_t kCandWords = 8;          // inv_rank, ret_rank, opidx, f | sl
 constexpr uint32_t kAuxWords = 80;          // the scan of the per-slot counts; later the rank codes of the chunk + 6
 constexpr uint32_t kKeyWords = 32, kKeyBits = 32 * kKeyWords;       // A2's map of the live candidates' keys and its prefix, over the same words
 static_assert(2 * kKeyWords <= kAuxWords && kKeyWords == 32, "the map and its prefix fit the scratch; two rows of 16 lanes scan it");
-WV_HD constexpr uint32_t walk_lds_words() { return kCandCap * kCandWords + kAuxWords; }
+constexpr uint32_t kCursorWords = 64 + 32;   // what a slot lane carries from a chunk of a run to the next (walk_run): where this chunk's candidates
+//                                             ended (a word), and how many of them the next chunk still has (16 bits: eight at most, see phase A)
+WV_HD constexpr uint32_t walk_lds_words() { return kCandCap * kCandWords + kAuxWords + kCursorWords; }
+static_assert(4u * walk_lds_words() * sizeof(uint32_t) <= 20u * 1024u, "eight blocks of four wavefronts a CU");
 
 // candidate word 6: what the loop does with the call, decided once when the table is filled
 constexpr uint32_t kCList = 1u;             // live and in the fronts' lists (branch lists: not a read)
@@ -72,17 +80,57 @@ WV_DEV void store_entries(const wv::u32x16& r, uint64_t* row, uint32_t n) {     
   for (int v = 0; v < 8; v++) if ((uint32_t)(8 * Q + v) < n) row[8 * Q + v] = (uint64_t)r[2 * v] | ((uint64_t)r[2 * v + 1] << 32);
 }
 
+// A wavefront of the kernel owns a RUN of kWalkRun consecutive chunks of one history (walk_run below) and takes them one after the
+// other; what it carries from a chunk to the next is, per slot lane, where this chunk's candidates ended and how many of them are the next
+// chunk's too (LDS, kCursorWords) -- so only a run's first chunk searches (phase A).
+#ifndef TBC_WALK_RUN
+#define TBC_WALK_RUN 8
+#endif
+constexpr uint32_t kWalkRun = TBC_WALK_RUN;
+static_assert(kWalkRun >= 1u, "a run has a chunk");
+// wv::stat ids of an emulated run (tests/emu): chunks that searched, chunks that took the carried cursors, slot lanes whose carried
+// cursor is not what the search finds
+constexpr uint32_t kStatWalkSearch = 40, kStatWalkCarried = 41, kStatWalkCursorMiss = 42;
+
+// a UNIFORM value, opaque to the optimiser: what a chunk of a run derives from the history's number is worked out again per chunk
+// instead of being kept in registers over the whole run (wv::opaque does the same for the lane number)
+#if defined(TBC_EMU)
+WV_DEV uint32_t opaque_uniform(uint32_t v) { return v; }
+#else
+WV_DEV uint32_t opaque_uniform(uint32_t v) { asm volatile("" : "+s"(v)); return v; }
+#endif
+
+// What the walk only reads and reads at a UNIFORM address (a history's descriptors, its list of slot starts), as constant memory: scalar
+// loads.  A run's later chunks come after the stores of the chunks before, and behind a store the compiler takes a load from global memory
+// through the vector memory pipe whatever its address -- a dozen vector loads and two dependent trips at the head of every chunk.
+#if defined(TBC_EMU)
+template <class T>
+WV_DEV const T* read_only(const T* p) { return p; }
+#else
+template <class T>
+WV_DEV const __attribute__((address_space(4))) T* read_only(const T* p) { return (const __attribute__((address_space(4))) T*)(uintptr_t)p; }
+#endif
+
+// the first of the slot's records [l, hi) that has not completed before ret_from (hi: the tail sentinel)
+WV_DEV uint32_t first_open(const Rec* rec, uint32_t l, uint32_t hi, uint32_t ret_from) {
+  while (l < hi) {
+    const uint32_t mid = (l + hi) >> 1;
+    if (rec[mid].ret_rank >= ret_from) hi = mid; else l = mid + 1u;
+  }
+  return l;
+}
+
+// One chunk: fronts 64 c .. 64 c + 63 of history h.  carried: the slot cursors are what the chunk before left in LDS (else: from nothing).
+// Returns whether the history has a front after this chunk.
 // VCAP: row entries kept in registers (vpad <= VCAP)
 template <int VCAP>
-WV_DEV void walk_wave(const PackOpenArgs& A, uint32_t wid, uint32_t* lds, uint32_t lane) {
-  const uint32_t cph = A.chunks_per_hist;
-  const uint32_t hr = wid / cph, c = wid - hr * cph, h = A.h0 + hr;
-  if (h >= A.n_hist) return;
-  const Hist* H = &A.hist[h];
-  const BeamHist* B = &A.bh[h];
+WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t* lds, uint32_t lane, bool carried) {
+  const auto& A = *wv::cold(A_);            // (the arguments from the kernarg segment, per chunk: not some sixty scalar registers held over a run)
+  const auto* H = read_only(&A.hist[h]);
+  const auto* B = read_only(&A.bh[h]);
   const uint32_t R = H->n_ret;
   const uint32_t F_lo = c * 64u;
-  if (H->status != 0 || B->status != 0 || F_lo >= R) return;
+  if (H->status != 0 || B->status != 0 || F_lo >= R) return false;
   const uint32_t F_hi = F_lo + 64u < R ? F_lo + 64u : R;
   const uint32_t W = H->n_slots;
   const Rec* rec = A.rec + H->rec_off;
@@ -98,23 +146,38 @@ WV_DEV void walk_wave(const PackOpenArgs& A, uint32_t wid, uint32_t* lds, uint32
   uint64_t* look = A.look ? A.look + look_off(H->op_off, h, 1u) : nullptr;
   uint32_t* cand = lds;
   uint32_t* aux = lds + kCandCap * kCandWords;
+  uint32_t* const cur_end = aux + kAuxWords;                         // the cursors: a lane reads what it wrote itself (no barrier)
+  uint16_t* const cur_left = reinterpret_cast<uint16_t*>(cur_end + 64);
 
   // ---- A. lane = process slot: the slot's candidates are consecutive records -- from the first that has not completed before
-  // F_lo (lookahead: F_lo - 7, for the producer distance) to the last invoked before the chunk's last front
+  // F_lo (lookahead: F_lo - 7, for the producer distance) to the last invoked before the chunk's last front.
+  // The records of a slot are in order of invocation AND of completion, and the next chunk's ret_from is no smaller: its first
+  // candidate is this chunk's first plus those of this chunk's candidates that complete before the next ret_from (counted where
+  // the table is filled), and the record after this chunk's last candidate -- invoked at F_hi or later, so completing there or
+  // later -- is where the next chunk's scan of invocation ranks goes on.  Only a run's first chunk searches.  (Of a slot's candidates
+  // at most eight are the next chunk's as well: a slot has one call open at a time, so they complete at ranks of their own from
+  // F_lo + 64 - 7 on, and only the last of them at F_lo + 64 or later.)
+  // The scan loads four ranks a trip and looks at none behind the first that ends it, which the slot's tail sentinel (inv = kInf) does at
+  // the latest: the indices are kept inside the HISTORY's records, not the slot's.
   const uint32_t ret_from = look ? (F_lo >= kLookahead - 1u ? F_lo - (kLookahead - 1u) : 0u) : F_lo;
+  const uint32_t ret_from_next = look ? F_lo + 64u - (kLookahead - 1u) : F_lo + 64u;
   uint32_t lo = 0, k = 0;
+  if (lane == 0u) wv::stat(carried ? kStatWalkCarried : kStatWalkSearch, 1);
   if (lane < W) {
-    uint32_t l = seg[lane] + 1u, hi = seg[lane + 1] - 1u;          // [l, hi): the slot's calls; hi = its tail sentinel (inv = ret = kInf)
-    const uint32_t tail = hi;
-    while (l < hi) {
-      const uint32_t mid = (l + hi) >> 1;
-      if (rec[mid].ret_rank >= ret_from) hi = mid; else l = mid + 1u;
+    uint32_t i;
+    if (carried) { i = cur_end[lane]; lo = i - cur_left[lane]; }
+    else {
+      lo = first_open(rec, seg[lane] + 1u, seg[lane + 1] - 1u, ret_from);      // (up to the slot's tail sentinel: inv = ret = kInf)
+      i = lo;
     }
-    lo = l;
-    uint32_t i = lo;
+#if defined(TBC_EMU)
+    if (carried && lo != first_open(rec, seg[lane] + 1u, seg[lane + 1] - 1u, ret_from)) wv::stat(kStatWalkCursorMiss, 1);
+    if (i > seg[lane + 1] - 1u) wv::stat(kStatWalkCursorMiss, 1);     // (the scan starts at the tail sentinel at the latest)
+#endif
+    const uint32_t last = read_only(seg)[W] - 1u;                              // the history's last record (the last slot's tail sentinel)
     for (;;) {                                                      // four invocation ranks per trip (one or two calls is the rule)
-      const uint32_t i1 = i + 1u < tail ? i + 1u : tail, i2 = i + 2u < tail ? i + 2u : tail, i3 = i + 3u < tail ? i + 3u : tail;
-      const uint32_t v0 = rec[i < tail ? i : tail].inv_rank, v1 = rec[i1].inv_rank, v2 = rec[i2].inv_rank, v3 = rec[i3].inv_rank;
+      const uint32_t i1 = i + 1u < last ? i + 1u : last, i2 = i + 2u < last ? i + 2u : last, i3 = i + 3u < last ? i + 3u : last;
+      const uint32_t v0 = rec[i].inv_rank, v1 = rec[i1].inv_rank, v2 = rec[i2].inv_rank, v3 = rec[i3].inv_rank;
       if (v0 >= F_hi) break;
       i++;
       if (v1 >= F_hi) break;
@@ -138,8 +201,10 @@ WV_DEV void walk_wave(const PackOpenArgs& A, uint32_t wid, uint32_t* lds, uint32
   const uint32_t base = incl - k;
   const uint32_t NC_all = wv::readlane(incl, 63u);
   const uint32_t NC = NC_all < kCandCap ? NC_all : kCandCap;      // (never more: see the header)
+  uint32_t gone = 0;                                                // of the slot's candidates: completed before the next chunk's ret_from
   for (uint32_t j = 0; j < k; j++) {
     const Rec r = rec[lo + j];
+    gone += r.ret_rank < ret_from_next ? 1u : 0u;
     if (base + j < kCandCap) {
       const bool live = (r.cls & 2u) != 0u, isread = (r.cls & 16u) != 0u, wc = (r.cls & 8u) != 0u;
       const bool in_chunk = r.ret_rank >= F_lo;                     // (else: completed just before the chunk, a producer only)
@@ -156,6 +221,7 @@ WV_DEV void walk_wave(const PackOpenArgs& A, uint32_t wid, uint32_t* lds, uint32
       e[7] = (live && wc && in_chunk) ? effect_key(r.f, r.a, r.b) : 0xFFFFFFFFu;
     }
   }
+  cur_end[lane] = lo + k; cur_left[lane] = (uint16_t)(k - gone);
   wv::barrier();
 
   // ---- A2. list_order 1: the loop below takes the candidates in order of completion (then every front's list comes out in that
@@ -366,20 +432,46 @@ WV_DEV void walk_wave(const PackOpenArgs& A, uint32_t wid, uint32_t* lds, uint32
     const uint32_t nl = pos - pos0, nc = A.ncr[B->off_off + Fc];
     w6 = (uint64_t)pos0 | ((uint64_t)(nl & 0xFFu) << 32) | ((uint64_t)((nl + nc) & 0xFFFFFFu) << 40);
   }
-  if (!active) return;
-  if (rdm) {
+  if (active && rdm) {
     uint64_t* row = rdm + (uint64_t)F * FW;
     const uint32_t n_row = compact ? 6u : V;
     store_entries<0>(r0, row, n_row);
     if constexpr (VCAP > 8) { store_entries<1>(r1, row, n_row); store_entries<2>(r2, row, n_row); store_entries<3>(r3, row, n_row); }
     if (compact) { row[6] = w6; row[7] = w7; }
   }
-  if (look) {
+  if (active && look) {
     uint64_t pm = (uint64_t)pm_lo | ((uint64_t)pm_hi << 32);
     pm &= ~(1ull << (px & 63u));                                    // one call per slot is open at a front: this is the completing call itself
     const uint64_t w0 = (uint64_t)(px & 0xFFFFu) | (uint64_t)need << 16 | (uint64_t)xprod << 24 | (uint64_t)di << 32 | ((uint64_t)dmin << 40);
     look[(uint64_t)F * 2u] = w0;
     look[(uint64_t)F * 2u + 1u] = pm;
+  }
+  return F_lo + 64u < R;
+}
+
+// one chunk from nothing: chunk wid % chunks_per_hist of history h0 + wid / chunks_per_hist
+template <int VCAP>
+WV_DEV void walk_wave(const PackOpenArgs& A, uint32_t wid, uint32_t* lds, uint32_t lane) {
+  const uint32_t cph = A.chunks_per_hist;
+  const uint32_t hr = wid / cph, c = wid - hr * cph, h = A.h0 + hr;
+  if (h >= A.n_hist) return;
+  (void)walk_chunk<VCAP>(A, h, c, lds, lane, false);
+}
+
+// runs a history is cut into: ceil(chunks / RUN)
+WV_HD constexpr uint32_t walk_runs_per_hist(uint32_t chunks_per_hist, uint32_t run = kWalkRun) { return (chunks_per_hist + run - 1u) / run; }
+
+// a run: chunks RUN r .. RUN r + RUN - 1 of one history (run_id = history * runs per history + r), one after the other; it ends with
+// the history's last front.  The first chunk starts from nothing, the others from the cursors the chunk before left.
+template <int VCAP, uint32_t RUN = kWalkRun>
+WV_DEV void walk_run(const PackOpenArgs& A, uint32_t run_id, uint32_t* lds, uint32_t lane) {
+  const uint32_t rph = walk_runs_per_hist(A.chunks_per_hist, RUN);
+  const uint32_t hr = run_id / rph, c0 = (run_id - hr * rph) * RUN, h = A.h0 + hr;
+  if (h >= A.n_hist) return;
+  WV_NOUNROLL
+  for (uint32_t j = 0; j < RUN; j++) {
+    if (!walk_chunk<VCAP>(A, opaque_uniform(h), c0 + j, lds, wv::opaque(lane), j != 0u)) break;
+    wv::barrier();                                                  // (every lane is done with this chunk's table and scratch words)
   }
 }
 

@@ -459,11 +459,11 @@ __global__ __launch_bounds__(256) void open_walk_kernel(PackOpenArgs A) {
 
 // ---- the same walk with lane = front (open_walk_impl.h): up to 64 process slots, rows of up to VCAP entries
 template <int VCAP>
-__global__ __launch_bounds__(256, 2) void open_walk_fronts_kernel(PackOpenArgs A) {
+__global__ __launch_bounds__(256, VCAP <= 8 ? 8 : 2) void open_walk_fronts_kernel(PackOpenArgs A) {      // (<8>: eight blocks a CU, i.e. 64 vector registers)
   extern __shared__ __attribute__((aligned(16))) uint32_t walk_lds[];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv_ = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  walk::walk_wave<VCAP>(A, blockIdx.x * 4u + wv_, walk_lds + wv_ * walk::walk_lds_words(), lane);
+  walk::walk_run<VCAP>(A, blockIdx.x * 4u + wv_, walk_lds + wv_ * walk::walk_lds_words(), lane);     // a wavefront: kWalkRun chunks of one history
 }
 
 // ---- lookahead: how recently another producer of the needed value was invoked
@@ -612,8 +612,11 @@ void launch_pack_open(const PackOpenArgs& a, void* stream, bool skip_counts) {
   const bool by_front = a.mask_words == 1 && a.vpad <= 32;
   const size_t walk_lds_bytes = 4u * walk::walk_lds_words() * sizeof(uint32_t);
   if (by_front) {
-    if (a.vpad <= 8) hipLaunchKernelGGL(open_walk_fronts_kernel<8>, dim3(wgrid), dim3(256), walk_lds_bytes, s, a);
-    else hipLaunchKernelGGL(open_walk_fronts_kernel<32>, dim3(wgrid), dim3(256), walk_lds_bytes, s, a);
+    // (a wavefront per run of kWalkRun chunks of a history, four to a block)
+    const uint64_t runs = (uint64_t)n_here * walk::walk_runs_per_hist(a.chunks_per_hist);
+    const uint32_t rgrid = (uint32_t)((runs + 3) / 4);
+    if (a.vpad <= 8) hipLaunchKernelGGL(open_walk_fronts_kernel<8>, dim3(rgrid), dim3(256), walk_lds_bytes, s, a);
+    else hipLaunchKernelGGL(open_walk_fronts_kernel<32>, dim3(rgrid), dim3(256), walk_lds_bytes, s, a);
   } else switch (a.mask_words) {
     case 2: hipLaunchKernelGGL(open_walk_kernel<2>, dim3(wgrid), dim3(256), 0, s, a); break;
     default: hipLaunchKernelGGL(open_walk_kernel<4>, dim3(wgrid), dim3(256), 0, s, a); break;
