@@ -20,13 +20,28 @@
 // per lane (three register sets), one ballot per write / cas candidate finds its few static twins, and each of those costs the
 // lanes one membership test.
 //
+// THE SPARSE FORM of phase C (rows of at most 8 entries, i.e. open_walk_fronts_kernel<8>).  The loop above asks NC x 64 times "is this
+// call open at my front?" for the ~6 x 64 times the answer is yes.  The sparse form has no loop over the candidates with lane = front: a
+// call is open at fronts inv .. ret, so with lane = candidate it toggles a bit ON at the first of them and OFF behind the last in a 64-entry
+// array in LDS, and with lane = front an inclusive XOR scan over the lanes gives every front its set of open calls.  Three kinds of set:
+// bit = place in list order (each lane then walks ITS bits and stores its front's list entries; a twin mask comes down a chain that links
+// the calls of one effect by completion, phase B2), bit = process slot per read-row entry present (the scan is the row entry), bit =
+// process slot per produced value some front needs (the scan is the producer mask).  The producer distance comes from byte counters of the
+// invocation ranks, per produced value.  The tables it leaves are the dense loop's, word for word.
+// What keeps the dense loop, decided per chunk by a uniform condition (`sparse` in walk_chunk):
+//   * rows of more than 8 entries (open_walk_fronts_kernel<32>);
+//   * a chunk of more than kSparseCand = 101 candidates: the form's round buffer lies over the end of the candidate table, so that a block
+//     keeps its 20 KB of LDS and 64 registers (eight blocks a CU: at six the kernel gave back what the form saves), and a table that full
+//     has no room for it.  At the bench's shape (6.4 calls in flight, ~75 candidates) no chunk comes near it.
+//
 // A wavefront of the kernel takes a RUN of kWalkRun consecutive chunks of one history (walk_run), one after the other: the first
 // chunk finds each slot's first candidate by a binary search of the slot's records, the others carry the cursor on from the chunk
 // before (phase A).  walk_wave is one chunk from nothing; both forms share the body, walk_chunk.
 //
 // The body is written against wave_env.h like the narrow search kernel, so tests/emu runs it on the CPU (lane-accurate
 // emulator) and compares every word with tables built on the host from the definitions (tests/test_walk_emu.py: walk_wave;
-// tests/test_walk_runs_emu.py: walk_run, where the emulated build also searches and counts a carried cursor that differs).
+// tests/test_walk_runs_emu.py: walk_run, where the emulated build also searches and counts a carried cursor that differs;
+// tests/test_walk_sparse_emu.py: the sparse form, its schedule counts, three planted mutations of it, and the dense loop beside it).
 #pragma once
 #include "wave_env.h"
 #include "tbc_internal.h"
@@ -43,6 +58,18 @@ constexpr uint32_t kCursorWords = 64 + 32;   // what a slot lane carries from a 
 //                                             ended (a word), and how many of them the next chunk still has (16 bits: eight at most, see phase A)
 WV_HD constexpr uint32_t walk_lds_words() { return kCandCap * kCandWords + kAuxWords + kCursorWords; }
 static_assert(4u * walk_lds_words() * sizeof(uint32_t) <= 20u * 1024u, "eight blocks of four wavefronts a CU");
+// The sparse form's round buffer (see phase C): per front index an ON pair and an OFF pair of toggle words, then the byte counters of the
+// invocation ranks F_lo - 7 .. F_lo + 63 (71 bytes; a front reads three words from its own).  It lies over the END of the candidate table:
+// a chunk of more than kSparseCand candidates has no room for it and takes the dense loop.
+constexpr uint32_t kTogWords = 64 * 4, kRankCntWords = 24;
+constexpr uint32_t kSparseCand = kCandCap - (kTogWords + kRankCntWords) / kCandWords;
+constexpr int kSparseSets = 2;               // ... so the form holds its candidates one per lane in two register sets, not three
+static_assert(kSparseCand <= 64u * kSparseSets, "two sets of 64 candidates");
+static_assert((kTogWords + kRankCntWords) % kCandWords == 0u && (kSparseCand * kCandWords) % 4u == 0u && kSparseCand >= 96u, "the toggle words of a front are 16 bytes, aligned");
+// blocks of four wavefronts a CU the <8> kernel is compiled for (__launch_bounds__' second argument)
+#ifndef TBC_WALK_BLOCKS
+#define TBC_WALK_BLOCKS 8
+#endif
 
 // candidate word 6: what the loop does with the call, decided once when the table is filled
 constexpr uint32_t kCList = 1u;             // live and in the fronts' lists (branch lists: not a read)
@@ -91,6 +118,51 @@ static_assert(kWalkRun >= 1u, "a run has a chunk");
 // wv::stat ids of an emulated run (tests/emu): chunks that searched, chunks that took the carried cursors, slot lanes whose carried
 // cursor is not what the search finds
 constexpr uint32_t kStatWalkSearch = 40, kStatWalkCarried = 41, kStatWalkCursorMiss = 42;
+// ... chunks that took the sparse form of phase C / the dense loop; trips of the sparse form's emission loop (a wavefront's), per-lane
+// steps through a static twin list, value rounds (rows, then lookahead), per-lane exact compares where the static twins are found
+constexpr uint32_t kStatWalkSparse = 43, kStatWalkDense = 44, kStatWalkEmitTrips = 45, kStatWalkTwinSteps = 46, kStatWalkRounds = 47, kStatWalkTwinFind = 48;
+constexpr uint32_t kStatWalkCands = 49;     // + 0 / 1 / 2: chunks of at most 64, of 65 .. kSparseCand, of more candidates
+// what the WAVEFRONT runs of the two per-lane loops, i.e. the longest lane's steps: of B2's bucket walk (per pass and set), of the twin chain (per trip)
+constexpr uint32_t kStatWalkFindWave = 52, kStatWalkChainWave = 53;
+#if defined(TBC_EMU)
+// (emulated build) the largest n over the lanes, added to a count: one ballot per step of the longest lane
+#define WV_STAT_WAVE_MAX(id, n) do { for (uint32_t k_ = 1u; wv::ballot((n) >= k_) != 0ull; k_++) if (lane == 0u) wv::stat((id), 1); } while (0)
+#else
+#define WV_STAT_WAVE_MAX(id, n) do { (void)(n); } while (0)
+#endif
+
+// ---- the sparse form of phase C (walk_chunk): what it is made of
+// an inclusive XOR scan over the 64 lanes, in the form of A2's popcount scan: four row steps, then the rows' totals by lane reads
+WV_DEV uint32_t xor_scan(uint32_t x, uint32_t lane) {
+  x ^= wv::row_shr0<1>(x); x ^= wv::row_shr0<2>(x); x ^= wv::row_shr0<4>(x); x ^= wv::row_shr0<8>(x);
+  const uint32_t t0 = wv::readlane(x, 15u), t1 = wv::readlane(x, 31u), t2 = wv::readlane(x, 47u);
+  return x ^ (lane >= 16u ? t0 : 0u) ^ (lane >= 32u ? t1 : 0u) ^ (lane >= 48u ? t2 : 0u);
+}
+// where a call's bit goes OFF: the front after its last (tests/emu plants 0 here and must see the tables differ)
+#ifndef TBC_WALK_OFF_AFTER
+#define TBC_WALK_OFF_AFTER 1u
+#endif
+// (the three planted mutations -- this one, TBC_WALK_TWIN_LE, TBC_WALK_NO_SELF_EXCLUSION -- exist for the emulated build only)
+#if !defined(TBC_EMU) && (defined(TBC_WALK_TWIN_LE) || defined(TBC_WALK_NO_SELF_EXCLUSION) || (TBC_WALK_OFF_AFTER != 1u))
+#error "the planted mutations of the front walk are for tests/emu (TBC_EMU) only"
+#endif
+// lane = candidate: the call (inv, ret) toggles bit `slot` ON at its first front of the chunk and OFF behind its last one.  tog: per
+// front index four words, ON low / high, OFF low / high.  No ON when it completed before the chunk, no OFF when it outlasts it.
+WV_DEV void toggle_slot(uint32_t* tog, uint32_t F_lo, uint32_t inv, uint32_t ret, uint32_t slot) {
+  if (ret < F_lo) return;
+  const uint32_t on = inv > F_lo ? inv - F_lo : 0u, offi = ret + TBC_WALK_OFF_AFTER - F_lo, bit = 1u << (slot & 31u), w = slot >> 5;
+  wv::lds_add32(&tog[on * 4u + w], bit);
+  if (ret != kInf && offi < 64u) wv::lds_add32(&tog[offi * 4u + 2u + w], bit);
+}
+// a front's four toggle words zeroed (the zero is made here: as a constant the compiler keeps it in registers over the whole run of chunks)
+WV_DEV void zero_toggles(uint32_t* tog, uint32_t lane) {
+  const uint32_t z = wv::opaque(0u);
+  *reinterpret_cast<wv::u32x4*>(tog + lane * 4u) = wv::u32x4{z, z, z, z};
+}
+WV_DEV uint32_t key_bucket(uint32_t key) { return (key * 0x9E3779B1u) >> 26; }
+#if defined(TBC_EMU)
+inline bool& emu_force_dense() { static bool f = false; return f; }      // tests/emu: the dense loop for everything
+#endif
 
 // a UNIFORM value, opaque to the optimiser: what a chunk of a run derives from the history's number is worked out again per chunk
 // instead of being kept in registers over the whole run (wv::opaque does the same for the lane number)
@@ -255,8 +327,9 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
   const uint32_t wr_last = list_order == 2u ? 0x40000000u : list_order >= 16u ? 2u * (list_order - 16u) + 1u : 0u;
   const uint32_t rk_mul = list_order >= 16u ? 2u : 1u;
   uint16_t* const perm = reinterpret_cast<uint16_t*>(aux);
+  uint32_t place[3] = {0u, 0u, 0u};                                 // candidate lane + 64 s: its place in list order
   if (by_ret) {
-    uint32_t my[3], place[3] = {0u, 0u, 0u};
+    uint32_t my[3];
     uint32_t d[3];                                                  // key - base of a live candidate inside the window, else kInf
     const uint32_t wr_ofs = list_order == 2u ? kKeyBits / 2u : wr_last, lim_other = list_order == 2u ? kKeyBits / 2u : kKeyBits;
     bool outside = false;
@@ -323,11 +396,28 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
       if (idx < NC) perm[place[s]] = (uint16_t)idx;
     }
     wv::barrier();
+  } else {
+    WV_UNROLL
+    for (int s = 0; s < 3; s++) place[s] = lane + 64u * (uint32_t)s;
   }
 
-  // ---- B. the candidates once more, one per lane (three sets): what the static twin test asks of them
+  // ---- B. the candidates once more, one per lane (three sets): what the static twin test and the sparse form's toggles ask of them
   uint32_t c_key[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, c_ret[3] = {0u, 0u, 0u};
-  if (want_tw) {
+  // The sparse form of phase C (below) or the dense loop: decided per chunk, uniformly.  The dense loop takes rows of more than 8 entries
+  // (VCAP) and a chunk of more than kSparseCand candidates (the form's round buffer lies over the end of the table).
+  bool sparse = VCAP <= 8 && NC_all <= kSparseCand;
+#if defined(TBC_EMU)
+  if (emu_force_dense()) sparse = false;
+#endif
+  // (sparse) the flag word of the lane's candidates with the place in list order in its free bits: 18..23 the place's low six bits, 9..10 its pass
+  uint32_t c_fl[kSparseSets] = {0u, 0u};
+  if (sparse) {
+    WV_UNROLL
+    for (int s = 0; s < kSparseSets; s++) {
+      const uint32_t idx = lane + 64u * (uint32_t)s;
+      if (idx < NC) c_fl[s] = cand[idx * kCandWords + 6u] | ((place[s] & 63u) << 18) | ((place[s] >> 6) << 9);
+    }
+  } else if (want_tw) {
     WV_UNROLL
     for (int s = 0; s < 3; s++) {
       const uint32_t idx = lane + 64u * (uint32_t)s;
@@ -336,6 +426,58 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
       c_ret[s] = e[1];
     }
   }
+  uint32_t* const tog = cand + kSparseCand * kCandWords;
+  uint32_t* const rcnt = tog + kTogWords;
+  // ---- B2 (sparse, twin masks).  The calls of one effect that complete in the chunk or later, chained by completion: with lane = candidate,
+  // each finds the call of its effect that completes LAST BEFORE IT (its table index, 0xFF = none).  Per set of 64 source candidates, each
+  // adds its lane's bit to the bucket of its effect key (64 buckets of two words), and every candidate steps through the few bits of its own
+  // key's bucket with the exact test.  The links then take the place of the keys in the table (word 7): phase C has no other use for a
+  // key.  An entry's twins at a front are found down the chain (phase C).
+  if constexpr (VCAP <= 8) {
+    if (sparse && want_tw) {
+      uint32_t prev[kSparseSets] = {0xFFu, 0xFFu}, prev_ret[kSparseSets] = {0u, 0u};
+      WV_UNROLL
+      for (int s = 0; s < kSparseSets; s++) {
+        const uint32_t idx = lane + 64u * (uint32_t)s;
+        if (idx < NC) { c_key[s] = cand[idx * kCandWords + 7u]; c_ret[s] = cand[idx * kCandWords + 1u]; }
+      }
+      WV_UNROLL
+      for (int sp = 0; sp < kSparseSets; sp++) {
+        if (64u * (uint32_t)sp >= NC) continue;
+        { const uint32_t z = wv::opaque(0u); tog[lane * 2u] = z; tog[lane * 2u + 1u] = z; }
+        wv::barrier();
+        if (c_key[sp] != 0xFFFFFFFFu) wv::lds_add32(&tog[key_bucket(c_key[sp]) * 2u + (lane >> 5)], 1u << (lane & 31u));
+        wv::barrier();
+        WV_UNROLL
+        for (int s = 0; s < kSparseSets; s++) {
+          uint64_t mk = 0ull;
+          if (c_key[s] != 0xFFFFFFFFu) {
+            const uint32_t hb = key_bucket(c_key[s]);
+            mk = (uint64_t)tog[hb * 2u] | ((uint64_t)tog[hb * 2u + 1u] << 32);
+          }
+          WV_STAT_WAVE_MAX(kStatWalkFindWave, (uint32_t)__builtin_popcountll(mk));
+          while (mk) {
+            const uint32_t u = 64u * (uint32_t)sp + (uint32_t)__builtin_ctzll(mk);
+            mk &= mk - 1ull;
+            const uint32_t* eu = cand + u * kCandWords;
+            const uint32_t ru = eu[1];
+            wv::stat(kStatWalkTwinFind, 1);
+#if defined(TBC_WALK_TWIN_LE)       // (planted by tests/emu: the call itself becomes its own twin; phase C stops at a link to itself)
+            if (eu[7] == c_key[s] && ru <= c_ret[s] && (prev[s] == 0xFFu || ru > prev_ret[s])) { prev[s] = u; prev_ret[s] = ru; }
+#else
+            if (eu[7] == c_key[s] && ru < c_ret[s] && (prev[s] == 0xFFu || ru > prev_ret[s])) { prev[s] = u; prev_ret[s] = ru; }
+#endif
+          }
+        }
+        wv::barrier();
+      }
+      WV_UNROLL
+      for (int s = 0; s < kSparseSets; s++) if (lane + 64u * (uint32_t)s < NC) cand[(lane + 64u * (uint32_t)s) * kCandWords + 7u] = prev[s];
+      wv::barrier();
+    }
+  }
+  if (lane == 0u) wv::stat(sparse ? kStatWalkSparse : kStatWalkDense, 1);
+  if (lane == 0u) wv::stat(kStatWalkCands + (NC_all > 64u ? 1u : 0u) + (NC_all > kSparseCand ? 1u : 0u), 1);
 
   // ---- C. lane = front
   const uint32_t F = F_lo + lane;
@@ -357,11 +499,162 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
     need = look_need(xf, xa); xprod = look_prod(xf, xa, xb);
     di = F - xinv < 255u ? F - xinv : 255u;
   }
+
+  bool dense = true;
+  if constexpr (VCAP <= 8) if (sparse) {
+    dense = false;
+    // ---- C, THE SPARSE FORM.  No loop over the candidates with lane = front: a call is open at the fronts inv .. ret, so with lane =
+    // candidate it toggles a bit ON at index max(inv, F_lo) - F_lo and OFF at ret + 1 - F_lo of a 64-entry array in LDS (toggle_slot), and
+    // with lane = front the inclusive XOR scan of ON ^ OFF over the lanes is the set of calls open at each front.  The bits are unique per
+    // (word, index) -- a slot has one call open at a time, its next call is invoked at a later rank than its last completion, a crashed
+    // call's slot is not reused -- so adding is setting; a slot whose call ends at F - 1 and whose next begins at F gets both events at F.
+    // (b) bit = process slot, a round per read-row entry present among the chunk's candidates: the scan IS the front's row entry, stored
+    // where it is made (no row in registers); the entries no round made are stored as zero afterwards
+    {
+      uint64_t* const row = rdm ? rdm + (uint64_t)F * FW : nullptr;
+      const uint32_t n_row = compact ? 6u : V;
+      uint32_t made = 0u;
+      bool pend[kSparseSets];
+      WV_UNROLL
+      for (int s = 0; s < kSparseSets; s++) pend[s] = (c_fl[s] & kCRow) != 0u;
+      for (;;) {
+        const uint64_t b0 = wv::ballot(pend[0]), b1 = NC > 64u ? wv::ballot(pend[1]) : 0ull;
+        if ((b0 | b1) == 0ull) break;
+        uint32_t v;
+        if (b0) v = wv::readlane(c_fl[0], (uint32_t)__builtin_ctzll(b0)); else v = wv::readlane(c_fl[1], (uint32_t)__builtin_ctzll(b1));
+        v = (v >> 4) & 31u;
+        if (lane == 0u) wv::stat(kStatWalkRounds, 1);
+        zero_toggles(tog, lane);
+        wv::barrier();
+        WV_UNROLL
+        for (int s = 0; s < kSparseSets; s++)
+          if (pend[s] && ((c_fl[s] >> 4) & 31u) == v) { const uint32_t* e = cand + (lane + 64u * (uint32_t)s) * kCandWords; toggle_slot(tog, F_lo, e[0], e[1], (c_fl[s] >> 12) & 63u); pend[s] = false; }
+        wv::barrier();
+        const wv::u32x4 t4 = *reinterpret_cast<const wv::u32x4*>(tog + lane * 4u);
+        const uint32_t rlo = xor_scan(t4.x ^ t4.z, lane), rhi = W > 32u ? xor_scan(t4.y ^ t4.w, lane) : 0u;
+        if (active && v < n_row) row[v] = (uint64_t)rlo | ((uint64_t)rhi << 32);
+        made |= 1u << v;
+        wv::barrier();
+      }
+      if (rdm)
+        for (uint32_t v = 0; v < n_row; v++) if (!((made >> v) & 1u) && active) row[v] = 0ull;
+    }
+    // (c) bit = process slot, a round per produced value present that some front of the chunk needs: a front takes the scan of its own
+    // `need` as its producer mask.  The same round counts, a byte per rank, the producers of the value invoked at ranks F_lo - 7 ..
+    // F_lo + 63 (candidates that completed before the chunk included; at most one per slot and rank, so a byte does not carry): a front
+    // reads the eight bytes of ranks F - 7 .. F, takes its own call out (it may produce what it needs: a cas v v) and the highest byte
+    // left that is not zero is the nearest producer.
+    {
+      static_assert(kLookahead == 8u, "a front's window of invocation ranks is eight bytes");
+      uint32_t pm_lo = 0u, pm_hi = 0u, dmin = 255u;
+      bool pend[kSparseSets];
+      WV_UNROLL
+      for (int s = 0; s < kSparseSets; s++) pend[s] = (c_fl[s] & kCLook) != 0u;
+      for (;;) {
+        const uint64_t b0 = wv::ballot(pend[0]), b1 = NC > 64u ? wv::ballot(pend[1]) : 0ull;
+        if ((b0 | b1) == 0ull) break;
+        uint32_t v;
+        if (b0) v = wv::readlane(c_fl[0], (uint32_t)__builtin_ctzll(b0)); else v = wv::readlane(c_fl[1], (uint32_t)__builtin_ctzll(b1));
+        v >>= 24;
+        const bool mine = active && need == v;
+        if (wv::ballot(mine) == 0ull) {                              // nobody needs it
+          WV_UNROLL
+          for (int s = 0; s < kSparseSets; s++) if ((c_fl[s] >> 24) == v) pend[s] = false;
+          continue;
+        }
+        if (lane == 0u) wv::stat(kStatWalkRounds, 1);
+        zero_toggles(tog, lane);
+        if (lane < kRankCntWords) rcnt[lane] = 0u;
+        wv::barrier();
+        WV_UNROLL
+        for (int s = 0; s < kSparseSets; s++)
+          if (pend[s] && (c_fl[s] >> 24) == v) {
+            const uint32_t* e = cand + (lane + 64u * (uint32_t)s) * kCandWords;
+            const uint32_t inv = e[0];
+            toggle_slot(tog, F_lo, inv, e[1], (c_fl[s] >> 12) & 63u);
+            if (inv + (kLookahead - 1u) >= F_lo) {
+              const uint32_t ri = inv + (kLookahead - 1u) - F_lo;          // (invoked before the chunk's last front: below 71)
+              wv::lds_add32(&rcnt[ri >> 2], 1u << (8u * (ri & 3u)));
+            }
+            pend[s] = false;
+          }
+        wv::barrier();
+        const wv::u32x4 t4 = *reinterpret_cast<const wv::u32x4*>(tog + lane * 4u);
+        const uint32_t slo = xor_scan(t4.x ^ t4.z, lane), shi = W > 32u ? xor_scan(t4.y ^ t4.w, lane) : 0u;
+        if (mine) {
+          pm_lo = slo; pm_hi = shi;
+          const uint32_t wb = lane >> 2, sh = 8u * (lane & 3u);
+          const uint64_t lo64 = (uint64_t)rcnt[wb] | ((uint64_t)rcnt[wb + 1u] << 32);
+          uint64_t xb = sh ? ((lo64 >> sh) | ((uint64_t)rcnt[wb + 2u] << (64u - sh))) : lo64;     // byte j: rank F - 7 + j
+#if !defined(TBC_WALK_NO_SELF_EXCLUSION)
+          if (xprod == need && di < kLookahead) xb -= 1ull << (8u * (kLookahead - 1u - di));
+#endif
+          dmin = xb ? (uint32_t)__builtin_clzll(xb) >> 3 : 255u;
+        }
+        wv::barrier();
+      }
+      if (active && look) {
+        uint64_t pm = (uint64_t)pm_lo | ((uint64_t)pm_hi << 32);
+        pm &= ~(1ull << (px & 63u));                                  // (the completing call itself, as in phase D)
+        look[(uint64_t)F * 2u] = (uint64_t)(px & 0xFFFFu) | (uint64_t)need << 16 | (uint64_t)xprod << 24 | (uint64_t)di << 32 | ((uint64_t)dmin << 40);
+        look[(uint64_t)F * 2u + 1u] = pm;
+      }
+    }
+    // (a) bit = the candidate's place in list order, listed candidates only, 64 places a pass: a front's list entries, ascending bit = list
+    // order.  The entries: each lane walks the set bits of its words, lowest first, and takes the candidate's record from the table at an address
+    // of its own; the wavefront goes on while any lane has a bit left -- the longest list of the pass, not NC.  The twin mask of an entry
+    // at front F: down the chain of its effect (B2) from the call itself, the slots of the calls open at F -- the chain is in order of
+    // completion, so it ends at the first call that completed before F.
+    WV_UNROLL
+    for (int g = 0; g < kSparseSets; g++) {
+      if (64u * (uint32_t)g >= NC) continue;
+      zero_toggles(tog, lane);
+      wv::barrier();
+      WV_UNROLL
+      for (int s = 0; s < kSparseSets; s++)
+        if ((c_fl[s] & kCList) && ((c_fl[s] >> 9) & 3u) == (uint32_t)g) { const uint32_t* e = cand + (lane + 64u * (uint32_t)s) * kCandWords; toggle_slot(tog, F_lo, e[0], e[1], (c_fl[s] >> 18) & 63u); }
+      wv::barrier();
+      const wv::u32x4 t4 = *reinterpret_cast<const wv::u32x4*>(tog + lane * 4u);
+      const uint32_t mlo = xor_scan(t4.x ^ t4.z, lane), mhi = xor_scan(t4.y ^ t4.w, lane);
+      uint64_t cur = active ? ((uint64_t)mlo | ((uint64_t)mhi << 32)) : 0ull;
+      wv::barrier();
+      WV_NOUNROLL
+      while (wv::ballot(cur != 0ull) != 0ull) {
+        if (lane == 0u) wv::stat(kStatWalkEmitTrips, 1);
+        uint32_t chain_steps = 0u;                                    // (counted for the emulated build's statistics only)
+        if (cur != 0ull) {
+          const uint32_t p = 64u * (uint32_t)g + (uint32_t)__builtin_ctzll(cur);
+          cur &= cur - 1ull;
+          const uint32_t* e = cand + (by_ret ? (uint32_t)perm[p] : p) * kCandWords;
+          OpRec o; o.op = e[2]; o.f_slot = e[3] | (e[1] == F ? kAtFront : 0u); o.a = (int32_t)e[4]; o.b = (int32_t)e[5];
+          lst[pos] = o;
+          if (twn) {
+            uint64_t tw = 0ull;
+            for (uint32_t u = e[7] & 0xFFu; u != 0xFFu;) {
+              const uint32_t* eu = cand + u * kCandWords;
+              wv::stat(kStatWalkTwinSteps, 1);
+              chain_steps++;
+              if (eu[1] < F) break;
+              if (eu[0] <= F) tw |= 1ull << ((eu[3] >> 8) & 63u);
+#if defined(TBC_WALK_TWIN_LE)
+              if ((eu[7] & 0xFFu) == u) break;
+#endif
+              u = eu[7] & 0xFFu;
+            }
+            twn[pos] = tw;
+          }
+          pos++;
+        }
+        WV_STAT_WAVE_MAX(kStatWalkChainWave, chain_steps);
+      }
+    }
+  }
+
+  if (dense) {                              // (its row and masks are registers of this block only: the sparse form holds none of them)
   wv::u32x16 r0, r1, r2, r3;                // the front's row (r1 .. r3: rows of more than 8 entries only)
   WV_UNROLL
   for (int i = 0; i < 16; i++) { r0[i] = 0u; r1[i] = 0u; r2[i] = 0u; r3[i] = 0u; }
   uint32_t pm_lo = 0u, pm_hi = 0u, dmin = 255u;
-
   WV_NOUNROLL
   for (uint32_t t = 0; t < NC; t++) {
     const uint32_t* e = cand + (by_ret ? (uint32_t)perm[t] : t) * kCandWords;
@@ -411,6 +704,20 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
       if (hit && dist < kLookahead && e[2] != x) dmin = dist < dmin ? dist : dmin;
     }
   }
+  if (active && rdm) {
+    uint64_t* row = rdm + (uint64_t)F * FW;
+    const uint32_t n_row = compact ? 6u : V;
+    store_entries<0>(r0, row, n_row);
+    if constexpr (VCAP > 8) { store_entries<1>(r1, row, n_row); store_entries<2>(r2, row, n_row); store_entries<3>(r3, row, n_row); }
+  }
+  if (active && look) {
+    uint64_t pm = (uint64_t)pm_lo | ((uint64_t)pm_hi << 32);
+    pm &= ~(1ull << (px & 63u));                                    // one call per slot is open at a front: this is the completing call itself
+    const uint64_t w0 = (uint64_t)(px & 0xFFFFu) | (uint64_t)need << 16 | (uint64_t)xprod << 24 | (uint64_t)di << 32 | ((uint64_t)dmin << 40);
+    look[(uint64_t)F * 2u] = w0;
+    look[(uint64_t)F * 2u + 1u] = pm;
+  }
+  }
 
   // ---- D. the rest of each front's record / row
   uint64_t w6 = 0ull, w7 = 0ull;
@@ -432,19 +739,9 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
     const uint32_t nl = pos - pos0, nc = A.ncr[B->off_off + Fc];
     w6 = (uint64_t)pos0 | ((uint64_t)(nl & 0xFFu) << 32) | ((uint64_t)((nl + nc) & 0xFFFFFFu) << 40);
   }
-  if (active && rdm) {
+  if (active && rdm && compact) {
     uint64_t* row = rdm + (uint64_t)F * FW;
-    const uint32_t n_row = compact ? 6u : V;
-    store_entries<0>(r0, row, n_row);
-    if constexpr (VCAP > 8) { store_entries<1>(r1, row, n_row); store_entries<2>(r2, row, n_row); store_entries<3>(r3, row, n_row); }
-    if (compact) { row[6] = w6; row[7] = w7; }
-  }
-  if (active && look) {
-    uint64_t pm = (uint64_t)pm_lo | ((uint64_t)pm_hi << 32);
-    pm &= ~(1ull << (px & 63u));                                    // one call per slot is open at a front: this is the completing call itself
-    const uint64_t w0 = (uint64_t)(px & 0xFFFFu) | (uint64_t)need << 16 | (uint64_t)xprod << 24 | (uint64_t)di << 32 | ((uint64_t)dmin << 40);
-    look[(uint64_t)F * 2u] = w0;
-    look[(uint64_t)F * 2u + 1u] = pm;
+    row[6] = w6; row[7] = w7;
   }
   return F_lo + 64u < R;
 }

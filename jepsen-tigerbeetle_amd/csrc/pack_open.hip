@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256) void open_walk_kernel(PackOpenArgs A) {
 
 // ---- the same walk with lane = front (open_walk_impl.h): up to 64 process slots, rows of up to VCAP entries
 template <int VCAP>
-__global__ __launch_bounds__(256, VCAP <= 8 ? 8 : 2) void open_walk_fronts_kernel(PackOpenArgs A) {      // (<8>: eight blocks a CU, i.e. 64 vector registers)
+__global__ __launch_bounds__(256, VCAP <= 8 ? TBC_WALK_BLOCKS : 2) void open_walk_fronts_kernel(PackOpenArgs A) {      // (<8>: TBC_WALK_BLOCKS = 8 blocks a CU, i.e. 64 vector registers; open_walk_impl.h)
   extern __shared__ __attribute__((aligned(16))) uint32_t walk_lds[];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv_ = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
