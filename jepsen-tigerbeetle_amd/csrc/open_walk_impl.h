@@ -38,6 +38,17 @@
 // chunk finds each slot's first candidate by a binary search of the slot's records, the others carry the cursor on from the chunk
 // before (phase A).  walk_wave is one chunk from nothing; both forms share the body, walk_chunk.
 //
+// walk_chunk is the setup of a chunk (struct Chunk: pointers and flags, all uniform) and one call per PHASE, each a function of its own
+// with its comment above it:
+//   A   fill_candidates     lane = slot: the slot's cursor (searched or carried), its candidates, the table in LDS
+//   A2  list_places         lane = candidate: its place in list order (places_by_counting, else places_by_compare)
+//   B   sparse_flags / dense_twin_keys      the candidates once more, one per lane, in registers
+//   B2  link_twins          (sparse, twin masks) the chain of each effect's calls by completion
+//   C   front_of            lane = front: the front's list position and the call completing there; then either
+//       sparse_read_rows, sparse_producers, sparse_lists   -- rdm rows; look records; lst / twn entries -- (rounds of toggles: open_bits)
+//       or dense_loop       the candidate loop, all three at once, the row in registers
+//   D   compact_tail        words 6 and 7 of a compact front record
+//
 // The body is written against wave_env.h like the narrow search kernel, so tests/emu runs it on the CPU (lane-accurate
 // emulator) and compares every word with tables built on the host from the definitions (tests/test_walk_emu.py: walk_wave;
 // tests/test_walk_runs_emu.py: walk_run, where the emulated build also searches and counts a carried cursor that differs;
@@ -92,10 +103,9 @@ WV_DEV uint32_t effect_key(uint32_t f, int32_t a, int32_t b) {
 static_assert(kMaxRuleValue < 0x7FFF && TBC_F_READ < 3 && TBC_F_WRITE < 3 && TBC_F_CAS < 3, "effect_key packs f and two rule values into a word, and no key has all bits set");
 static_assert(kLookNone <= 0xFFu, "the produced value shares a word with the flags");
 
-// the nine bits a compact front record keeps per rank: process slot | read kind << 6 (7 = not a read)
+// the nine bits a compact front record keeps per rank (front_rank_code), from the completing call itself
 WV_DEV uint32_t rank_code(uint32_t slot, uint32_t f, int32_t a, uint32_t vpad) {
-  const uint32_t k8 = f == TBC_F_READ ? (rdm_index(a, vpad) & 0xFFu) : 0xFFu;
-  return (slot & 63u) | ((k8 == 0xFFu ? 7u : (k8 & 7u)) << 6);
+  return front_rank_code(slot, f == TBC_F_READ ? (rdm_index(a, vpad) & 0xFFu) : 0xFFu);
 }
 
 // A front's open-read row lives in registers as u32x16 vectors (16 words = 8 entries each: entry v = words 2v, slots 0..31, and
@@ -131,7 +141,7 @@ constexpr uint32_t kStatWalkFindWave = 52, kStatWalkChainWave = 53;
 #define WV_STAT_WAVE_MAX(id, n) do { (void)(n); } while (0)
 #endif
 
-// ---- the sparse form of phase C (walk_chunk): what it is made of
+// ---- the sparse form of phase C: what it is made of
 // an inclusive XOR scan over the 64 lanes, in the form of A2's popcount scan: four row steps, then the rows' totals by lane reads
 WV_DEV uint32_t xor_scan(uint32_t x, uint32_t lane) {
   x ^= wv::row_shr0<1>(x); x ^= wv::row_shr0<2>(x); x ^= wv::row_shr0<4>(x); x ^= wv::row_shr0<8>(x);
@@ -159,6 +169,22 @@ WV_DEV void zero_toggles(uint32_t* tog, uint32_t lane) {
   const uint32_t z = wv::opaque(0u);
   *reinterpret_cast<wv::u32x4*>(tog + lane * 4u) = wv::u32x4{z, z, z, z};
 }
+// A round of the form is  zero_toggles, barrier, the candidates' toggles, then this: with lane = front, the inclusive XOR scan of ON ^ OFF
+// over the lanes -- the bits whose call is open at the lane's front, low word | high word << 32.  high: whether a bit can be in the high
+// word at all (else: one scan).  The caller puts a barrier between its last use of the round's words and the next round's zero_toggles.
+WV_DEV uint64_t open_bits(const uint32_t* tog, uint32_t lane, bool high) {
+  wv::barrier();
+  const wv::u32x4 t4 = *reinterpret_cast<const wv::u32x4*>(tog + lane * 4u);
+  const uint32_t lo = xor_scan(t4.x ^ t4.z, lane), hi = high ? xor_scan(t4.y ^ t4.w, lane) : 0u;
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+// The rounds that go by value take the value of the first candidate still pending (set 0 first, then lane order): its flag word, uniform.
+// 0 when none is pending (a pending candidate's word has at least the bit that made it pending).
+WV_DEV uint32_t next_pending(const bool (&pend)[kSparseSets], const uint32_t (&c_fl)[kSparseSets], uint32_t NC) {
+  const uint64_t b0 = wv::ballot(pend[0]), b1 = NC > 64u ? wv::ballot(pend[1]) : 0ull;
+  if ((b0 | b1) == 0ull) return 0u;
+  return b0 ? wv::readlane(c_fl[0], (uint32_t)__builtin_ctzll(b0)) : wv::readlane(c_fl[1], (uint32_t)__builtin_ctzll(b1));
+}
 WV_DEV uint32_t key_bucket(uint32_t key) { return (key * 0x9E3779B1u) >> 26; }
 #if defined(TBC_EMU)
 inline bool& emu_force_dense() { static bool f = false; return f; }      // tests/emu: the dense loop for everything
@@ -176,12 +202,12 @@ WV_DEV uint32_t opaque_uniform(uint32_t v) { asm volatile("" : "+s"(v)); return 
 // loads.  A run's later chunks come after the stores of the chunks before, and behind a store the compiler takes a load from global memory
 // through the vector memory pipe whatever its address -- a dozen vector loads and two dependent trips at the head of every chunk.
 #if defined(TBC_EMU)
-template <class T>
-WV_DEV const T* read_only(const T* p) { return p; }
+template <class T> using ro_t = const T;
 #else
-template <class T>
-WV_DEV const __attribute__((address_space(4))) T* read_only(const T* p) { return (const __attribute__((address_space(4))) T*)(uintptr_t)p; }
+template <class T> using ro_t = const __attribute__((address_space(4))) T;
 #endif
+template <class T>
+WV_DEV ro_t<T>* read_only(const T* p) { return (ro_t<T>*)(uintptr_t)p; }
 
 // the first of the slot's records [l, hi) that has not completed before ret_from (hi: the tail sentinel)
 WV_DEV uint32_t first_open(const Rec* rec, uint32_t l, uint32_t hi, uint32_t ret_from) {
@@ -192,52 +218,48 @@ WV_DEV uint32_t first_open(const Rec* rec, uint32_t l, uint32_t hi, uint32_t ret
   return l;
 }
 
-// One chunk: fronts 64 c .. 64 c + 63 of history h.  carried: the slot cursors are what the chunk before left in LDS (else: from nothing).
-// Returns whether the history has a front after this chunk.
-// VCAP: row entries kept in registers (vpad <= VCAP)
-template <int VCAP>
-WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t* lds, uint32_t lane, bool carried) {
-  const auto& A = *wv::cold(A_);            // (the arguments from the kernarg segment, per chunk: not some sixty scalar registers held over a run)
-  const auto* H = read_only(&A.hist[h]);
-  const auto* B = read_only(&A.bh[h]);
-  const uint32_t R = H->n_ret;
-  const uint32_t F_lo = c * 64u;
-  if (H->status != 0 || B->status != 0 || F_lo >= R) return false;
-  const uint32_t F_hi = F_lo + 64u < R ? F_lo + 64u : R;
-  const uint32_t W = H->n_slots;
-  const Rec* rec = A.rec + H->rec_off;
-  const uint32_t* seg = A.seg + H->seg_off;
-  const uint32_t* off = A.off + B->off_off;
-  OpRec* lst = A.lst + B->lst_off;
-  uint64_t* twn = A.twn ? A.twn + B->lst_off : nullptr;
-  const uint32_t V = A.vpad;
-  const uint32_t FW = A.front_words ? A.front_words : V;             // u64 words per front: a plain row, or a front record
-  const bool compact = A.front_compact != 0u;                        // the 64 B record, written whole (masks, list location, windows)
-  uint64_t* rdm = (A.rdm && (V || compact)) ? A.rdm + H->op_off * FW : nullptr;
-  const bool want_tw = twn != nullptr;
-  uint64_t* look = A.look ? A.look + look_off(H->op_off, h, 1u) : nullptr;
-  uint32_t* cand = lds;
-  uint32_t* aux = lds + kCandCap * kCandWords;
-  uint32_t* const cur_end = aux + kAuxWords;                         // the cursors: a lane reads what it wrote itself (no barrier)
-  uint16_t* const cur_left = reinterpret_cast<uint16_t*>(cur_end + 64);
+// What the phases of a chunk are handed by walk_chunk: where the chunk is, the history's tables, the wavefront's LDS.  All of it is UNIFORM.
+// (What a lane keeps from phase to phase -- places, keys, flag words, the list position -- are plain locals of walk_chunk passed by
+// reference, and the dense loop's row registers are locals of dense_loop: see store_entries.)
+struct Chunk {
+  ro_t<PackOpenArgs>* A;                     // (the kernarg segment, wv::cold: what a phase alone reads it takes from here where it uses it)
+  ro_t<Hist>* H;
+  ro_t<BeamHist>* B;
+  uint32_t R, F_lo, F_hi, W;                 // the history's ranks, the chunk's fronts [F_lo, F_hi), the history's slots
+  uint32_t ret_from;                         // candidates: the calls that have not completed before this rank (phase A)
+  const Rec* rec; const uint32_t* seg; const uint32_t* off;
+  OpRec* lst; uint64_t* twn;                 // twn: null = no twin masks
+  bool want_tw;
+  uint32_t V, FW;                            // row entries; u64 words per front: a plain row, or a front record
+  bool compact;                              // the 64 B record, written whole (masks, list location, windows)
+  uint64_t* rdm; uint64_t* look;             // null = no rows / no lookahead records
+  uint32_t *cand, *aux;                      // LDS: the candidate table; the scratch words (scans, A2's key map, D's rank codes)
+  uint16_t* perm;                            //      over aux: the table index of the candidate at each place in list order
+  uint32_t* cur_end; uint16_t* cur_left;     //      the cursors: a lane reads what it wrote itself (no barrier)
+  uint32_t *tog, *rcnt;                      //      the sparse form's round buffer, over the end of the table
+};
 
-  // ---- A. lane = process slot: the slot's candidates are consecutive records -- from the first that has not completed before
-  // F_lo (lookahead: F_lo - 7, for the producer distance) to the last invoked before the chunk's last front.
-  // The records of a slot are in order of invocation AND of completion, and the next chunk's ret_from is no smaller: its first
-  // candidate is this chunk's first plus those of this chunk's candidates that complete before the next ret_from (counted where
-  // the table is filled), and the record after this chunk's last candidate -- invoked at F_hi or later, so completing there or
-  // later -- is where the next chunk's scan of invocation ranks goes on.  Only a run's first chunk searches.  (Of a slot's candidates
-  // at most eight are the next chunk's as well: a slot has one call open at a time, so they complete at ranks of their own from
-  // F_lo + 64 - 7 on, and only the last of them at F_lo + 64 or later.)
-  // The scan loads four ranks a trip and looks at none behind the first that ends it, which the slot's tail sentinel (inv = kInf) does at
-  // the latest: the indices are kept inside the HISTORY's records, not the slot's.
-  const uint32_t ret_from = look ? (F_lo >= kLookahead - 1u ? F_lo - (kLookahead - 1u) : 0u) : F_lo;
-  const uint32_t ret_from_next = look ? F_lo + 64u - (kLookahead - 1u) : F_lo + 64u;
+// ---- A. lane = process slot: the slot's candidates are consecutive records -- from the first that has not completed before
+// F_lo (lookahead: F_lo - 7, for the producer distance) to the last invoked before the chunk's last front.
+// The records of a slot are in order of invocation AND of completion, and the next chunk's ret_from is no smaller: its first
+// candidate is this chunk's first plus those of this chunk's candidates that complete before the next ret_from (counted where
+// the table is filled), and the record after this chunk's last candidate -- invoked at F_hi or later, so completing there or
+// later -- is where the next chunk's scan of invocation ranks goes on.  Only a run's first chunk searches.  (Of a slot's candidates
+// at most eight are the next chunk's as well: a slot has one call open at a time, so they complete at ranks of their own from
+// F_lo + 64 - 7 on, and only the last of them at F_lo + 64 or later.)
+// The scan loads four ranks a trip and looks at none behind the first that ends it, which the slot's tail sentinel (inv = kInf) does at
+// the latest: the indices are kept inside the HISTORY's records, not the slot's.
+// Returns the chunk's candidates, all slots'; the table holds the first kCandCap of them (never more: see the header).
+WV_DEV uint32_t fill_candidates(const Chunk& K, uint32_t lane, bool carried) {
+  const Rec* rec = K.rec;
+  const uint32_t* seg = K.seg;
+  const uint32_t F_lo = K.F_lo, F_hi = K.F_hi, W = K.W, V = K.V, ret_from = K.ret_from;
+  const uint32_t ret_from_next = K.look ? F_lo + 64u - (kLookahead - 1u) : F_lo + 64u;
   uint32_t lo = 0, k = 0;
   if (lane == 0u) wv::stat(carried ? kStatWalkCarried : kStatWalkSearch, 1);
   if (lane < W) {
     uint32_t i;
-    if (carried) { i = cur_end[lane]; lo = i - cur_left[lane]; }
+    if (carried) { i = K.cur_end[lane]; lo = i - K.cur_left[lane]; }
     else {
       lo = first_open(rec, seg[lane] + 1u, seg[lane + 1] - 1u, ret_from);      // (up to the slot's tail sentinel: inv = ret = kInf)
       i = lo;
@@ -264,15 +286,14 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
   // where each slot's candidates start: inclusive scan of k over the lanes (through LDS)
   uint32_t incl = k;
   for (uint32_t d = 1; d < 64u; d <<= 1) {
-    aux[lane] = incl;
+    K.aux[lane] = incl;
     wv::barrier();
-    const uint32_t add = lane >= d ? aux[lane - d] : 0u;
+    const uint32_t add = lane >= d ? K.aux[lane - d] : 0u;
     wv::barrier();
     incl += add;
   }
   const uint32_t base = incl - k;
   const uint32_t NC_all = wv::readlane(incl, 63u);
-  const uint32_t NC = NC_all < kCandCap ? NC_all : kCandCap;      // (never more: see the header)
   uint32_t gone = 0;                                                // of the slot's candidates: completed before the next chunk's ret_from
   for (uint32_t j = 0; j < k; j++) {
     const Rec r = rec[lo + j];
@@ -280,384 +301,389 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
     if (base + j < kCandCap) {
       const bool live = (r.cls & 2u) != 0u, isread = (r.cls & 16u) != 0u, wc = (r.cls & 8u) != 0u;
       const bool in_chunk = r.ret_rank >= F_lo;                     // (else: completed just before the chunk, a producer only)
-      const bool listed = live && in_chunk && !(A.branch_lists && isread);
+      const bool listed = live && in_chunk && !(K.A->branch_lists && isread);
       const uint32_t vi = rdm_index(r.a, V);
       uint32_t fl = (lane << 12) | (r.prod << 24);
       if (listed) fl |= kCList;
-      if (listed && wc && want_tw) fl |= kCTwin;
-      if (live && in_chunk && isread && rdm && V && (vi != 0u || r.a == TBC_NIL)) fl |= kCRow | (vi << 4);
-      if (look && (r.cls & 6u) && r.prod != kLookNone) fl |= kCLook;
-      uint32_t* e = cand + (base + j) * kCandWords;
+      if (listed && wc && K.want_tw) fl |= kCTwin;
+      if (live && in_chunk && isread && K.rdm && V && (vi != 0u || r.a == TBC_NIL)) fl |= kCRow | (vi << 4);
+      if (K.look && (r.cls & 6u) && r.prod != kLookNone) fl |= kCLook;
+      uint32_t* e = K.cand + (base + j) * kCandWords;
       e[0] = r.inv_rank; e[1] = r.ret_rank; e[2] = r.opidx; e[3] = r.f | (lane << 8);
       e[4] = (uint32_t)r.a; e[5] = (uint32_t)r.b; e[6] = fl;
       e[7] = (live && wc && in_chunk) ? effect_key(r.f, r.a, r.b) : 0xFFFFFFFFu;
     }
   }
-  cur_end[lane] = lo + k; cur_left[lane] = (uint16_t)(k - gone);
+  K.cur_end[lane] = lo + k; K.cur_left[lane] = (uint16_t)(k - gone);
   wv::barrier();
+  return NC_all;
+}
 
-  // ---- A2. list_order 1: the loop below takes the candidates in order of completion (then every front's list comes out in that
-  // order: a front's entries are appended as the loop meets its members).  Candidate i's place = the candidates that complete before it
-  // (ties -- crashed calls, ret = kInf, which are in no list -- by table position); the places as 16-bit words over the scan's scratch.
-  // list_order 2: in order of completion with the :write calls after everything else -- the search takes a config's candidates last to
-  // first and pops the last child first, so a :cas the state allows NOW is tried before a :write, which the state always allows
-  // (oracle/wgl_beam.c list order 4: at 19 calls in flight a quarter fewer rounds again than plain completion order).  The key: the
-  // completion rank plus 2^30 for a :write (ranks are below 2^30).
-  // list_order 16 + W: a :write takes the place of a call completing W ranks later (the soft form of the same preference; keys are doubled
-  // ranks, a :write's odd: after the call it ties with) -- W = 16 .. 24 is the best of the scan at 6, 19 and 32 calls in flight (oracle list
-  // order 16 + W: at 19 in flight 19 - 22k rounds a history against 28k writes last, 59k plain completion order).  Any key gives a
-  // permutation: a place is the count of smaller keys, ties by table position.
-  // The keys are made UNIQUE so that a place is one compare per pair: completion ranks are (live calls), and so are ranks + 2^30 for
-  // the writes and doubled ranks with the writes' odd; the only ties of the definition are among crashed calls (ret = kInf), which are in
-  // no list -- and what the loop does for an unlisted candidate (a bit of a read row, of the lookahead mask, the producer distance)
-  // does not depend on when it meets it: they take keys above every live one, by table position.  The keys stay in registers, one
-  // candidate per lane (three sets); candidate j's key reaches the lanes by a lane read (j is uniform), and every lane counts the
-  // smaller keys for each of its candidates: 1 + 2 vector instructions per set instead of a dozen with two LDS reads.  That is
-  // NC x 3 .. 5 instructions a chunk, and it is the fallback now:
-  //
-  // BY COUNTING.  A live candidate completes at ret_from or later (phase A's search), and all but a slot's last one before F_hi: the live
-  // keys sit in a window above ret_from's that is a few hundred wide unless a call stays open for hundreds of ranks.  Key - base is then a
-  // bit of a kKeyBits-bit map in LDS (the keys are unique: adding the bit is setting it), 32 lanes prefix the words' popcounts, and a
-  // place is the bits below the candidate's own; the crashed calls follow the live ones by table position (ballots).  list_order 2 is
-  // two windows of half the bits, the writes' after the others'.  A chunk with a live key outside its window -- decided per chunk, so
-  // this covers a race's per-history order_of and any W -- takes the compare loop; so does a list_order whose write offset alone
-  // exceeds the window.
-  const uint32_t list_order = A.order_of ? A.order_of[h] : A.list_order;          // (the history's own order, if the batch says one)
-  const bool by_ret = list_order != 0u;
-  const uint32_t wr_last = list_order == 2u ? 0x40000000u : list_order >= 16u ? 2u * (list_order - 16u) + 1u : 0u;
-  const uint32_t rk_mul = list_order >= 16u ? 2u : 1u;
-  uint16_t* const perm = reinterpret_cast<uint16_t*>(aux);
-  uint32_t place[3] = {0u, 0u, 0u};                                 // candidate lane + 64 s: its place in list order
-  if (by_ret) {
-    uint32_t my[3];
-    uint32_t d[3];                                                  // key - base of a live candidate inside the window, else kInf
-    const uint32_t wr_ofs = list_order == 2u ? kKeyBits / 2u : wr_last, lim_other = list_order == 2u ? kKeyBits / 2u : kKeyBits;
-    bool outside = false;
-    WV_UNROLL
-    for (int s = 0; s < 3; s++) {
-      const uint32_t idx = lane + 64u * (uint32_t)s;
-      const uint32_t* e = cand + (idx < NC ? idx : 0u) * kCandWords;
-      const uint32_t rt = e[1];
-      const bool wr = (e[3] & 0xFFu) == TBC_F_WRITE;
-      my[s] = idx >= NC ? 0xFFFFFFFFu : rt == kInf ? (0xFFFFFF00u | idx) : rt * rk_mul + (wr ? wr_last : 0u);
-      const bool live = idx < NC && rt != kInf;
-      const uint32_t x = rt - ret_from;                             // (a live call's: below 2^30)
-      const bool inside = x < kKeyBits && x * rk_mul + (wr ? wr_ofs : 0u) < (wr ? kKeyBits : lim_other);
-      d[s] = (live && inside) ? x * rk_mul + (wr ? wr_ofs : 0u) : kInf;
-      outside = outside || (live && !inside);
-    }
-    const uint32_t n0 = NC < 64u ? NC : 64u, n1 = NC <= 64u ? 0u : (NC < 128u ? NC - 64u : 64u), n2 = NC <= 128u ? 0u : NC - 128u;
-    if (wr_ofs < kKeyBits && wv::ballot(outside) == 0ull) {
-      if (lane < kKeyWords) aux[lane] = 0u;
-      wv::barrier();
-      WV_UNROLL
-      for (int s = 0; s < 3; s++) if (d[s] != kInf) wv::lds_add32(&aux[d[s] >> 5], 1u << (d[s] & 31u));
-      wv::barrier();
-      const uint32_t wc = lane < kKeyWords ? (uint32_t)__builtin_popcount(aux[lane]) : 0u;
-      uint32_t y = wc;                                              // inclusive scan over lanes 0 .. 31: two rows of 16
-      y += wv::row_shr0<1>(y); y += wv::row_shr0<2>(y); y += wv::row_shr0<4>(y); y += wv::row_shr0<8>(y);
-      const uint32_t row0 = wv::readlane(y, 15u);
-      y += lane >= 16u ? row0 : 0u;
-      const uint32_t n_live = wv::readlane(y, kKeyWords - 1u);
-      if (lane < kKeyWords) aux[kKeyWords + lane] = y - wc;
-      // the crashed candidates (in no list): after the live ones, by table position
-      const uint64_t below = (1ull << lane) - 1ull;
-      uint32_t cr_before = n_live;
-      WV_UNROLL
-      for (int s = 0; s < 3; s++) {
-        const uint32_t idx = lane + 64u * (uint32_t)s;
-        const uint64_t cr = wv::ballot(idx < NC && d[s] == kInf);
-        if (d[s] == kInf) place[s] = cr_before + (uint32_t)__builtin_popcountll(cr & below);
-        cr_before += (uint32_t)__builtin_popcountll(cr);
-      }
-      wv::barrier();
-      WV_UNROLL
-      for (int s = 0; s < 3; s++)
-        if (d[s] != kInf) place[s] = aux[kKeyWords + (d[s] >> 5)] + (uint32_t)__builtin_popcount(aux[d[s] >> 5] & ((1u << (d[s] & 31u)) - 1u));
-      wv::barrier();                                                // (the places go over the words of the map)
-    } else if (NC <= 64u) {
-      for (uint32_t j = 0; j < n0; j++) place[0] += wv::readlane(my[0], j) < my[0] ? 1u : 0u;
-    } else if (NC <= 128u) {
-      for (uint32_t j = 0; j < n0; j++) { const uint32_t kj = wv::readlane(my[0], j); place[0] += kj < my[0] ? 1u : 0u; place[1] += kj < my[1] ? 1u : 0u; }
-      for (uint32_t j = 0; j < n1; j++) { const uint32_t kj = wv::readlane(my[1], j); place[0] += kj < my[0] ? 1u : 0u; place[1] += kj < my[1] ? 1u : 0u; }
-    } else {
-      WV_UNROLL
-      for (int s2 = 0; s2 < 3; s2++) {
-        const uint32_t cnt = s2 == 0 ? n0 : s2 == 1 ? n1 : n2;
-        for (uint32_t j = 0; j < cnt; j++) {
-          const uint32_t kj = wv::readlane(my[s2], j);
-          place[0] += kj < my[0] ? 1u : 0u; place[1] += kj < my[1] ? 1u : 0u; place[2] += kj < my[2] ? 1u : 0u;
-        }
-      }
-    }
-    WV_UNROLL
-    for (int s = 0; s < 3; s++) {
-      const uint32_t idx = lane + 64u * (uint32_t)s;
-      if (idx < NC) perm[place[s]] = (uint16_t)idx;
-    }
-    wv::barrier();
+// ---- A2. list_order 1: phase C takes the candidates in order of completion (then every front's list comes out in that
+// order: a front's entries are appended as the loop meets its members).  Candidate i's place = the candidates that complete before it
+// (ties -- crashed calls, ret = kInf, which are in no list -- by table position); the places as 16-bit words over the scan's scratch.
+// list_order 2: in order of completion with the :write calls after everything else -- the search takes a config's candidates last to
+// first and pops the last child first, so a :cas the state allows NOW is tried before a :write, which the state always allows
+// (oracle/wgl_beam.c list order 4: at 19 calls in flight a quarter fewer rounds again than plain completion order).  The key: the
+// completion rank plus 2^30 for a :write (ranks are below 2^30).
+// list_order 16 + W: a :write takes the place of a call completing W ranks later (the soft form of the same preference; keys are doubled
+// ranks, a :write's odd: after the call it ties with) -- W = 16 .. 24 is the best of the scan at 6, 19 and 32 calls in flight (oracle list
+// order 16 + W: at 19 in flight 19 - 22k rounds a history against 28k writes last, 59k plain completion order).  Any key gives a
+// permutation: a place is the count of smaller keys, ties by table position.
+// The keys are made UNIQUE so that a place is one compare per pair: completion ranks are (live calls), and so are ranks + 2^30 for
+// the writes and doubled ranks with the writes' odd; the only ties of the definition are among crashed calls (ret = kInf), which are in
+// no list -- and what phase C does for an unlisted candidate (a bit of a read row, of the lookahead mask, the producer distance)
+// does not depend on when it meets it: they take keys above every live one, by table position.
+//
+// places_by_compare, the fallback.  The keys stay in registers, one candidate per lane (three sets); candidate j's key reaches the lanes by
+// a lane read (j is uniform), and every lane counts the smaller keys for each of its candidates: 1 + 2 vector instructions per set instead
+// of a dozen with two LDS reads.  That is NC x 3 .. 5 instructions a chunk.  place: zero on entry
+WV_DEV void places_by_compare(uint32_t NC, const uint32_t (&my)[3], uint32_t (&place)[3]) {
+  if (NC <= 64u) {
+    for (uint32_t j = 0; j < NC; j++) place[0] += wv::readlane(my[0], j) < my[0] ? 1u : 0u;
+  } else if (NC <= 128u) {
+    for (uint32_t j = 0; j < 64u; j++) { const uint32_t kj = wv::readlane(my[0], j); place[0] += kj < my[0] ? 1u : 0u; place[1] += kj < my[1] ? 1u : 0u; }
+    for (uint32_t j = 0; j < NC - 64u; j++) { const uint32_t kj = wv::readlane(my[1], j); place[0] += kj < my[0] ? 1u : 0u; place[1] += kj < my[1] ? 1u : 0u; }
   } else {
     WV_UNROLL
-    for (int s = 0; s < 3; s++) place[s] = lane + 64u * (uint32_t)s;
+    for (int s2 = 0; s2 < 3; s2++) {
+      const uint32_t cnt = s2 < 2 ? 64u : NC - 128u;
+      for (uint32_t j = 0; j < cnt; j++) {
+        const uint32_t kj = wv::readlane(my[s2], j);
+        place[0] += kj < my[0] ? 1u : 0u; place[1] += kj < my[1] ? 1u : 0u; place[2] += kj < my[2] ? 1u : 0u;
+      }
+    }
   }
+}
+// places_by_counting.  A live candidate completes at ret_from or later (phase A's search), and all but a slot's last one before F_hi: the live
+// keys sit in a window above ret_from's that is a few hundred wide unless a call stays open for hundreds of ranks.  Key - base is then a
+// bit of a kKeyBits-bit map in LDS (the keys are unique: adding the bit is setting it), 32 lanes prefix the words' popcounts, and a
+// place is the bits below the candidate's own; the crashed calls follow the live ones by table position (ballots).  list_order 2 is
+// two windows of half the bits, the writes' after the others'.  A chunk with a live key outside its window -- decided per chunk, so
+// this covers a race's per-history order_of and any W -- takes the compare loop; so does a list_order whose write offset alone
+// exceeds the window.
+// d: key - base of a live candidate (inside the window, all of them), else kInf
+WV_DEV void places_by_counting(uint32_t* aux, uint32_t NC, uint32_t lane, const uint32_t (&d)[3], uint32_t (&place)[3]) {
+  if (lane < kKeyWords) aux[lane] = 0u;
+  wv::barrier();
+  WV_UNROLL
+  for (int s = 0; s < 3; s++) if (d[s] != kInf) wv::lds_add32(&aux[d[s] >> 5], 1u << (d[s] & 31u));
+  wv::barrier();
+  const uint32_t wc = lane < kKeyWords ? (uint32_t)__builtin_popcount(aux[lane]) : 0u;
+  uint32_t y = wc;                                              // inclusive scan over lanes 0 .. 31: two rows of 16
+  y += wv::row_shr0<1>(y); y += wv::row_shr0<2>(y); y += wv::row_shr0<4>(y); y += wv::row_shr0<8>(y);
+  const uint32_t row0 = wv::readlane(y, 15u);
+  y += lane >= 16u ? row0 : 0u;
+  const uint32_t n_live = wv::readlane(y, kKeyWords - 1u);
+  if (lane < kKeyWords) aux[kKeyWords + lane] = y - wc;
+  // the crashed candidates (in no list): after the live ones, by table position
+  const uint64_t below = (1ull << lane) - 1ull;
+  uint32_t cr_before = n_live;
+  WV_UNROLL
+  for (int s = 0; s < 3; s++) {
+    const uint32_t idx = lane + 64u * (uint32_t)s;
+    const uint64_t cr = wv::ballot(idx < NC && d[s] == kInf);
+    if (d[s] == kInf) place[s] = cr_before + (uint32_t)__builtin_popcountll(cr & below);
+    cr_before += (uint32_t)__builtin_popcountll(cr);
+  }
+  wv::barrier();
+  WV_UNROLL
+  for (int s = 0; s < 3; s++)
+    if (d[s] != kInf) place[s] = aux[kKeyWords + (d[s] >> 5)] + (uint32_t)__builtin_popcount(aux[d[s] >> 5] & ((1u << (d[s] & 31u)) - 1u));
+  wv::barrier();                                                // (the places go over the words of the map)
+}
+// list_places (list_order != 0; else the places are the table's and there is no perm).  place[s]: the place in list order of candidate
+// lane + 64 s; K.perm: the candidate at each place
+WV_DEV void list_places(const Chunk& K, uint32_t NC, uint32_t lane, uint32_t list_order, uint32_t (&place)[3]) {
+  const uint32_t wr_last = list_order == 2u ? 0x40000000u : list_order >= 16u ? 2u * (list_order - 16u) + 1u : 0u;
+  const uint32_t rk_mul = list_order >= 16u ? 2u : 1u;
+  const uint32_t wr_ofs = list_order == 2u ? kKeyBits / 2u : wr_last, lim_other = list_order == 2u ? kKeyBits / 2u : kKeyBits;
+  uint32_t my[3];                                                   // the key
+  uint32_t d[3];                                                    // key - base of a live candidate inside the window, else kInf
+  bool outside = false;
+  WV_UNROLL
+  for (int s = 0; s < 3; s++) {
+    const uint32_t idx = lane + 64u * (uint32_t)s;
+    const uint32_t* e = K.cand + (idx < NC ? idx : 0u) * kCandWords;
+    const uint32_t rt = e[1];
+    const bool wr = (e[3] & 0xFFu) == TBC_F_WRITE;
+    my[s] = idx >= NC ? 0xFFFFFFFFu : rt == kInf ? (0xFFFFFF00u | idx) : rt * rk_mul + (wr ? wr_last : 0u);
+    const bool live = idx < NC && rt != kInf;
+    const uint32_t x = rt - K.ret_from;                             // (a live call's: below 2^30)
+    const bool inside = x < kKeyBits && x * rk_mul + (wr ? wr_ofs : 0u) < (wr ? kKeyBits : lim_other);
+    d[s] = (live && inside) ? x * rk_mul + (wr ? wr_ofs : 0u) : kInf;
+    outside = outside || (live && !inside);
+    place[s] = 0u;
+  }
+  if (wr_ofs < kKeyBits && wv::ballot(outside) == 0ull) places_by_counting(K.aux, NC, lane, d, place);
+  else places_by_compare(NC, my, place);
+  WV_UNROLL
+  for (int s = 0; s < 3; s++) {
+    const uint32_t idx = lane + 64u * (uint32_t)s;
+    if (idx < NC) K.perm[place[s]] = (uint16_t)idx;
+  }
+  wv::barrier();
+}
 
-  // ---- B. the candidates once more, one per lane (three sets): what the static twin test and the sparse form's toggles ask of them
-  uint32_t c_key[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, c_ret[3] = {0u, 0u, 0u};
-  // The sparse form of phase C (below) or the dense loop: decided per chunk, uniformly.  The dense loop takes rows of more than 8 entries
-  // (VCAP) and a chunk of more than kSparseCand candidates (the form's round buffer lies over the end of the table).
-  bool sparse = VCAP <= 8 && NC_all <= kSparseCand;
-#if defined(TBC_EMU)
-  if (emu_force_dense()) sparse = false;
-#endif
-  // (sparse) the flag word of the lane's candidates with the place in list order in its free bits: 18..23 the place's low six bits, 9..10 its pass
-  uint32_t c_fl[kSparseSets] = {0u, 0u};
-  if (sparse) {
+// ---- B. the candidates once more, one per lane: what the sparse form's toggles (two sets) / the dense loop's static twin test (three) ask of them
+// (sparse) the flag word of the lane's candidates with the place in list order in its free bits: 18..23 the place's low six bits, 9..10 its pass
+WV_DEV void sparse_flags(const Chunk& K, uint32_t NC, uint32_t lane, const uint32_t (&place)[3], uint32_t (&c_fl)[kSparseSets]) {
+  WV_UNROLL
+  for (int s = 0; s < kSparseSets; s++) {
+    const uint32_t idx = lane + 64u * (uint32_t)s;
+    if (idx < NC) c_fl[s] = K.cand[idx * kCandWords + 6u] | ((place[s] & 63u) << 18) | ((place[s] >> 6) << 9);
+  }
+}
+// (dense, twin masks) the effect key and the completion rank
+WV_DEV void dense_twin_keys(const Chunk& K, uint32_t NC, uint32_t lane, uint32_t (&c_key)[3], uint32_t (&c_ret)[3]) {
+  WV_UNROLL
+  for (int s = 0; s < 3; s++) {
+    const uint32_t idx = lane + 64u * (uint32_t)s;
+    const uint32_t* e = K.cand + (idx < NC ? idx : 0u) * kCandWords;
+    c_key[s] = idx < NC ? e[7] : 0xFFFFFFFFu;
+    c_ret[s] = e[1];
+  }
+}
+
+// ---- B2 (sparse, twin masks).  The calls of one effect that complete in the chunk or later, chained by completion: with lane = candidate,
+// each finds the call of its effect that completes LAST BEFORE IT (its table index, 0xFF = none).  Per set of 64 source candidates, each
+// adds its lane's bit to the bucket of its effect key (64 buckets of two words), and every candidate steps through the few bits of its own
+// key's bucket with the exact test.  The links then take the place of the keys in the table (word 7): phase C has no other use for a
+// key.  An entry's twins at a front are found down the chain (sparse_lists).
+// c_key, c_ret: two sets of the registers dense_twin_keys fills for the dense loop, which a chunk on the sparse form does not run
+WV_DEV void link_twins(const Chunk& K, uint32_t NC, uint32_t lane, uint32_t (&c_key)[3], uint32_t (&c_ret)[3]) {
+  uint32_t* const cand = K.cand;
+  uint32_t* const tog = K.tog;
+  uint32_t prev[kSparseSets] = {0xFFu, 0xFFu}, prev_ret[kSparseSets] = {0u, 0u};
+  WV_UNROLL
+  for (int s = 0; s < kSparseSets; s++) {
+    const uint32_t idx = lane + 64u * (uint32_t)s;
+    if (idx < NC) { c_key[s] = cand[idx * kCandWords + 7u]; c_ret[s] = cand[idx * kCandWords + 1u]; }
+  }
+  WV_UNROLL
+  for (int sp = 0; sp < kSparseSets; sp++) {
+    if (64u * (uint32_t)sp >= NC) continue;
+    { const uint32_t z = wv::opaque(0u); tog[lane * 2u] = z; tog[lane * 2u + 1u] = z; }
+    wv::barrier();
+    if (c_key[sp] != 0xFFFFFFFFu) wv::lds_add32(&tog[key_bucket(c_key[sp]) * 2u + (lane >> 5)], 1u << (lane & 31u));
+    wv::barrier();
     WV_UNROLL
     for (int s = 0; s < kSparseSets; s++) {
-      const uint32_t idx = lane + 64u * (uint32_t)s;
-      if (idx < NC) c_fl[s] = cand[idx * kCandWords + 6u] | ((place[s] & 63u) << 18) | ((place[s] >> 6) << 9);
-    }
-  } else if (want_tw) {
-    WV_UNROLL
-    for (int s = 0; s < 3; s++) {
-      const uint32_t idx = lane + 64u * (uint32_t)s;
-      const uint32_t* e = cand + (idx < NC ? idx : 0u) * kCandWords;
-      c_key[s] = idx < NC ? e[7] : 0xFFFFFFFFu;
-      c_ret[s] = e[1];
-    }
-  }
-  uint32_t* const tog = cand + kSparseCand * kCandWords;
-  uint32_t* const rcnt = tog + kTogWords;
-  // ---- B2 (sparse, twin masks).  The calls of one effect that complete in the chunk or later, chained by completion: with lane = candidate,
-  // each finds the call of its effect that completes LAST BEFORE IT (its table index, 0xFF = none).  Per set of 64 source candidates, each
-  // adds its lane's bit to the bucket of its effect key (64 buckets of two words), and every candidate steps through the few bits of its own
-  // key's bucket with the exact test.  The links then take the place of the keys in the table (word 7): phase C has no other use for a
-  // key.  An entry's twins at a front are found down the chain (phase C).
-  if constexpr (VCAP <= 8) {
-    if (sparse && want_tw) {
-      uint32_t prev[kSparseSets] = {0xFFu, 0xFFu}, prev_ret[kSparseSets] = {0u, 0u};
-      WV_UNROLL
-      for (int s = 0; s < kSparseSets; s++) {
-        const uint32_t idx = lane + 64u * (uint32_t)s;
-        if (idx < NC) { c_key[s] = cand[idx * kCandWords + 7u]; c_ret[s] = cand[idx * kCandWords + 1u]; }
+      uint64_t mk = 0ull;
+      if (c_key[s] != 0xFFFFFFFFu) {
+        const uint32_t hb = key_bucket(c_key[s]);
+        mk = (uint64_t)tog[hb * 2u] | ((uint64_t)tog[hb * 2u + 1u] << 32);
       }
-      WV_UNROLL
-      for (int sp = 0; sp < kSparseSets; sp++) {
-        if (64u * (uint32_t)sp >= NC) continue;
-        { const uint32_t z = wv::opaque(0u); tog[lane * 2u] = z; tog[lane * 2u + 1u] = z; }
-        wv::barrier();
-        if (c_key[sp] != 0xFFFFFFFFu) wv::lds_add32(&tog[key_bucket(c_key[sp]) * 2u + (lane >> 5)], 1u << (lane & 31u));
-        wv::barrier();
-        WV_UNROLL
-        for (int s = 0; s < kSparseSets; s++) {
-          uint64_t mk = 0ull;
-          if (c_key[s] != 0xFFFFFFFFu) {
-            const uint32_t hb = key_bucket(c_key[s]);
-            mk = (uint64_t)tog[hb * 2u] | ((uint64_t)tog[hb * 2u + 1u] << 32);
-          }
-          WV_STAT_WAVE_MAX(kStatWalkFindWave, (uint32_t)__builtin_popcountll(mk));
-          while (mk) {
-            const uint32_t u = 64u * (uint32_t)sp + (uint32_t)__builtin_ctzll(mk);
-            mk &= mk - 1ull;
-            const uint32_t* eu = cand + u * kCandWords;
-            const uint32_t ru = eu[1];
-            wv::stat(kStatWalkTwinFind, 1);
-#if defined(TBC_WALK_TWIN_LE)       // (planted by tests/emu: the call itself becomes its own twin; phase C stops at a link to itself)
-            if (eu[7] == c_key[s] && ru <= c_ret[s] && (prev[s] == 0xFFu || ru > prev_ret[s])) { prev[s] = u; prev_ret[s] = ru; }
+      WV_STAT_WAVE_MAX(kStatWalkFindWave, (uint32_t)__builtin_popcountll(mk));
+      while (mk) {
+        const uint32_t u = 64u * (uint32_t)sp + (uint32_t)__builtin_ctzll(mk);
+        mk &= mk - 1ull;
+        const uint32_t* eu = cand + u * kCandWords;
+        const uint32_t ru = eu[1];
+        wv::stat(kStatWalkTwinFind, 1);
+#if defined(TBC_WALK_TWIN_LE)       // (planted by tests/emu: the call itself becomes its own twin; sparse_lists stops at a link to itself)
+        if (eu[7] == c_key[s] && ru <= c_ret[s] && (prev[s] == 0xFFu || ru > prev_ret[s])) { prev[s] = u; prev_ret[s] = ru; }
 #else
-            if (eu[7] == c_key[s] && ru < c_ret[s] && (prev[s] == 0xFFu || ru > prev_ret[s])) { prev[s] = u; prev_ret[s] = ru; }
+        if (eu[7] == c_key[s] && ru < c_ret[s] && (prev[s] == 0xFFu || ru > prev_ret[s])) { prev[s] = u; prev_ret[s] = ru; }
 #endif
-          }
-        }
-        wv::barrier();
       }
-      WV_UNROLL
-      for (int s = 0; s < kSparseSets; s++) if (lane + 64u * (uint32_t)s < NC) cand[(lane + 64u * (uint32_t)s) * kCandWords + 7u] = prev[s];
-      wv::barrier();
     }
+    wv::barrier();
   }
-  if (lane == 0u) wv::stat(sparse ? kStatWalkSparse : kStatWalkDense, 1);
-  if (lane == 0u) wv::stat(kStatWalkCands + (NC_all > 64u ? 1u : 0u) + (NC_all > kSparseCand ? 1u : 0u), 1);
+  WV_UNROLL
+  for (int s = 0; s < kSparseSets; s++) if (lane + 64u * (uint32_t)s < NC) cand[(lane + 64u * (uint32_t)s) * kCandWords + 7u] = prev[s];
+  wv::barrier();
+}
 
-  // ---- C. lane = front
-  const uint32_t F = F_lo + lane;
-  const bool active = F < F_hi;
-  const uint32_t Fc = active ? F : F_hi - 1u;                       // (loads of the idle lanes of the last chunk stay in range)
-  const uint32_t pos0 = off[Fc];
-  uint32_t pos = pos0;
-  const uint32_t px = A.ret_slot[H->ret_off + Fc];
-  uint32_t need = kLookNone, xprod = kLookNone, di = 0, x = 0, xf = kFNone;
-  int32_t xa = 0;
-  if (look || compact) {     // the call completing at this front, from the op columns (pack_kernel copied the records from them)
-    x = A.ret_op[H->ret_off + Fc];
-    xf = A.f[H->op_off + x];
-    xa = A.a[H->op_off + x];
+// ---- C. lane = front.  What a lane knows of its front before it looks at a candidate, read only from here on: where its list starts, and
+// the call completing there, from the op columns (pack_kernel copied the records from them) -- its slot; what it needs, produces and how
+// long it has been open (lookahead); its function and argument (compact records).  Fc: the front the idle lanes of the last chunk load from.
+struct Front {
+  uint32_t F, Fc; bool active;
+  uint32_t pos0, px, need, xprod, di, x, xf; int32_t xa;
+};
+WV_DEV Front front_of(const Chunk& K, uint32_t lane) {
+  const auto& A = *K.A;
+  const auto* H = K.H;
+  Front f;
+  f.F = K.F_lo + lane;
+  f.active = f.F < K.F_hi;
+  f.Fc = f.active ? f.F : K.F_hi - 1u;                              // (loads of the idle lanes of the last chunk stay in range)
+  f.pos0 = K.off[f.Fc];
+  f.px = A.ret_slot[H->ret_off + f.Fc];
+  f.need = kLookNone; f.xprod = kLookNone; f.di = 0; f.x = 0; f.xf = kFNone; f.xa = 0;
+  if (K.look || K.compact) {
+    f.x = A.ret_op[H->ret_off + f.Fc];
+    f.xf = A.f[H->op_off + f.x];
+    f.xa = A.a[H->op_off + f.x];
   }
-  if (look) {
-    const int32_t xb = A.b[H->op_off + x];
-    const uint32_t xinv = A.scratch[H->frame_off + x];
-    need = look_need(xf, xa); xprod = look_prod(xf, xa, xb);
-    di = F - xinv < 255u ? F - xinv : 255u;
+  if (K.look) {
+    const int32_t xb = A.b[H->op_off + f.x];
+    const uint32_t xinv = A.scratch[H->frame_off + f.x];
+    f.need = look_need(f.xf, f.xa); f.xprod = look_prod(f.xf, f.xa, xb);
+    f.di = f.F - xinv < 255u ? f.F - xinv : 255u;
   }
+  return f;
+}
+// the front's lookahead record: pm = the slots of the calls open here that produce what the completing call needs, dmin = the producer distance
+WV_DEV void store_look(const Chunk& K, const Front& f, uint64_t pm, uint32_t dmin) {
+  if (f.active && K.look) {
+    pm &= ~(1ull << (f.px & 63u));                                  // one call per slot is open at a front: this is the completing call itself
+    K.look[(uint64_t)f.F * 2u] = look_word0(f.px, f.need, f.xprod, f.di, dmin);
+    K.look[(uint64_t)f.F * 2u + 1u] = pm;
+  }
+}
 
-  bool dense = true;
-  if constexpr (VCAP <= 8) if (sparse) {
-    dense = false;
-    // ---- C, THE SPARSE FORM.  No loop over the candidates with lane = front: a call is open at the fronts inv .. ret, so with lane =
-    // candidate it toggles a bit ON at index max(inv, F_lo) - F_lo and OFF at ret + 1 - F_lo of a 64-entry array in LDS (toggle_slot), and
-    // with lane = front the inclusive XOR scan of ON ^ OFF over the lanes is the set of calls open at each front.  The bits are unique per
-    // (word, index) -- a slot has one call open at a time, its next call is invoked at a later rank than its last completion, a crashed
-    // call's slot is not reused -- so adding is setting; a slot whose call ends at F - 1 and whose next begins at F gets both events at F.
-    // (b) bit = process slot, a round per read-row entry present among the chunk's candidates: the scan IS the front's row entry, stored
-    // where it is made (no row in registers); the entries no round made are stored as zero afterwards
-    {
-      uint64_t* const row = rdm ? rdm + (uint64_t)F * FW : nullptr;
-      const uint32_t n_row = compact ? 6u : V;
-      uint32_t made = 0u;
-      bool pend[kSparseSets];
-      WV_UNROLL
-      for (int s = 0; s < kSparseSets; s++) pend[s] = (c_fl[s] & kCRow) != 0u;
-      for (;;) {
-        const uint64_t b0 = wv::ballot(pend[0]), b1 = NC > 64u ? wv::ballot(pend[1]) : 0ull;
-        if ((b0 | b1) == 0ull) break;
-        uint32_t v;
-        if (b0) v = wv::readlane(c_fl[0], (uint32_t)__builtin_ctzll(b0)); else v = wv::readlane(c_fl[1], (uint32_t)__builtin_ctzll(b1));
-        v = (v >> 4) & 31u;
-        if (lane == 0u) wv::stat(kStatWalkRounds, 1);
-        zero_toggles(tog, lane);
-        wv::barrier();
-        WV_UNROLL
-        for (int s = 0; s < kSparseSets; s++)
-          if (pend[s] && ((c_fl[s] >> 4) & 31u) == v) { const uint32_t* e = cand + (lane + 64u * (uint32_t)s) * kCandWords; toggle_slot(tog, F_lo, e[0], e[1], (c_fl[s] >> 12) & 63u); pend[s] = false; }
-        wv::barrier();
-        const wv::u32x4 t4 = *reinterpret_cast<const wv::u32x4*>(tog + lane * 4u);
-        const uint32_t rlo = xor_scan(t4.x ^ t4.z, lane), rhi = W > 32u ? xor_scan(t4.y ^ t4.w, lane) : 0u;
-        if (active && v < n_row) row[v] = (uint64_t)rlo | ((uint64_t)rhi << 32);
-        made |= 1u << v;
-        wv::barrier();
-      }
-      if (rdm)
-        for (uint32_t v = 0; v < n_row; v++) if (!((made >> v) & 1u) && active) row[v] = 0ull;
-    }
-    // (c) bit = process slot, a round per produced value present that some front of the chunk needs: a front takes the scan of its own
-    // `need` as its producer mask.  The same round counts, a byte per rank, the producers of the value invoked at ranks F_lo - 7 ..
-    // F_lo + 63 (candidates that completed before the chunk included; at most one per slot and rank, so a byte does not carry): a front
-    // reads the eight bytes of ranks F - 7 .. F, takes its own call out (it may produce what it needs: a cas v v) and the highest byte
-    // left that is not zero is the nearest producer.
-    {
-      static_assert(kLookahead == 8u, "a front's window of invocation ranks is eight bytes");
-      uint32_t pm_lo = 0u, pm_hi = 0u, dmin = 255u;
-      bool pend[kSparseSets];
-      WV_UNROLL
-      for (int s = 0; s < kSparseSets; s++) pend[s] = (c_fl[s] & kCLook) != 0u;
-      for (;;) {
-        const uint64_t b0 = wv::ballot(pend[0]), b1 = NC > 64u ? wv::ballot(pend[1]) : 0ull;
-        if ((b0 | b1) == 0ull) break;
-        uint32_t v;
-        if (b0) v = wv::readlane(c_fl[0], (uint32_t)__builtin_ctzll(b0)); else v = wv::readlane(c_fl[1], (uint32_t)__builtin_ctzll(b1));
-        v >>= 24;
-        const bool mine = active && need == v;
-        if (wv::ballot(mine) == 0ull) {                              // nobody needs it
-          WV_UNROLL
-          for (int s = 0; s < kSparseSets; s++) if ((c_fl[s] >> 24) == v) pend[s] = false;
-          continue;
-        }
-        if (lane == 0u) wv::stat(kStatWalkRounds, 1);
-        zero_toggles(tog, lane);
-        if (lane < kRankCntWords) rcnt[lane] = 0u;
-        wv::barrier();
-        WV_UNROLL
-        for (int s = 0; s < kSparseSets; s++)
-          if (pend[s] && (c_fl[s] >> 24) == v) {
-            const uint32_t* e = cand + (lane + 64u * (uint32_t)s) * kCandWords;
-            const uint32_t inv = e[0];
-            toggle_slot(tog, F_lo, inv, e[1], (c_fl[s] >> 12) & 63u);
-            if (inv + (kLookahead - 1u) >= F_lo) {
-              const uint32_t ri = inv + (kLookahead - 1u) - F_lo;          // (invoked before the chunk's last front: below 71)
-              wv::lds_add32(&rcnt[ri >> 2], 1u << (8u * (ri & 3u)));
-            }
-            pend[s] = false;
-          }
-        wv::barrier();
-        const wv::u32x4 t4 = *reinterpret_cast<const wv::u32x4*>(tog + lane * 4u);
-        const uint32_t slo = xor_scan(t4.x ^ t4.z, lane), shi = W > 32u ? xor_scan(t4.y ^ t4.w, lane) : 0u;
-        if (mine) {
-          pm_lo = slo; pm_hi = shi;
-          const uint32_t wb = lane >> 2, sh = 8u * (lane & 3u);
-          const uint64_t lo64 = (uint64_t)rcnt[wb] | ((uint64_t)rcnt[wb + 1u] << 32);
-          uint64_t xb = sh ? ((lo64 >> sh) | ((uint64_t)rcnt[wb + 2u] << (64u - sh))) : lo64;     // byte j: rank F - 7 + j
-#if !defined(TBC_WALK_NO_SELF_EXCLUSION)
-          if (xprod == need && di < kLookahead) xb -= 1ull << (8u * (kLookahead - 1u - di));
-#endif
-          dmin = xb ? (uint32_t)__builtin_clzll(xb) >> 3 : 255u;
-        }
-        wv::barrier();
-      }
-      if (active && look) {
-        uint64_t pm = (uint64_t)pm_lo | ((uint64_t)pm_hi << 32);
-        pm &= ~(1ull << (px & 63u));                                  // (the completing call itself, as in phase D)
-        look[(uint64_t)F * 2u] = (uint64_t)(px & 0xFFFFu) | (uint64_t)need << 16 | (uint64_t)xprod << 24 | (uint64_t)di << 32 | ((uint64_t)dmin << 40);
-        look[(uint64_t)F * 2u + 1u] = pm;
-      }
-    }
-    // (a) bit = the candidate's place in list order, listed candidates only, 64 places a pass: a front's list entries, ascending bit = list
-    // order.  The entries: each lane walks the set bits of its words, lowest first, and takes the candidate's record from the table at an address
-    // of its own; the wavefront goes on while any lane has a bit left -- the longest list of the pass, not NC.  The twin mask of an entry
-    // at front F: down the chain of its effect (B2) from the call itself, the slots of the calls open at F -- the chain is in order of
-    // completion, so it ends at the first call that completed before F.
+// ---- C, THE SPARSE FORM.  No loop over the candidates with lane = front: a call is open at the fronts inv .. ret, so with lane =
+// candidate it toggles a bit ON at index max(inv, F_lo) - F_lo and OFF at ret + 1 - F_lo of a 64-entry array in LDS (toggle_slot), and
+// with lane = front the inclusive XOR scan of ON ^ OFF over the lanes is the set of calls open at each front (open_bits).  The bits are
+// unique per (word, index) -- a slot has one call open at a time, its next call is invoked at a later rank than its last completion, a
+// crashed call's slot is not reused -- so adding is setting; a slot whose call ends at F - 1 and whose next begins at F gets both events at F.
+// sparse_read_rows: bit = process slot, a round per read-row entry present among the chunk's candidates: the scan IS the front's row entry,
+// stored where it is made (no row in registers); the entries no round made are stored as zero afterwards
+WV_DEV void sparse_read_rows(const Chunk& K, uint32_t NC, uint32_t lane, const Front& f, const uint32_t (&c_fl)[kSparseSets]) {
+  uint64_t* const row = K.rdm ? K.rdm + (uint64_t)f.F * K.FW : nullptr;
+  const uint32_t n_row = K.compact ? 6u : K.V;
+  uint32_t made = 0u;
+  bool pend[kSparseSets];
+  WV_UNROLL
+  for (int s = 0; s < kSparseSets; s++) pend[s] = (c_fl[s] & kCRow) != 0u;
+  for (uint32_t fl; (fl = next_pending(pend, c_fl, NC)) != 0u;) {
+    const uint32_t v = (fl >> 4) & 31u;
+    if (lane == 0u) wv::stat(kStatWalkRounds, 1);
+    zero_toggles(K.tog, lane);
+    wv::barrier();
     WV_UNROLL
-    for (int g = 0; g < kSparseSets; g++) {
-      if (64u * (uint32_t)g >= NC) continue;
-      zero_toggles(tog, lane);
-      wv::barrier();
+    for (int s = 0; s < kSparseSets; s++)
+      if (pend[s] && ((c_fl[s] >> 4) & 31u) == v) { const uint32_t* e = K.cand + (lane + 64u * (uint32_t)s) * kCandWords; toggle_slot(K.tog, K.F_lo, e[0], e[1], (c_fl[s] >> 12) & 63u); pend[s] = false; }
+    const uint64_t open = open_bits(K.tog, lane, K.W > 32u);
+    if (f.active && v < n_row) row[v] = open;
+    made |= 1u << v;
+    wv::barrier();
+  }
+  if (K.rdm)
+    for (uint32_t v = 0; v < n_row; v++) if (!((made >> v) & 1u) && f.active) row[v] = 0ull;
+}
+// sparse_producers: bit = process slot, a round per produced value present that some front of the chunk needs: a front takes the scan of its
+// own `need` as its producer mask.  The same round counts, a byte per rank, the producers of the value invoked at ranks F_lo - 7 ..
+// F_lo + 63 (candidates that completed before the chunk included; at most one per slot and rank, so a byte does not carry): a front
+// reads the eight bytes of ranks F - 7 .. F, takes its own call out (it may produce what it needs: a cas v v) and the highest byte
+// left that is not zero is the nearest producer.
+WV_DEV void sparse_producers(const Chunk& K, uint32_t NC, uint32_t lane, const Front& f, const uint32_t (&c_fl)[kSparseSets]) {
+  static_assert(kLookahead == 8u, "a front's window of invocation ranks is eight bytes");
+  uint32_t* const rcnt = K.rcnt;
+  uint64_t pm = 0ull;
+  uint32_t dmin = 255u;
+  bool pend[kSparseSets];
+  WV_UNROLL
+  for (int s = 0; s < kSparseSets; s++) pend[s] = (c_fl[s] & kCLook) != 0u;
+  for (uint32_t fl; (fl = next_pending(pend, c_fl, NC)) != 0u;) {
+    const uint32_t v = fl >> 24;
+    const bool mine = f.active && f.need == v;
+    if (wv::ballot(mine) == 0ull) {                              // nobody needs it
       WV_UNROLL
-      for (int s = 0; s < kSparseSets; s++)
-        if ((c_fl[s] & kCList) && ((c_fl[s] >> 9) & 3u) == (uint32_t)g) { const uint32_t* e = cand + (lane + 64u * (uint32_t)s) * kCandWords; toggle_slot(tog, F_lo, e[0], e[1], (c_fl[s] >> 18) & 63u); }
-      wv::barrier();
-      const wv::u32x4 t4 = *reinterpret_cast<const wv::u32x4*>(tog + lane * 4u);
-      const uint32_t mlo = xor_scan(t4.x ^ t4.z, lane), mhi = xor_scan(t4.y ^ t4.w, lane);
-      uint64_t cur = active ? ((uint64_t)mlo | ((uint64_t)mhi << 32)) : 0ull;
-      wv::barrier();
-      WV_NOUNROLL
-      while (wv::ballot(cur != 0ull) != 0ull) {
-        if (lane == 0u) wv::stat(kStatWalkEmitTrips, 1);
-        uint32_t chain_steps = 0u;                                    // (counted for the emulated build's statistics only)
-        if (cur != 0ull) {
-          const uint32_t p = 64u * (uint32_t)g + (uint32_t)__builtin_ctzll(cur);
-          cur &= cur - 1ull;
-          const uint32_t* e = cand + (by_ret ? (uint32_t)perm[p] : p) * kCandWords;
-          OpRec o; o.op = e[2]; o.f_slot = e[3] | (e[1] == F ? kAtFront : 0u); o.a = (int32_t)e[4]; o.b = (int32_t)e[5];
-          lst[pos] = o;
-          if (twn) {
-            uint64_t tw = 0ull;
-            for (uint32_t u = e[7] & 0xFFu; u != 0xFFu;) {
-              const uint32_t* eu = cand + u * kCandWords;
-              wv::stat(kStatWalkTwinSteps, 1);
-              chain_steps++;
-              if (eu[1] < F) break;
-              if (eu[0] <= F) tw |= 1ull << ((eu[3] >> 8) & 63u);
-#if defined(TBC_WALK_TWIN_LE)
-              if ((eu[7] & 0xFFu) == u) break;
-#endif
-              u = eu[7] & 0xFFu;
-            }
-            twn[pos] = tw;
-          }
-          pos++;
+      for (int s = 0; s < kSparseSets; s++) if ((c_fl[s] >> 24) == v) pend[s] = false;
+      continue;
+    }
+    if (lane == 0u) wv::stat(kStatWalkRounds, 1);
+    zero_toggles(K.tog, lane);
+    if (lane < kRankCntWords) rcnt[lane] = 0u;
+    wv::barrier();
+    WV_UNROLL
+    for (int s = 0; s < kSparseSets; s++)
+      if (pend[s] && (c_fl[s] >> 24) == v) {
+        const uint32_t* e = K.cand + (lane + 64u * (uint32_t)s) * kCandWords;
+        const uint32_t inv = e[0];
+        toggle_slot(K.tog, K.F_lo, inv, e[1], (c_fl[s] >> 12) & 63u);
+        if (inv + (kLookahead - 1u) >= K.F_lo) {
+          const uint32_t ri = inv + (kLookahead - 1u) - K.F_lo;        // (invoked before the chunk's last front: below 71)
+          wv::lds_add32(&rcnt[ri >> 2], 1u << (8u * (ri & 3u)));
         }
-        WV_STAT_WAVE_MAX(kStatWalkChainWave, chain_steps);
+        pend[s] = false;
       }
+    const uint64_t open = open_bits(K.tog, lane, K.W > 32u);
+    if (mine) {
+      pm = open;
+      const uint32_t wb = lane >> 2, sh = 8u * (lane & 3u);
+      const uint64_t lo64 = (uint64_t)rcnt[wb] | ((uint64_t)rcnt[wb + 1u] << 32);
+      uint64_t xb = sh ? ((lo64 >> sh) | ((uint64_t)rcnt[wb + 2u] << (64u - sh))) : lo64;     // byte j: rank F - 7 + j
+#if !defined(TBC_WALK_NO_SELF_EXCLUSION)
+      if (f.xprod == f.need && f.di < kLookahead) xb -= 1ull << (8u * (kLookahead - 1u - f.di));
+#endif
+      dmin = xb ? (uint32_t)__builtin_clzll(xb) >> 3 : 255u;
+    }
+    wv::barrier();
+  }
+  store_look(K, f, pm, dmin);
+}
+// sparse_lists: bit = the candidate's place in list order, listed candidates only, 64 places a pass: a front's list entries, ascending bit =
+// list order.  The entries: each lane walks the set bits of its words, lowest first, and takes the candidate's record from the table at an
+// address of its own; the wavefront goes on while any lane has a bit left -- the longest list of the pass, not NC.  The twin mask of an entry
+// at front F: down the chain of its effect (link_twins) from the call itself, the slots of the calls open at F -- the chain is in order of
+// completion, so it ends at the first call that completed before F.
+// pos: where the front's next list entry goes (lst, twn)
+WV_DEV uint32_t sparse_lists(const Chunk& K, uint32_t NC, uint32_t lane, const Front& f, const uint32_t (&c_fl)[kSparseSets], bool by_ret, uint32_t pos) {
+  const uint32_t* const cand = K.cand;
+  const uint32_t F = f.F;
+  WV_UNROLL
+  for (int g = 0; g < kSparseSets; g++) {
+    if (64u * (uint32_t)g >= NC) continue;
+    zero_toggles(K.tog, lane);
+    wv::barrier();
+    WV_UNROLL
+    for (int s = 0; s < kSparseSets; s++)
+      if ((c_fl[s] & kCList) && ((c_fl[s] >> 9) & 3u) == (uint32_t)g) { const uint32_t* e = cand + (lane + 64u * (uint32_t)s) * kCandWords; toggle_slot(K.tog, K.F_lo, e[0], e[1], (c_fl[s] >> 18) & 63u); }
+    const uint64_t open = open_bits(K.tog, lane, true);
+    uint64_t cur = f.active ? open : 0ull;
+    wv::barrier();
+    WV_NOUNROLL
+    while (wv::ballot(cur != 0ull) != 0ull) {
+      if (lane == 0u) wv::stat(kStatWalkEmitTrips, 1);
+      uint32_t chain_steps = 0u;                                    // (counted for the emulated build's statistics only)
+      if (cur != 0ull) {
+        const uint32_t p = 64u * (uint32_t)g + (uint32_t)__builtin_ctzll(cur);
+        cur &= cur - 1ull;
+        const uint32_t* e = cand + (by_ret ? (uint32_t)K.perm[p] : p) * kCandWords;
+        OpRec o; o.op = e[2]; o.f_slot = e[3] | (e[1] == F ? kAtFront : 0u); o.a = (int32_t)e[4]; o.b = (int32_t)e[5];
+        K.lst[pos] = o;
+        if (K.twn) {
+          uint64_t tw = 0ull;
+          for (uint32_t u = e[7] & 0xFFu; u != 0xFFu;) {
+            const uint32_t* eu = cand + u * kCandWords;
+            wv::stat(kStatWalkTwinSteps, 1);
+            chain_steps++;
+            if (eu[1] < F) break;
+            if (eu[0] <= F) tw |= 1ull << ((eu[3] >> 8) & 63u);
+#if defined(TBC_WALK_TWIN_LE)
+            if ((eu[7] & 0xFFu) == u) break;
+#endif
+            u = eu[7] & 0xFFu;
+          }
+          K.twn[pos] = tw;
+        }
+        pos++;
+      }
+      WV_STAT_WAVE_MAX(kStatWalkChainWave, chain_steps);
     }
   }
+  return pos;
+}
 
-  if (dense) {                              // (its row and masks are registers of this block only: the sparse form holds none of them)
+// ---- C, THE DENSE LOOP: iteration t broadcasts the candidate at place t of the list order to the 64 lanes, and each lane decides for ITS
+// front whether the call is open there -- then appends it to its front's list (lst, twn at pos), ors its slot into its read row (registers:
+// see store_entries) / its producer mask, keeps the nearest producer.  c_key, c_ret: dense_twin_keys.
+template <int VCAP>
+WV_DEV uint32_t dense_loop(const Chunk& K, uint32_t NC, uint32_t lane, const Front& f, const uint32_t (&c_key)[3], const uint32_t (&c_ret)[3], bool by_ret, uint32_t pos) {
+  const uint32_t* const cand = K.cand;
+  const uint32_t F = f.F;
+  const bool active = f.active;
   wv::u32x16 r0, r1, r2, r3;                // the front's row (r1 .. r3: rows of more than 8 entries only)
   WV_UNROLL
   for (int i = 0; i < 16; i++) { r0[i] = 0u; r1[i] = 0u; r2[i] = 0u; r3[i] = 0u; }
   uint32_t pm_lo = 0u, pm_hi = 0u, dmin = 255u;
   WV_NOUNROLL
   for (uint32_t t = 0; t < NC; t++) {
-    const uint32_t* e = cand + (by_ret ? (uint32_t)perm[t] : t) * kCandWords;
+    const uint32_t* e = cand + (by_ret ? (uint32_t)K.perm[t] : t) * kCandWords;
     const uint32_t inv = e[0], ret = e[1];
     const uint32_t fl = wv::readfirstlane(e[6]);
     const uint32_t slot = (fl >> 12) & 63u;
@@ -683,8 +709,8 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
       }
       if (member) {
         OpRec o; o.op = e[2]; o.f_slot = e[3] | (ret == F ? kAtFront : 0u); o.a = (int32_t)e[4]; o.b = (int32_t)e[5];
-        lst[pos] = o;
-        if (twn) twn[pos] = (uint64_t)tw_lo | ((uint64_t)tw_hi << 32);
+        K.lst[pos] = o;
+        if (K.twn) K.twn[pos] = (uint64_t)tw_lo | ((uint64_t)tw_hi << 32);
         pos++;
       }
     }
@@ -698,51 +724,122 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
       }
     }
     if (fl & kCLook) {                 // who else, open here, produces what the completing call needs; how recently such a call was invoked
-      const bool hit = (fl >> 24) == need;
+      const bool hit = (fl >> 24) == f.need;
       or_slot(pm_lo, pm_hi, member && hit, slot);
       const uint32_t dist = F - inv;                                // (invoked after this front: wraps past kLookahead)
-      if (hit && dist < kLookahead && e[2] != x) dmin = dist < dmin ? dist : dmin;
+      if (hit && dist < kLookahead && e[2] != f.x) dmin = dist < dmin ? dist : dmin;
     }
   }
-  if (active && rdm) {
-    uint64_t* row = rdm + (uint64_t)F * FW;
-    const uint32_t n_row = compact ? 6u : V;
+  if (active && K.rdm) {
+    uint64_t* row = K.rdm + (uint64_t)F * K.FW;
+    const uint32_t n_row = K.compact ? 6u : K.V;
     store_entries<0>(r0, row, n_row);
     if constexpr (VCAP > 8) { store_entries<1>(r1, row, n_row); store_entries<2>(r2, row, n_row); store_entries<3>(r3, row, n_row); }
   }
-  if (active && look) {
-    uint64_t pm = (uint64_t)pm_lo | ((uint64_t)pm_hi << 32);
-    pm &= ~(1ull << (px & 63u));                                    // one call per slot is open at a front: this is the completing call itself
-    const uint64_t w0 = (uint64_t)(px & 0xFFFFu) | (uint64_t)need << 16 | (uint64_t)xprod << 24 | (uint64_t)di << 32 | ((uint64_t)dmin << 40);
-    look[(uint64_t)F * 2u] = w0;
-    look[(uint64_t)F * 2u + 1u] = pm;
-  }
-  }
+  store_look(K, f, (uint64_t)pm_lo | ((uint64_t)pm_hi << 32), dmin);
+  return pos;
+}
 
-  // ---- D. the rest of each front's record / row
-  uint64_t w6 = 0ull, w7 = 0ull;
-  if (compact) {           // list location and the window of the next seven ranks (tbc_internal.h), through LDS: codes of the chunk + 6 after
-    if (by_ret) wv::barrier();                                      // (the places above lived in these words: every lane is past the loop)
-    aux[lane] = active ? rank_code(px, xf, xa, V) : (7u << 6);
-    if (lane < kFrontCompactRanks - 1u) {
-      const uint32_t G = F_lo + 64u + lane;
-      uint32_t code = 7u << 6;                                      // (past the last rank: slot 0, not a read)
-      if (G < R) {
-        const uint32_t gx = A.ret_op[H->ret_off + G];
-        code = rank_code(A.ret_slot[H->ret_off + G], A.f[H->op_off + gx], A.a[H->op_off + gx], V);
-      }
-      aux[64u + lane] = code;
+// ---- D. the rest of a compact front record: word 6, the list's location (nl entries from pos0) and the count of open calls, and word 7,
+// the window of the next seven ranks (tbc_internal.h), through LDS: codes of the chunk + 6 after
+WV_DEV void compact_tail(const Chunk& K, uint32_t lane, const Front& f, bool by_ret, uint32_t nl) {
+  const auto& A = *K.A;
+  const auto* H = K.H;
+  uint32_t* const aux = K.aux;
+  if (by_ret) wv::barrier();                                        // (the places lived in these words: every lane is past phase C)
+  aux[lane] = f.active ? rank_code(f.px, f.xf, f.xa, K.V) : (7u << 6);
+  if (lane < kFrontCompactRanks - 1u) {
+    const uint32_t G = K.F_lo + 64u + lane;
+    uint32_t code = 7u << 6;                                        // (past the last rank: slot 0, not a read)
+    if (G < K.R) {
+      const uint32_t gx = A.ret_op[H->ret_off + G];
+      code = rank_code(A.ret_slot[H->ret_off + G], A.f[H->op_off + gx], A.a[H->op_off + gx], K.V);
     }
-    wv::barrier();
-    WV_UNROLL
-    for (uint32_t l = 0; l < kFrontCompactRanks; l++) w7 |= (uint64_t)aux[lane + l] << (9u * l);
-    const uint32_t nl = pos - pos0, nc = A.ncr[B->off_off + Fc];
-    w6 = (uint64_t)pos0 | ((uint64_t)(nl & 0xFFu) << 32) | ((uint64_t)((nl + nc) & 0xFFFFFFu) << 40);
+    aux[64u + lane] = code;
   }
-  if (active && rdm && compact) {
-    uint64_t* row = rdm + (uint64_t)F * FW;
+  wv::barrier();
+  uint64_t w7 = 0ull;
+  WV_UNROLL
+  for (uint32_t l = kFrontCompactRanks; l-- > 0u;) w7 |= (uint64_t)aux[lane + l] << (9u * l);
+  const uint64_t w6 = front_word6(f.pos0, nl, A.ncr[K.B->off_off + f.Fc]);
+  if (f.active && K.rdm) {
+    uint64_t* row = K.rdm + (uint64_t)f.F * K.FW;
     row[6] = w6; row[7] = w7;
   }
+}
+
+// One chunk: fronts 64 c .. 64 c + 63 of history h.  carried: the slot cursors are what the chunk before left in LDS (else: from nothing).
+// Returns whether the history has a front after this chunk.
+// VCAP: row entries kept in registers (vpad <= VCAP)
+template <int VCAP>
+WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t* lds, uint32_t lane, bool carried) {
+  const auto& A = *wv::cold(A_);            // (the arguments from the kernarg segment, per chunk: not some sixty scalar registers held over a run)
+  const auto* H = read_only(&A.hist[h]);
+  const auto* B = read_only(&A.bh[h]);
+  const uint32_t R = H->n_ret;
+  const uint32_t F_lo = c * 64u;
+  if (H->status != 0 || B->status != 0 || F_lo >= R) return false;
+  Chunk K;
+  K.A = &A; K.H = H; K.B = B;
+  K.R = R; K.F_lo = F_lo; K.F_hi = F_lo + 64u < R ? F_lo + 64u : R;
+  K.W = H->n_slots;
+  K.rec = A.rec + H->rec_off;
+  K.seg = A.seg + H->seg_off;
+  K.off = A.off + B->off_off;
+  K.lst = A.lst + B->lst_off;
+  K.twn = A.twn ? A.twn + B->lst_off : nullptr;
+  K.want_tw = K.twn != nullptr;
+  K.V = A.vpad;
+  K.FW = A.front_words ? A.front_words : K.V;
+  K.compact = A.front_compact != 0u;
+  K.rdm = (A.rdm && (K.V || K.compact)) ? A.rdm + H->op_off * K.FW : nullptr;
+  K.look = A.look ? A.look + look_off(H->op_off, h, 1u) : nullptr;
+  K.ret_from = K.look ? (F_lo >= kLookahead - 1u ? F_lo - (kLookahead - 1u) : 0u) : F_lo;
+  K.cand = lds;
+  K.aux = lds + kCandCap * kCandWords;
+  K.perm = reinterpret_cast<uint16_t*>(K.aux);
+  K.cur_end = K.aux + kAuxWords;
+  K.cur_left = reinterpret_cast<uint16_t*>(K.cur_end + 64);
+  K.tog = K.cand + kSparseCand * kCandWords;
+  K.rcnt = K.tog + kTogWords;
+
+  // A: the candidate table
+  const uint32_t NC_all = fill_candidates(K, lane, carried);
+  const uint32_t NC = NC_all < kCandCap ? NC_all : kCandCap;      // (never more: see the header)
+  // A2: the candidates' places in list order
+  const uint32_t list_order = A.order_of ? A.order_of[h] : A.list_order;          // (the history's own order, if the batch says one)
+  const bool by_ret = list_order != 0u;
+  uint32_t place[3] = {lane, lane + 64u, lane + 128u};              // candidate lane + 64 s: its place in list order (list_order 0: the table's)
+  if (by_ret) list_places(K, NC, lane, list_order, place);
+
+  // The sparse form of phase C or the dense loop: decided per chunk, uniformly.  The dense loop takes rows of more than 8 entries
+  // (VCAP) and a chunk of more than kSparseCand candidates (the form's round buffer lies over the end of the table).
+  bool sparse = VCAP <= 8 && NC_all <= kSparseCand;
+#if defined(TBC_EMU)
+  if (emu_force_dense()) sparse = false;
+#endif
+  // B, B2: the candidates in registers, one per lane; (sparse) the twin chains
+  uint32_t c_fl[kSparseSets] = {0u, 0u};
+  uint32_t c_key[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, c_ret[3] = {0u, 0u, 0u};
+  if (sparse) sparse_flags(K, NC, lane, place, c_fl);
+  else if (K.want_tw) dense_twin_keys(K, NC, lane, c_key, c_ret);
+  if constexpr (VCAP <= 8) if (sparse && K.want_tw) link_twins(K, NC, lane, c_key, c_ret);
+  if (lane == 0u) wv::stat(sparse ? kStatWalkSparse : kStatWalkDense, 1);
+  if (lane == 0u) wv::stat(kStatWalkCands + (NC_all > 64u ? 1u : 0u) + (NC_all > kSparseCand ? 1u : 0u), 1);
+
+  // C: lane = front.  Either form leaves the fronts' rdm rows, their look records and, from pos on, their lst / twn entries
+  const Front f = front_of(K, lane);
+  uint32_t pos = f.pos0;
+  bool dense = true;
+  if constexpr (VCAP <= 8) if (sparse) {
+    dense = false;
+    sparse_read_rows(K, NC, lane, f, c_fl);
+    sparse_producers(K, NC, lane, f, c_fl);
+    pos = sparse_lists(K, NC, lane, f, c_fl, by_ret, pos);
+  }
+  if (dense) pos = dense_loop<VCAP>(K, NC, lane, f, c_key, c_ret, by_ret, pos);
+  // D: words 6 and 7 of a compact record
+  if (K.compact) compact_tail(K, lane, f, by_ret, pos - f.pos0);
   return F_lo + 64u < R;
 }
 

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(1024) void open_counts_kernel(PackOpenArgs A) {
       const uint32_t LW = 1 + MW;
       uint64_t* look = A.look + look_off(H->op_off, h, MW);
       for (uint32_t t = R + tid; t < R + kLookPad; t += NT) {
-        look[(uint64_t)t * LW] = (uint64_t)(kLookNone << 16 | kLookNone << 24) | (255ull << 32) | (255ull << 40);
+        look[(uint64_t)t * LW] = look_word0(0u, kLookNone, kLookNone, 255u, 255u);
         for (uint32_t w = 0; w < MW; w++) look[(uint64_t)t * LW + 1 + w] = 0ull;
       }
     }
@@ -314,12 +314,8 @@ __global__ __launch_bounds__(256) void open_walk_kernel(PackOpenArgs A) {
     const uint32_t p = lane + 64u * (uint32_t)j;
     cur[j] = Cur{kInf, kInf, kInf, kFNone, 0, 0, 0u, kLookNone}; nxt[j] = cur[j]; at[j] = 0; tail[j] = 0;
     if (p < W) {
-      uint32_t lo = seg[p] + 1u, hi = seg[p + 1] - 1u;     // [lo, hi): the slot's calls; hi = its tail sentinel
-      tail[j] = hi;
-      while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (rec[mid].ret_rank >= F_lo) hi = mid; else lo = mid + 1u;
-      }
+      tail[j] = seg[p + 1] - 1u;                           // [seg[p] + 1, tail): the slot's calls; tail = its tail sentinel
+      const uint32_t lo = walk::first_open(rec, seg[p] + 1u, tail[j], F_lo);
       at[j] = lo;
       cur[j] = load_cur(rec + lo);
       nxt[j] = load_cur(rec + min(lo + 1u, tail[j]));
@@ -426,7 +422,7 @@ __global__ __launch_bounds__(256) void open_walk_kernel(PackOpenArgs A) {
         xa = (int32_t)__builtin_amdgcn_readlane((uint32_t)cur[j].a, lx); xb = (int32_t)__builtin_amdgcn_readlane((uint32_t)cur[j].b, lx);
       }
       const uint32_t need = look_need(xf, xa), prod = look_prod(xf, xa, xb), di = min(F - xinv, 255u);
-      const uint64_t w0 = (uint64_t)(px & 0xFFFFu) | (uint64_t)need << 16 | (uint64_t)prod << 24 | (uint64_t)di << 32 | (255ull << 40);
+      const uint64_t w0 = look_word0(px, need, prod, di, 255u);
       const uint32_t LW = 1 + MW;
 #pragma unroll
       for (int j = 0; j < MW; j++) {
@@ -579,11 +575,9 @@ __global__ __launch_bounds__(256) void front_meta_kernel(PackOpenArgs A) {
     uint64_t* rec = A.rdm + (H->op_off + F) * kFrontCompactWords;
     uint64_t win = 0;
 #pragma unroll
-    for (uint32_t l = 0; l < kFrontCompactRanks; l++) {
-      const uint32_t sl = (uint32_t)(w[0] >> (8u * l)) & 63u, k = (uint32_t)(w[2] >> (8u * l)) & 0xFFu;
-      win |= (uint64_t)(sl | ((k == 0xFFu ? 7u : (k & 7u)) << 6)) << (9u * l);
-    }
-    rec[6] = (uint64_t)o0 | ((uint64_t)((o1 - o0) & 0xFFu) << 32) | ((uint64_t)(((o1 - o0) + nc) & 0xFFFFFFu) << 40);
+    for (uint32_t l = 0; l < kFrontCompactRanks; l++)
+      win |= (uint64_t)front_rank_code((uint32_t)(w[0] >> (8u * l)), (uint32_t)(w[2] >> (8u * l)) & 0xFFu) << (9u * l);
+    rec[6] = front_word6(o0, o1 - o0, nc);
     rec[7] = win;
     return;
   }

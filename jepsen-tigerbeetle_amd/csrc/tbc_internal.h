@@ -148,6 +148,10 @@ __host__ __device__ inline uint32_t look_need(uint32_t f, int32_t a) {
 __host__ __device__ inline uint32_t look_prod(uint32_t f, int32_t a, int32_t b) {
   return f == TBC_F_WRITE ? look_val(a) : (f == TBC_F_CAS ? look_val(b) : kLookNone);
 }
+// word 0 of a lookahead record (above)
+__host__ __device__ inline uint64_t look_word0(uint32_t slot, uint32_t need, uint32_t prod, uint32_t dinv, uint32_t dprod) {
+  return (uint64_t)(slot & 0xFFFFu) | (uint64_t)need << 16 | (uint64_t)prod << 24 | (uint64_t)dinv << 32 | (uint64_t)dprod << 40;
+}
 // Rec.cls: bit 0 = a call at all (not a sentinel), 1 = live (completes), 2 = crashed and a candidate (not a nil read),
 // 3 = write / cas, 4 = read
 __host__ __device__ inline uint32_t rec_cls(uint32_t f, int32_t a, bool crashed) {
@@ -223,6 +227,14 @@ __host__ __device__ inline uint32_t front_stride(uint32_t vpad, uint32_t mask_wo
 //   6   off[F] | nlive << 32 | cnt << 40
 //   7   ranks F .. F + 6, nine bits each: process slot (6) | read kind (3: the rdm index of the value read, 7 = not a read)
 constexpr uint32_t kFrontCompactWords = 8, kFrontCompactRanks = 7;
+// word 6: the front's list (nlive entries from off) and cnt = nlive + the crashed candidates open at F
+__host__ __device__ inline uint64_t front_word6(uint32_t off, uint32_t nlive, uint32_t ncrashed) {
+  return (uint64_t)off | ((uint64_t)(nlive & 0xFFu) << 32) | ((uint64_t)((nlive + ncrashed) & 0xFFFFFFu) << 40);
+}
+// a rank's nine bits of word 7, from its slot and its rk8 byte (0xFF = not a read, else the rdm index of the value read)
+__host__ __device__ inline uint32_t front_rank_code(uint32_t slot, uint32_t rk8) {
+  return (slot & 63u) | ((rk8 == 0xFFu ? 7u : (rk8 & 7u)) << 6);
+}
 __host__ __device__ inline bool front_compact_ok(uint32_t n_dom, uint32_t mask_words) { return mask_words == 1 && n_dom >= 2 && n_dom <= 6; }
 constexpr uint64_t kNarrowMaxOps = 0xFFFFF0ull;          // several histories per wavefront: front + 1 must fit 24 bits of a visited-set key
 constexpr int32_t kMaxRuleValue = 30;       // register values 0..30 (vpad <= 32); anything else switches the rules off

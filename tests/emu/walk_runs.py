@@ -12,7 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "jepsen-tigerbeetle_amd", "csrc")
 _SO = os.path.join(_HERE, "_build", "libemu_walk_runs.so")
-_SRCS = [os.path.join(_HERE, "emu_walk_runs.cpp"), os.path.join(_HERE, "wave_env_emu.h"), os.path.join(_HERE, "host_tables.h"),
+_SRCS = [os.path.join(_HERE, "emu_walk_runs.cpp"), os.path.join(_HERE, "walk_harness.h"), os.path.join(_HERE, "wave_env_emu.h"), os.path.join(_HERE, "host_tables.h"),
          os.path.join(_CSRC, "open_walk_impl.h"), os.path.join(_CSRC, "tbc_internal.h"), os.path.join(_CSRC, "wave_env.h")]
 _FLAGS = ["-g", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I", _HERE, "-I", _CSRC]
 _LIB = None
@@ -79,22 +79,32 @@ def expected_counts(hists, run):
     return runs, chunks
 
 
+WHAT = {1: "lst", 2: "twn", 3: "rdm", 4: "look word 0", 5: "look mask", 6: "tmp", 9: "bad input"}
+COUNT_NAMES = ("searches", "carried", "mismatches", "runs", "chunks")
+
+
+def call_check(fn, hists, vpad, flags, run=None):
+    """One of the harness's checks (emu_walk_check: run=None, it takes neither run nor counts; emu_walk_runs_check,
+    emu_walk_sparse_count_check) on these histories.  Returns (None or (what, history, front, index, got, want), counts)."""
+    nh, op_off, npr, f, a, b, pr, inv, ret = _columns(hists)
+    diag = np.zeros(8, np.uint64)
+    cnt = np.zeros(8, np.uint64)
+    fn.restype = C.c_int
+    rc = fn(C.c_uint32(nh), _p(op_off, C.c_uint64), _p(npr, C.c_uint32), _p(f, C.c_uint8), _p(a, C.c_int32), _p(b, C.c_int32),
+            _p(pr, C.c_int32), _p(inv, C.c_uint32), _p(ret, C.c_uint32), C.c_uint32(vpad), C.c_uint32(flags),
+            *(() if run is None else (C.c_uint32(run),)), _p(diag, C.c_uint64), *(() if run is None else (_p(cnt, C.c_uint64),)))
+    counts = dict(zip(COUNT_NAMES, (int(x) for x in cnt[:5])))
+    if rc == 0:
+        return None, counts
+    return (WHAT.get(rc, str(rc)), int(diag[0]), int(diag[1]), int(diag[2]), hex(int(diag[3])), hex(int(diag[4]))), counts
+
+
 def walk_runs_check(hists, vpad, run=0, twin=True, look=True, branch=False, front="plain", by_ret=0):
     """Run walk_run (run chunks a wavefront: 0 = the kernel's kWalkRun, or 2, 3) on these histories and compare every word it writes with
     the host-built tables.  Returns (None or (what, history, front, index, got, want), counts) with counts = dict(searches, carried,
     mismatches, runs, chunks): chunks that searched / took carried cursors, slot lanes whose carried cursor was not the searched one, and
     the harness's own count of (history, run) pairs and chunks that have a front."""
-    nh, op_off, npr, f, a, b, pr, inv, ret = _columns(hists)
-    diag = np.zeros(8, np.uint64)
-    cnt = np.zeros(8, np.uint64)
-    rc = _lib().emu_walk_runs_check(C.c_uint32(nh), _p(op_off, C.c_uint64), _p(npr, C.c_uint32), _p(f, C.c_uint8), _p(a, C.c_int32), _p(b, C.c_int32),
-                                    _p(pr, C.c_int32), _p(inv, C.c_uint32), _p(ret, C.c_uint32), C.c_uint32(vpad), C.c_uint32(_flags(twin, look, branch, front, by_ret)),
-                                    C.c_uint32(run), _p(diag, C.c_uint64), _p(cnt, C.c_uint64))
-    counts = dict(zip(("searches", "carried", "mismatches", "runs", "chunks"), (int(x) for x in cnt[:5])))
-    if rc == 0:
-        return None, counts
-    what = {1: "lst", 2: "twn", 3: "rdm", 4: "look word 0", 5: "look mask", 9: "bad input"}.get(rc, str(rc))
-    return (what, int(diag[0]), int(diag[1]), int(diag[2]), hex(int(diag[3])), hex(int(diag[4]))), counts
+    return call_check(_lib().emu_walk_runs_check, hists, vpad, _flags(twin, look, branch, front, by_ret), run)
 
 
 def dump(path, hists, vpad, run=0, twin=True, look=True, branch=False, front="plain", by_ret=0):

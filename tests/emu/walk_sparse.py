@@ -56,23 +56,14 @@ def check(hists, vpad, run=0, twin=True, look=True, branch=False, front="plain",
     counts): walk_runs.walk_runs_check's counts plus the sparse form's (STAT_NAMES).  dense: every chunk takes the dense loop.  count_form: the histories as the count form
     lays them out (live calls on re-used slots, crashed calls on none); run must be 0 there."""
     lib = _lib(mutation)
-    nh, op_off, npr, f, a, b, pr, inv, ret = walk_runs._columns(hists)
-    p = walk_runs._p
-    diag = np.zeros(8, np.uint64)
-    cnt = np.zeros(8, np.uint64)
     st = np.zeros(16, np.uint64)
     lib.emu_walk_force_dense(C.c_int(1 if dense else 0))
-    lib.emu_walk_sparse_stats(p(st, C.c_uint64), C.c_int(1))
+    lib.emu_walk_sparse_stats(walk_runs._p(st, C.c_uint64), C.c_int(1))
     try:
-        rc = (lib.emu_walk_sparse_count_check if count_form else lib.emu_walk_runs_check)(C.c_uint32(nh), p(op_off, C.c_uint64), p(npr, C.c_uint32), p(f, C.c_uint8), p(a, C.c_int32), p(b, C.c_int32),
-                                     p(pr, C.c_int32), p(inv, C.c_uint32), p(ret, C.c_uint32), C.c_uint32(vpad),
-                                     C.c_uint32(walk_runs._flags(twin, look, branch, front, by_ret)), C.c_uint32(run), p(diag, C.c_uint64), p(cnt, C.c_uint64))
+        err, counts = walk_runs.call_check(lib.emu_walk_sparse_count_check if count_form else lib.emu_walk_runs_check, hists, vpad,
+                                           walk_runs._flags(twin, look, branch, front, by_ret), run)
     finally:
         lib.emu_walk_force_dense(C.c_int(0))
-    lib.emu_walk_sparse_stats(p(st, C.c_uint64), C.c_int(1))
-    counts = dict(zip(("searches", "carried", "mismatches", "runs", "chunks"), (int(x) for x in cnt[:5])))
+    lib.emu_walk_sparse_stats(walk_runs._p(st, C.c_uint64), C.c_int(1))
     counts.update(zip(STAT_NAMES, (int(x) for x in st[:len(STAT_NAMES)])))
-    if rc == 0:
-        return None, counts
-    what = {1: "lst", 2: "twn", 3: "rdm", 4: "look word 0", 5: "look mask", 9: "bad input"}.get(rc, str(rc))
-    return (what, int(diag[0]), int(diag[1]), int(diag[2]), hex(int(diag[3])), hex(int(diag[4]))), counts
+    return err, counts
