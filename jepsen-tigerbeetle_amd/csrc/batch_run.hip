@@ -54,7 +54,8 @@ PackOpenArgs make_pack_open_args(tbc_batch* B) {
   po.crashed = B->d_crashed.p; po.ret_slot = B->d_ret_slot.p; po.slot8 = B->d_slot8.p;
   po.ret_op = B->d_ret_op.p; po.look = B->lookahead ? B->d_look.p : nullptr; po.tmp = B->d_looktmp.p; po.n_hist = B->n_hist; po.mask_words = B->mask_words;
   po.branch_lists = (B->rules & kRuleBranch) ? 1u : 0u;
-  po.rk8 = B->lanes ? B->d_rk8.p : nullptr; po.front_words = B->front_words(); po.front_compact = B->front_words() == kFrontCompactWords ? 1u : 0u;
+  po.rk8 = B->lanes ? B->d_rk8.p : nullptr; po.front_words = B->front_words();
+  po.front_compact = front_is_compact(B->front_words(), B->mask_words) ? 1u : 0u;          // (not by the record's size alone: tbc_internal.h)
   po.twn = B->reg_rules() ? B->d_twn.p : nullptr; po.rdm = (B->reg_rules() || B->lanes) ? B->d_rdm.p : nullptr; po.vpad = B->vpad;
   po.cmem = B->count_form ? B->d_cmem.p : nullptr;
   po.list_order = B->list_order();

@@ -236,6 +236,11 @@ __host__ __device__ inline uint32_t front_rank_code(uint32_t slot, uint32_t rk8)
   return (slot & 63u) | ((rk8 == 0xFFu ? 7u : (rk8 & 7u)) << 6);
 }
 __host__ __device__ inline bool front_compact_ok(uint32_t n_dom, uint32_t mask_words) { return mask_words == 1 && n_dom >= 2 && n_dom <= 6; }
+// Are a batch's front records the compact ones?  The ONE statement of it, for the pack (PackOpenArgs.front_compact) and for the narrow
+// kernel's launch alike: the compact record exists at one mask word only, and 8 words is also what front_stride() gives at EVERY mask
+// width when there are no rule tables (vpad 0: a mutex, register values past 30) -- at two or four mask words that is the plain record.
+// (At one mask word a record of 8 words is packed and read as the compact one whichever way it came to 8: both sides ask this function.)
+__host__ __device__ inline bool front_is_compact(uint32_t front_words, uint32_t mask_words) { return mask_words == 1 && front_words == kFrontCompactWords; }
 constexpr uint64_t kNarrowMaxOps = 0xFFFFF0ull;          // several histories per wavefront: front + 1 must fit 24 bits of a visited-set key
 constexpr int32_t kMaxRuleValue = 30;       // register values 0..30 (vpad <= 32); anything else switches the rules off
 __host__ __device__ inline uint32_t rdm_index(int32_t v, uint32_t vpad) {   // row entry of state / read value v

@@ -57,13 +57,13 @@ template <int MW, int L>
 void launch_one(const BeamArgs& a, hipStream_t s, uint32_t wps) {
   if constexpr (MW <= 2 && L >= 8) {
     if (a.rules & kRuleCount) {          // the count form (crashed calls as counts per class): one or two mask words, 8 / 16 / 32 lanes per history
-      if constexpr (MW == 1) { if (a.front_words == kFrontCompactWords) { launch_cf<1, L, true, true>(a, s, wps); return; } }
+      if constexpr (MW == 1) { if (front_is_compact(a.front_words, MW)) { launch_cf<1, L, true, true>(a, s, wps); return; } }
       launch_cf<MW, L, false, true>(a, s, wps);
       return;
     }
   }
   if constexpr (MW == 1) {
-    if (a.front_words == kFrontCompactWords) { launch_cf<1, L, true>(a, s, wps); return; }
+    if (front_is_compact(a.front_words, MW)) { launch_cf<1, L, true>(a, s, wps); return; }
   }
   launch_cf<MW, L, false>(a, s, wps);
 }

@@ -37,7 +37,7 @@ void run_all(BeamArgs& A, uint32_t max_waves) {
   static unsigned int next_work;
   next_work = 0;
   A.first_dynamic = waves * H; A.next_work = &next_work;
-  const bool cf = MW == 1 && A.front_words == kFrontCompactWords;
+  const bool cf = front_is_compact(A.front_words, MW);
   const bool cnt = (A.rules & kRuleCount) != 0u;
   std::vector<uint32_t> lds(narrow::narrow_lds_words(MW, L, cf, cnt) + 16);
   for (uint32_t w = 0; w < waves; w++) {

@@ -2,6 +2,8 @@
 import json
 import os
 
+import numpy as np
+
 from jepsen_tigerbeetle_amd import _native as N
 from jepsen_tigerbeetle_amd.knossos import model as M
 
@@ -29,6 +31,33 @@ def oracle_model(name):
 def op_tuples(ops):
     return [(int(ops.f[i]), int(ops.a[i]), int(ops.b[i]), int(ops.inv_pos[i]), int(ops.ret_pos[i]))
             for i in range(len(ops))]
+
+
+# ---- a device result against the oracle of its schedule, field by field (tests/test_gpu_parity.py, tests/test_models_gpu.py)
+def assert_same(got, exp, tag=""):
+    """the sequential kernel against oracle.check(..., "window")"""
+    assert got["valid"] == exp["valid"], (tag, got["valid"], exp["valid"])
+    if exp["valid"] == 0:
+        assert got["fail_op"] == exp["fail_op"], tag
+        assert got["prev_ok_op"] == (None if exp["prev_ok_op"] == N.NO_OP else exp["prev_ok_op"]), tag
+    if exp["valid"] == 1:
+        assert got["final_state"] == exp["final_state"], tag
+        assert np.array_equal(got["witness"], exp["witness"]), tag
+    for k in ("steps", "visited", "probes", "backtracks", "max_depth"):
+        assert got[k] == exp[k], (tag, k, got[k], exp[k])
+
+
+def _assert_narrow(got, exp, tag):
+    """the narrow kernel (several histories per wavefront) against oracle.check_beam(..., 1, round_pairs=L, ...)"""
+    assert got["valid"] == exp["valid"], (tag, got["valid"], exp["valid"], got["cause"])
+    assert got["search_width"] == 1, tag
+    assert (got["probes"], got["visited"], got["backtracks"], got["max_depth"]) == (exp["probes"], exp["visited"], exp["expanded"], exp["max_stack"]), tag
+    if exp["valid"] == 1:
+        assert got["final_state"] == exp["final_state"], tag
+        if got["witness"] is not None:
+            assert np.array_equal(got["witness"], exp["witness"]), tag
+    elif exp["valid"] == 0:
+        assert got["fail_op"] == exp["fail_op"], tag
 
 
 def multi_register_history(n_ops, n_procs, seed, n_keys=4, n_values=4, busy=0.4, info=0.0, corrupt=False):
@@ -94,6 +123,10 @@ def multi_register_history(n_ops, n_procs, seed, n_keys=4, n_values=4, busy=0.4,
     return hist
 
 
+class Refused:
+    """What apply_op returns for a call the object refuses: it has no effect and completes :fail (a crashed one stays :info)."""
+
+
 def _simulate(n_ops, n_procs, seed, busy, info, make_op, apply_op):
     """Generic discrete-event simulation of one atomic object (see multi_register_history)."""
     import heapq
@@ -129,6 +162,8 @@ def _simulate(n_ops, n_procs, seed, busy, info, make_op, apply_op):
                 hist.append({"type": "info", "f": c["f"], "value": c["value"], "process": pid[w], "error": "timeout"})
                 pid[w] = next_pid
                 next_pid += 1
+            elif c["res"] is Refused:
+                hist.append({"type": "fail", "f": c["f"], "value": c["value"], "process": pid[w]})
             else:
                 hist.append({"type": "ok", "f": c["f"], "value": c["res"], "process": pid[w]})
             heapq.heappush(heap, (t + rng.expovariate(1.0 / think) + 1e-9, seq, w, "inv")); seq += 1

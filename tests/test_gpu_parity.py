@@ -7,7 +7,7 @@ idempotent)."""
 import numpy as np
 import pytest
 
-from helpers import MODELS, load_kats, op_tuples, oracle_model
+from helpers import MODELS, _assert_narrow, assert_same, load_kats, op_tuples, oracle_model
 from jepsen_tigerbeetle_amd import _native as N, columns, core, synth
 from jepsen_tigerbeetle_amd.jepsen import checker as jc, independent
 from jepsen_tigerbeetle_amd.knossos import _analysis, competition, linear, model as M, op as kop, wgl
@@ -23,18 +23,6 @@ def gm():
 
 
 SEQ = dict(algorithm=N.ALG_WGL)   # the sequential knossos.wgl order (search_width 1)
-
-
-def assert_same(got, exp, tag=""):
-    assert got["valid"] == exp["valid"], (tag, got["valid"], exp["valid"])
-    if exp["valid"] == 0:
-        assert got["fail_op"] == exp["fail_op"], tag
-        assert got["prev_ok_op"] == (None if exp["prev_ok_op"] == N.NO_OP else exp["prev_ok_op"]), tag
-    if exp["valid"] == 1:
-        assert got["final_state"] == exp["final_state"], tag
-        assert np.array_equal(got["witness"], exp["witness"]), tag
-    for k in ("steps", "visited", "probes", "backtracks", "max_depth"):
-        assert got[k] == exp[k], (tag, k, got[k], exp[k])
 
 
 KATS = load_kats()
@@ -210,7 +198,11 @@ def test_rejects_malformed_ops(native):
         assert e.value.status == N.ERR_MODEL
 
 
-def test_mutex_and_table_models(native, oracle):
+def test_hand_histories_of_mutex_set_and_txn_through_the_surface(native, oracle):
+    """Hand-written histories through knossos.wgl/analysis: a lock handed back and forth (TBC_MODEL_MUTEX, the sequential kernel), and
+    a set and a txn history -- which the surface encodes as the DIRECT device models (_analysis._set_direct, _multi_register_direct),
+    not as the memo table.  The memo-table route (TBC_MODEL_TABLE) and the mutex on every other engine, seeded and against the
+    oracles: tests/test_models_gpu.py."""
     h = []
     for i in range(40):   # two processes handing a lock back and forth, one bad double-acquire at the end
         p = i % 2
@@ -219,7 +211,7 @@ def test_mutex_and_table_models(native, oracle):
     h += [kop.invoke(0, "acquire", None), kop.ok(0, "acquire", None), kop.invoke(1, "acquire", None), kop.ok(1, "acquire", None)]
     a = wgl.analysis(M.mutex(), h)
     assert a["valid?"] is False and a["op"]["index"] == len(h) - 1
-    # memo-table path: the set model and multi-register through knossos.model.memo
+    # the set model and multi-register (unique elements, few keys: direct device models)
     s = [kop.invoke(0, "add", 1), kop.invoke(1, "add", 2), kop.ok(1, "add", 2), kop.invoke(2, "read", None),
          kop.ok(2, "read", [2]), kop.ok(0, "add", 1), kop.invoke(2, "read", None), kop.ok(2, "read", [1, 2])]
     assert wgl.analysis(M.set(), s)["valid?"] is True
@@ -466,18 +458,6 @@ def _narrow_expect(oracle, h, L, model=None, **kw):
                              branch_lists=kw.get("eager_reads", True), **kw)
 
 
-def _assert_narrow(got, exp, tag):
-    assert got["valid"] == exp["valid"], (tag, got["valid"], exp["valid"], got["cause"])
-    assert got["search_width"] == 1, tag
-    assert (got["probes"], got["visited"], got["backtracks"], got["max_depth"]) == (exp["probes"], exp["visited"], exp["expanded"], exp["max_stack"]), tag
-    if exp["valid"] == 1:
-        assert got["final_state"] == exp["final_state"], tag
-        if got["witness"] is not None:
-            assert np.array_equal(got["witness"], exp["witness"]), tag
-    elif exp["valid"] == 0:
-        assert got["fail_op"] == exp["fail_op"], tag
-
-
 @pytest.mark.parametrize("L", [8, 16, 32])
 def test_narrow_kernel_matches_its_oracle(native, oracle, L):
     """lanes_per_history = L: 64 / L histories per wavefront, each on the oracle's schedule for one config per iteration and
@@ -538,6 +518,20 @@ def test_narrow_kernel_wide_masks_and_other_models(native, oracle):
         core.Batch(reg, core.make_model(N.MODEL_REGISTER, N.NIL), core.make_opts(algorithm=N.ALG_WGL, lanes_per_history=8))
     with pytest.raises(N.TbcError):
         core.Batch(reg, core.make_model(N.MODEL_REGISTER, N.NIL), core.make_opts(algorithm=N.ALG_COMPETITION, lanes_per_history=8, search_width=4))
+
+
+def test_narrow_kernel_wide_masks_without_rule_tables(native, oracle):
+    """Register values past 30 switch the rule tables off (vpad 0), and a front record is then 8 words at every mask width -- the size
+    of the compact record, which exists at one mask word only: at two mask words the pack must write the plain record the kernel reads
+    there (tbc_internal.h front_is_compact; the mutex's case of it: tests/test_models_gpu.py)."""
+    hv = [columns.pair_events(synth.register_events(n_ops=1200, n_procs=24, seed=s, busy=0.15, info=0.05, n_values=40)) for s in range(3)]
+    assert all(64 < h.n_process <= 128 and int(h.a.max()) > 30 for h in hv)
+    for L in (8, 16):
+        with core.Batch(hv, gm(), core.make_opts(time_limit_ms=60000, algorithm=N.ALG_COMPETITION, lanes_per_history=L, max_steps=60000)) as b:
+            assert b.lanes_per_history() == L
+            res = b.run().results()
+        for i, (h, got) in enumerate(zip(hv, res)):
+            _assert_narrow(got, _narrow_expect(oracle, h, L, max_probes=60000), (L, h.n_process, i))
 
 
 def test_batches_in_flight_from_several_threads(native, oracle):
