@@ -1,5 +1,6 @@
 // ledger_kernels.h -- the O(micro-ops) part of tbc_ledger_check on the MI355X (gfx950): the kernel bodies.  ledger.hip compiles them
-// into libtbcheck.so and launches them; the host plan (which op is which row, the runs, the transfer ids, the arena) is ledger_plan.h.
+// into libtbcheck.so; their launches are lg::sequence at the end of this file; the host plan (which op is which row, the runs, the
+// transfer ids, the arena) is ledger_plan.h.
 // In launch order -- the kernel boundary is the only ordering between them, and no kernel holds an agent-scope fence:
 //
 //   lg_si_kernel            a workgroup of 256 per RUN of consecutive OK reads (grid-stride).  Lane = micro-op: 256 micro-ops a step, each
@@ -24,7 +25,7 @@
 //                           rows and the suspect lookups counted (ballot + popcount)
 //   lg_summary_kernel       one thread: counts, verdicts, the summary as the caller gets it
 // Ballots, lane reads, the workgroup barrier and index / thread go through wave_env.h / wave_env_wg.h; the atomics (on LDS words and on
-// global memory) are plain HIP, which tests/emu/emu_ledger.cpp states for the host emulator -- these very kernels run there lane by
+// global memory) are plain HIP, which tests/emu/oneshot_emu.h states for the host emulator -- these very kernels run there lane by
 // lane, with a window of a few words, against the host statement of jepsen/ledger.py (tests/test_ledger_emu.py).
 #pragma once
 #include "wave_env_wg.h"
@@ -234,3 +235,29 @@ __global__ __launch_bounds__(64) void lg_summary_kernel(LgArgs A) {
 }
 
 }  // namespace
+
+namespace lg {
+
+// Every kernel of the call in order, over a launcher (oneshot_plan.h): THE statement of the launches -- the library runs it over a
+// stream (ledger.hip), the tests over the emulator and over a recorder.  A kernel with nothing to do is not launched: no reads, no
+// invoked transfers, fewer than two final rows of a kind.  kWindowWords: the lookup kernel's LDS window.
+template <uint32_t kWindowWords, class Launcher>
+void sequence(Launcher& go, LgArgs A, unsigned long long fr_mops, unsigned long long fl_mops) {
+  A.grid_si = go.grid(A.n_runs, 16384u);
+  A.grid_lookup = go.grid(A.n_final_lookups, 4096u);
+  if (A.n_runs) go.launch(lg_si_kernel, A.grid_si, 256u, A);
+  if (A.n_transfers) go.launch(lg_table_build_kernel, (A.n_transfers + 255u) / 256u, 256u, A);
+  if (A.n_transfers && A.n_final_lookups) go.launch(lg_lookup_kernel<kWindowWords>, A.grid_lookup, 256u, A);
+  const auto rows_equal = [&](LgRows F, unsigned long long mops) {
+    if (F.n < 2u) return;
+    F.grid = std::max(1u, go.grid((mops + 255u) / 256u, 8192u));
+    go.launch(lg_rows_equal_kernel, F.grid, 256u, A, F);
+  };
+  rows_equal(LgRows{A.fr_lo, A.fr_cum, A.n_final_reads, 0u, A.fr_unlike}, fr_mops);
+  rows_equal(LgRows{A.fl_lo, A.fl_cum, A.n_final_lookups, 0u, A.fl_unlike}, fl_mops);
+  const uint32_t n_threads = std::max(A.n_reads, std::max(A.n_final_reads, A.n_final_lookups));
+  if (n_threads) go.launch(lg_finish_kernel, (n_threads + 255u) / 256u, 256u, A, n_threads);
+  go.launch(lg_summary_kernel, 1u, 64u, A);
+}
+
+}  // namespace lg

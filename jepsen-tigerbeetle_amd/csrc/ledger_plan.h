@@ -18,6 +18,7 @@
 #include <vector>
 #include "../../include/tbcheck.h"
 #include "enc_table.h"
+#include "oneshot_plan.h"
 #include "set_full_encode_plan.h"          // sfenc::table_slots
 
 namespace lg {
@@ -51,21 +52,21 @@ struct LgArgs {
 // the final rows of one kind, as lg_rows_equal_kernel takes them
 struct LgRows { const unsigned long long *lo, *cum; uint32_t n, grid; uint32_t* unlike; };
 
-// Every kernel of the call on `stream` (a hipStream_t: this header names no HIP type), in the order ledger_kernels.h gives; defined in
-// ledger.hip, the unit that holds the kernels.  fr_mops / fl_mops: the micro-ops of all final reads / final lookups.  The grids are its
-// to choose (grid_si, grid_lookup of `A` are ignored).
+// Every kernel of the call on `stream` (a hipStream_t: this header names no HIP type): lg::sequence of ledger_kernels.h over the
+// library's launcher; defined in ledger.hip, the unit that holds the kernels.  fr_mops / fl_mops: the micro-ops of all final reads /
+// final lookups.  The grids are the sequence's to choose (grid_si, grid_lookup of `A` are ignored).
 void launch(void* stream, LgArgs A, unsigned long long fr_mops, unsigned long long fl_mops);
 
-struct LgRegion { size_t at = 0, bytes = 0; };
-struct LgCursor { size_t at = 0; LgRegion take(size_t bytes) { const LgRegion r{at, bytes}; at += (bytes + 255) & ~(size_t)255; return r; } };
+using oneshot::Region;
+using LgRegion = Region;                   // (the name it had while this header held it: programs written against that still build)
 
 // The call's one arena, in order: the head the host makes (ONE image, one copy), the caller's micro-op columns, what the device
 // makes (zeroed before the kernels: the table's slots, the unlike bytes, the lookups' missing counts), the per-read results.
 struct LgArena {
-  LgRegion acc, summary, accounts, transfer, read_lo, read_cum, run_first, fr_lo, fr_cum, fl_lo, fl_cum;        // the head
-  LgRegion mop_id, mop_a, mop_b, mop_c, mop_flags;                                                              // the caller's
-  LgRegion slots, fr_unlike, fl_unlike, missing;                                                                // zeroed
-  LgRegion read_error, read_total, read_badness;
+  Region acc, summary, accounts, transfer, read_lo, read_cum, run_first, fr_lo, fr_cum, fl_lo, fl_cum;        // the head
+  Region mop_id, mop_a, mop_b, mop_c, mop_flags;                                                              // the caller's
+  Region slots, fr_unlike, fl_unlike, missing;                                                                // zeroed
+  Region read_error, read_total, read_badness;
   size_t bytes = 0;
   size_t head_bytes() const { return mop_id.at; }
   size_t zero_bytes() const { return read_error.at - slots.at; }
@@ -166,10 +167,9 @@ inline bool plan(const char* fn, const tbc_ledger_in* in, Plan& P, std::string& 
     r = e;
   }
   P.n_runs = (uint32_t)P.run_first.size() - 1u;
-  P.accounts.assign(in->accounts, in->accounts + in->n_accounts);
-  std::sort(P.accounts.begin(), P.accounts.end());
+  for (uint32_t k : oneshot::sorted_accounts(in->accounts, in->n_accounts)) P.accounts.push_back(in->accounts[k]);
   LgArena& A = P.arena;
-  LgCursor c;
+  oneshot::Cursor c;
   const size_t nm = (size_t)P.n_mops, R = P.n_reads, FR = P.n_final_reads, FL = P.n_final_lookups;
   A.acc = c.take(sizeof(LgAcc)); A.summary = c.take(sizeof(tbc_ledger_summary));
   A.accounts = c.take(P.accounts.size() * 8); A.transfer = c.take((size_t)P.n_transfers * 8);
@@ -198,12 +198,33 @@ inline std::vector<unsigned char> head_image(const Plan& P) {
   const LgArena& A = P.arena;
   std::vector<unsigned char> img(A.head_bytes(), 0);
   const LgAcc a = acc_start();
-  const auto put = [&](const LgRegion& r, const void* src) { if (r.bytes) std::copy((const unsigned char*)src, (const unsigned char*)src + r.bytes, img.begin() + r.at); };
+  const auto put = [&](const Region& r, const void* src) { oneshot::put(img, r, src); };
   put(A.acc, &a);
   put(A.accounts, P.accounts.data()); put(A.transfer, P.transfer.data());
   put(A.read_lo, P.read_lo.data()); put(A.read_cum, P.read_cum.data()); put(A.run_first, P.run_first.data());
   put(A.fr_lo, P.fr_lo.data()); put(A.fr_cum, P.fr_cum.data()); put(A.fl_lo, P.fl_lo.data()); put(A.fl_cum, P.fl_cum.data());
   return img;
+}
+
+// the kernels' arguments over an arena at `base`
+inline LgArgs args(const tbc_ledger_in* in, const Plan& P, char* base) {
+  const LgArena& L = P.arena;
+  const auto at = [&](const Region& r) { return base + r.at; };
+  LgArgs A{};
+  A.acc = (LgAcc*)at(L.acc); A.summary = (tbc_ledger_summary*)at(L.summary);
+  A.mop_id = (const long long*)at(L.mop_id); A.mop_a = (const long long*)at(L.mop_a); A.mop_b = (const long long*)at(L.mop_b);
+  A.mop_c = (const long long*)at(L.mop_c); A.mop_flags = (const uint8_t*)at(L.mop_flags);
+  A.accounts = (const long long*)at(L.accounts); A.n_accounts = in->n_accounts; A.negative_balances = in->negative_balances;
+  A.total_amount = in->total_amount;
+  A.read_lo = (const unsigned long long*)at(L.read_lo); A.read_cum = (const unsigned long long*)at(L.read_cum);
+  A.run_first = (const uint32_t*)at(L.run_first); A.n_reads = P.n_reads; A.n_runs = P.n_runs;
+  A.read_error = (uint8_t*)at(L.read_error); A.read_total = (long long*)at(L.read_total); A.read_badness = (long long*)at(L.read_badness);
+  A.transfer = (const long long*)at(L.transfer); A.slots = at(L.slots); A.n_transfers = P.n_transfers; A.tab_mask = P.tab_mask;
+  A.fl_lo = (const unsigned long long*)at(L.fl_lo); A.fl_cum = (const unsigned long long*)at(L.fl_cum); A.n_final_lookups = P.n_final_lookups;
+  A.missing = (uint32_t*)at(L.missing);
+  A.fr_lo = (const unsigned long long*)at(L.fr_lo); A.fr_cum = (const unsigned long long*)at(L.fr_cum); A.n_final_reads = P.n_final_reads;
+  A.fr_unlike = (uint32_t*)at(L.fr_unlike); A.fl_unlike = (uint32_t*)at(L.fl_unlike);
+  return A;
 }
 
 }  // namespace lg

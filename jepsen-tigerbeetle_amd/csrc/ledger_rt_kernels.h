@@ -1,5 +1,6 @@
 // ledger_rt_kernels.h -- the O(micro-ops) part of tbc_ledger_realtime on the MI355X (gfx950): the kernel bodies.  ledger_rt.hip compiles
-// them into libtbcheck.so and launches them; the host plan (pairing, statuses, the three streams of rows, the arena) is ledger_rt_plan.h;
+// them into libtbcheck.so; their launches are lgrt::sequence at the end of this file; the host plan (pairing, statuses, the three
+// streams of rows, the arena) is ledger_rt_plan.h;
 // the rules are stated in jepsen/ledger.py.  A micro-op of a stream gives two ENTRIES, credits (e & 1 = 0) then debits, each of a CLASS
 // side * n_accounts + account number and a VALUE: a transfer's amount (summed) or a read's counter as an order-preserving key (maximum).
 // What the query needs per class is its entries in position order with the inclusive running sum / maximum beside each: a STABLE
@@ -26,7 +27,7 @@
 //   rt_worst_kernel         lane = read (grid-stride): the EARLIEST read that holds each kind's greatest miss (atomic min of the read number)
 //   rt_summary_kernel       one thread: the summary as the caller gets it
 // Ballots, lane reads, the workgroup barrier and index / thread go through wave_env.h / wave_env_wg.h; the atomics are plain HIP, which
-// tests/emu/emu_ledger_rt.cpp states for the host emulator -- these very kernels run there lane by lane (tests/test_ledger_realtime_emu.py).
+// tests/emu/oneshot_emu.h states for the host emulator -- these very kernels run there lane by lane (tests/test_ledger_realtime_emu.py).
 #pragma once
 #include "wave_env_wg.h"
 #include "wg_scan.h"
@@ -296,3 +297,40 @@ __global__ __launch_bounds__(64) void rt_summary_kernel(RtArgs A) {
 }
 
 }  // namespace
+
+namespace lgrt {
+
+// Every kernel of the call in order, over a launcher (oneshot_plan.h): THE statement of the launches -- the library runs it over a
+// stream (ledger_rt.hip), the tests over the emulator and over a recorder.  A kernel with nothing to do is not launched: a stream
+// without entries, no reads; without accounts only the numbering runs (it counts the sides and the amounts).
+template <bool kReads, class Launcher>
+void stream_sequence(Launcher& go, const RtArgs& A, RtStream S, uint32_t count_sides) {
+  if (!S.n_entries) return;
+  S.grid = go.grid(S.n_chunks, 8192u);
+  go.launch(rt_number_kernel<kReads>, S.grid, 64u, A, S, count_sides);
+  if (!A.n_class) return;                                                   // (no account: every side was counted as naming none, and there is no list)
+  RtStream C = S;
+  C.grid = go.grid(A.n_class, 4096u);
+  go.launch(rt_carry_kernel<kReads>, C.grid, 256u, A, C);
+  go.launch(rt_offsets_kernel, 1u, 256u, A, S);
+  go.launch(rt_scan_kernel<kReads>, S.grid, 64u, A, S);
+}
+
+template <class Launcher>
+void sequence(Launcher& go, RtArgs A) {
+  stream_sequence<false>(go, A, A.s[kDefinite], 0u);
+  stream_sequence<false>(go, A, A.s[kPossible], 1u);
+  stream_sequence<true>(go, A, A.s[kReads], 0u);
+  if (A.n_read_mops) {
+    A.grid_query = go.grid((A.n_read_mops + 255u) / 256u, 16384u);
+    go.launch(rt_query_kernel, A.grid_query, 256u, A);
+  }
+  if (A.n_reads) {
+    const uint32_t grid = go.grid((A.n_reads + 255u) / 256u, 16384u);
+    go.launch(rt_count_kernel, grid, 256u, A, grid);
+    go.launch(rt_worst_kernel, grid, 256u, A, grid);
+  }
+  go.launch(rt_summary_kernel, 1u, 64u, A);
+}
+
+}  // namespace lgrt

@@ -17,8 +17,8 @@
 
 namespace lgrt {
 
-using lg::LgCursor;
-using lg::LgRegion;
+using oneshot::Region;
+using oneshot::Span;                       // (lgrt::Span, as it was named while this header held it)
 
 constexpr uint32_t kRtNone = 0xFFFFFFFFu;
 constexpr uint64_t kRtCarryWords = 1ull << 22;      // a stream's carried totals: chunks x classes at most (but one chunk at least)
@@ -62,17 +62,17 @@ struct RtArgs {
   long long *mop_lo, *mop_hi, *mop_floor;                         // [n_read_mops][2]
 };
 
-// Every kernel of the call on `stream` (a hipStream_t), in the order ledger_rt_kernels.h gives; defined in ledger_rt.hip.  The grids are its
-// to choose.
+// Every kernel of the call on `stream` (a hipStream_t): lgrt::sequence of ledger_rt_kernels.h over the library's launcher; defined in
+// ledger_rt.hip.  The grids are the sequence's to choose.
 void launch(void* stream, RtArgs A);
 
 // The call's one arena, in order: what the host makes (ONE image, one copy: the head, then the micro-op columns of the ops the kernels
 // look at, gathered), what the device adds into (zeroed before the kernels), what the kernels write in full.
 struct RtArena {
-  LgRegion acc, accounts, init, read_inv, row_lo[kStreams], row_cum[kStreams], row_pos[kStreams];                 // the head
-  LgRegion mop_id, mop_a, mop_b, mop_c, mop_flags;                                                                // the caller's
-  LgRegion carry_cnt[kStreams], carry_val[kStreams], off[kStreams], rt_bits, rt_miss;                             // zeroed
-  LgRegion summary, ent_cls[kStreams], ent_pos[kStreams], ent_val[kStreams], list_pos[kStreams], list_val[kStreams], mop_lo, mop_hi, mop_floor;
+  Region acc, accounts, init, read_inv, row_lo[kStreams], row_cum[kStreams], row_pos[kStreams];                 // the head
+  Region mop_id, mop_a, mop_b, mop_c, mop_flags;                                                                // the caller's
+  Region carry_cnt[kStreams], carry_val[kStreams], off[kStreams], rt_bits, rt_miss;                             // zeroed
+  Region summary, ent_cls[kStreams], ent_pos[kStreams], ent_val[kStreams], list_pos[kStreams], list_val[kStreams], mop_lo, mop_hi, mop_floor;
   size_t bytes = 0;
   size_t image_bytes() const { return carry_cnt[0].at; }
   size_t zero_bytes() const { return summary.at - carry_cnt[0].at; }
@@ -86,13 +86,9 @@ struct Rows {
   void push(uint64_t at, uint64_t n, uint32_t p) { lo.push_back(at); cum.push_back(cum.back() + n); pos.push_back(p); }
 };
 
-// micro-ops src .. src + n of the caller's columns lie at dst .. dst + n of the device's
-struct Span { uint64_t src, dst, n; };
-
-struct Plan {
+// (its Spans: the micro-ops the device gets are those of the :ok reads and of the transfers that did not fail)
+struct Plan : oneshot::Spans {
   uint32_t n_reads = 0, n_class = 0;
-  uint64_t n_mops = 0;                                // the micro-ops the device gets: those of the :ok reads and of the transfers that did not fail
-  std::vector<Span> spans;                            // ... in the caller's order, neighbours merged
   std::vector<uint32_t> partner;                      // [n_ops] the row of the op's completion / invocation, kRtNone
   std::vector<uint8_t> status;                        // [n_ops] of an invoked transfer: the TBC_LEDGER_T_* of its completion, TBC_LEDGER_T_INVOKE = open
   Rows rows[kStreams];
@@ -140,11 +136,7 @@ inline bool plan(const char* fn, const tbc_ledger_rt_in* rin, Plan& P, std::stri
     const bool transfer = in->type[i] == TBC_LEDGER_T_INVOKE && in->kind[i] == TBC_LEDGER_K_TRANSFER && P.status[i] != TBC_LEDGER_T_FAIL;
     const bool read = in->type[i] == TBC_LEDGER_T_OK && in->kind[i] == TBC_LEDGER_K_READ;
     if (!transfer && !read) continue;
-    const uint64_t lo = in->mop_off[i], n = in->mop_off[i + 1] - lo;
-    at[i] = P.n_mops;
-    if (n && !P.spans.empty() && P.spans.back().src + P.spans.back().n == lo) P.spans.back().n += n;
-    else if (n) P.spans.push_back(Span{lo, P.n_mops, n});
-    P.n_mops += n;
+    at[i] = P.push(in->mop_off[i], in->mop_off[i + 1] - in->mop_off[i]);
   }
   for (uint32_t i = 0; i < in->n_ops; i++) {
     const uint64_t n = in->mop_off[i + 1] - in->mop_off[i];
@@ -166,9 +158,7 @@ inline bool plan(const char* fn, const tbc_ledger_rt_in* rin, Plan& P, std::stri
   P.n_reads = (uint32_t)P.rows[kReads].lo.size();
   // the accounts, sorted, and init in that order
   const uint32_t nA = in->n_accounts;
-  std::vector<uint32_t> perm(nA);
-  for (uint32_t k = 0; k < nA; k++) perm[k] = k;
-  std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return in->accounts[a] < in->accounts[b]; });
+  const std::vector<uint32_t> perm = oneshot::sorted_accounts(in->accounts, nA);
   P.accounts.resize(nA); P.init.assign(2 * (size_t)nA, 0);
   for (uint32_t k = 0; k < nA; k++) {
     P.accounts[k] = in->accounts[perm[k]];
@@ -179,12 +169,12 @@ inline bool plan(const char* fn, const tbc_ledger_rt_in* rin, Plan& P, std::stri
   // the chunks: whole wavefronts' worth of entries, as many as keep chunks x classes carried totals within bounds
   const uint64_t chunks_max = std::max<uint64_t>(1, std::min<uint64_t>(chunks_cap, kRtCarryWords / std::max<uint32_t>(1u, P.n_class)));
   for (Rows& R : P.rows) {
-    const uint64_t entries = 2 * R.mops(), waves = (entries + 63u) / 64u;
-    R.chunk_entries = (uint32_t)(64u * std::max<uint64_t>(1, (waves + chunks_max - 1u) / chunks_max));
+    const uint64_t entries = 2 * R.mops();
+    R.chunk_entries = oneshot::chunk_size(entries, chunks_max);
     R.n_chunks = (uint32_t)((entries + R.chunk_entries - 1u) / R.chunk_entries);
   }
   RtArena& A = P.arena;
-  LgCursor c;
+  oneshot::Cursor c;
   const size_t nm = (size_t)P.n_mops, R = P.n_reads, Mr = (size_t)P.rows[kReads].mops(), C = P.n_class;
   A.acc = c.take(sizeof(RtAcc)); A.accounts = c.take((size_t)nA * 8); A.init = c.take(2 * (size_t)nA * 8); A.read_inv = c.take(R * 4);
   for (int k = 0; k < kStreams; k++) A.row_lo[k] = c.take(P.rows[k].lo.size() * 8);
@@ -220,13 +210,11 @@ inline std::vector<unsigned char> image(const tbc_ledger_rt_in* in, const Plan& 
   const RtArena& A = P.arena;
   std::vector<unsigned char> img(A.image_bytes(), 0);
   const RtAcc a = acc_start();
-  const auto put = [&](const LgRegion& r, const void* src) { if (r.bytes) std::copy((const unsigned char*)src, (const unsigned char*)src + r.bytes, img.begin() + r.at); };
+  const auto put = [&](const Region& r, const void* src) { oneshot::put(img, r, src); };
   put(A.acc, &a);
   put(A.accounts, P.accounts.data()); put(A.init, P.init.data()); put(A.read_inv, P.read_inv.data());
   for (int k = 0; k < kStreams; k++) { put(A.row_lo[k], P.rows[k].lo.data()); put(A.row_cum[k], P.rows[k].cum.data()); put(A.row_pos[k], P.rows[k].pos.data()); }
-  const auto gather = [&](const LgRegion& r, const void* src, size_t width) {
-    for (const Span& s : P.spans) std::copy((const unsigned char*)src + s.src * width, (const unsigned char*)src + (s.src + s.n) * width, img.begin() + r.at + s.dst * width);
-  };
+  const auto gather = [&](const Region& r, const void* src, size_t width) { P.gather(img, r, src, width); };
   gather(A.mop_id, in->ledger.mop_id, 8); gather(A.mop_a, in->ledger.mop_a, 8); gather(A.mop_b, in->ledger.mop_b, 8); gather(A.mop_c, in->ledger.mop_c, 8);
   gather(A.mop_flags, in->ledger.mop_flags, 1);
   return img;
@@ -235,7 +223,7 @@ inline std::vector<unsigned char> image(const tbc_ledger_rt_in* in, const Plan& 
 // the kernels' arguments over an arena at `base`
 inline RtArgs args(const tbc_ledger_rt_in* in, const Plan& P, char* base) {
   const RtArena& L = P.arena;
-  const auto at = [&](const LgRegion& r) { return base + r.at; };
+  const auto at = [&](const Region& r) { return base + r.at; };
   RtArgs A{};
   A.acc = (RtAcc*)at(L.acc); A.summary = (tbc_ledger_rt_summary*)at(L.summary);
   A.mop_id = (const long long*)at(L.mop_id); A.mop_a = (const long long*)at(L.mop_a); A.mop_b = (const long long*)at(L.mop_b);

@@ -1,5 +1,6 @@
 // ledger_snap_kernels.h -- tbc_ledger_snapshots on the MI355X (gfx950): the kernel bodies.  ledger_snap.hip compiles them into
-// libtbcheck.so and launches them; the host plan (the reads' rows, the gathered columns, the chunks, the arena) is ledger_snap_plan.h;
+// libtbcheck.so; their launches are lgsn::filter_sequence and lgsn::rest_sequence at the end of this file; the host plan (the reads'
+// rows, the gathered columns, the chunks, the arena) is ledger_snap_plan.h;
 // the rules are stated in jepsen/ledger.py ("Snapshot order").  A read is a dense ROW of C = 2 x n_accounts counters as
 // order-preserving keys (lg_key) with a bit per counter that says whether the read checks it.  The pairwise rule is O(R^2 C); a valid
 // history never pays it: for complete reads i before j in the order of (sum, read number), skewed(i, j) <=> some v_i[c] > v_j[c], so an
@@ -31,7 +32,7 @@
 //   sn_count_kernel, sn_worst_kernel, sn_summary_kernel   as rt_count / rt_worst / rt_summary: count, first, last, the greatest count and
 //                           the EARLIEST read that holds it, the pairs
 // Ballots, lane reads, barriers and index / thread go through wave_env.h / wave_env_wg.h; the atomics are plain HIP, which
-// tests/emu/emu_ledger_snap.cpp states for the host emulator -- these very kernels run there lane by lane.
+// tests/emu/oneshot_emu.h states for the host emulator -- these very kernels run there lane by lane.
 #pragma once
 #include "wave_env_wg.h"
 #include "wg_scan.h"
@@ -382,3 +383,52 @@ __global__ __launch_bounds__(64) void sn_summary_kernel(SnArgs A) {
 }
 
 }  // namespace
+
+namespace lgsn {
+
+// The kernels of the call in order, over a launcher (oneshot_plan.h): THE statement of the launches -- the library runs them over a
+// stream (ledger_snap.hip), the tests over the emulator and over a recorder.  Two sequences, because the host reads the candidates'
+// number between them.  A kernel with nothing to do is not launched: no reads -- only the summary; no accounts -- no counter, so no
+// sort, no scan and no candidate; no candidate -- no pair kernel.
+template <class Launcher>
+uint32_t grid_of(Launcher& go, unsigned long long items, uint32_t per, uint32_t cap) { return std::max(1u, go.grid((items + per - 1u) / per, cap)); }
+
+template <class Launcher>
+void filter_sequence(Launcher& go, const SnArgs& A) {
+  if (!A.n_reads) return;
+  const uint32_t grid_layout = grid_of(go, A.n_reads, 4u, 4096u);            // (a wavefront per read, four to a workgroup)
+  go.launch(sn_layout_kernel, grid_layout, 256u, A, grid_layout);
+  if (!A.n_class) return;
+  const uint32_t grid_sort = go.grid(A.sort_chunks, kSnSortChunksMax);      // (the plan cuts no more chunks than that)
+  for (uint32_t pass = 0; pass < kSnDigits; pass++) {
+    go.launch(sn_hist_kernel, grid_sort, 64u, A, pass, grid_sort);
+    go.launch(sn_carry_kernel, 1u, 256u, A);
+    go.launch(sn_scatter_kernel, grid_sort, 64u, A, pass, grid_sort);
+  }
+  const uint32_t grid_scan = grid_of(go, (unsigned long long)A.scan_chunks * A.n_class, 256u, 16384u);
+  const uint32_t grid_carry = go.grid(A.n_class, 4096u);
+  go.launch(sn_extremes_kernel, grid_scan, 256u, A, grid_scan);
+  go.launch(sn_scan_carry_kernel, grid_carry, 256u, A, grid_carry);
+  go.launch(sn_flag_kernel, grid_scan, 256u, A, grid_scan);
+  const uint32_t grid_reads = grid_of(go, A.n_reads, 256u, 16384u);
+  go.launch(sn_compact_kernel, grid_reads, 256u, A, grid_reads);
+}
+
+template <class Launcher>
+void rest_sequence(Launcher& go, const SnArgs& A, uint32_t n_candidates) {
+  if (A.n_reads) {
+    if (n_candidates) {
+      // the candidates in blocks of 256, the tiles of reads in as many slices as make about 2,048 workgroups
+      const uint32_t n_blocks = (n_candidates + 255u) / 256u, n_tiles = (A.n_reads + kSnTile - 1u) / kSnTile;
+      const uint32_t n_slices = std::max(1u, go.grid(n_tiles, 2048u / std::min<uint32_t>(n_blocks, 2048u)));
+      go.launch(sn_pair_kernel, n_blocks * n_slices, 256u, A, n_candidates, n_blocks, n_slices);
+    }
+    const uint32_t grid = grid_of(go, A.n_reads, 256u, 16384u);
+    go.launch(sn_keys_kernel, grid, 256u, A, grid);
+    go.launch(sn_count_kernel, grid, 256u, A, grid);
+    go.launch(sn_worst_kernel, grid, 256u, A, grid);
+  }
+  go.launch(sn_summary_kernel, 1u, 64u, A);
+}
+
+}  // namespace lgsn

@@ -14,8 +14,8 @@
 
 namespace lgsn {
 
-using lg::LgCursor;
-using lg::LgRegion;
+using oneshot::Region;
+using oneshot::Span;                       // (lgsn::Span, as it was named while this header held it)
 
 constexpr uint32_t kSnNone = 0xFFFFFFFFu;
 constexpr uint32_t kSnSortChunksMax = 256;          // the sort's chunks at most: a thread sums a digit's counts down them
@@ -47,33 +47,29 @@ struct SnArgs {
   uint32_t *skew_count, *skew_first, *skew_key; uint8_t* snap_flags;   // the results: [n_reads], [n_reads] (all ones at the start), [n_reads][2], [n_reads]
 };
 
-// The kernels on `stream` (a hipStream_t), in the order ledger_snap_kernels.h gives; defined in ledger_snap.hip.  launch_filter: lay out,
-// sort, scan, the candidates -- after it acc->n_candidates and acc->bad_values are final; launch_rest: the pairs (n_candidates > 0 only),
-// the keys and the summary.  The grids are the unit's to choose.
+// The kernels on `stream` (a hipStream_t): lgsn::filter_sequence and lgsn::rest_sequence of ledger_snap_kernels.h over the library's
+// launcher; defined in ledger_snap.hip.  launch_filter: lay out, sort, scan, the candidates -- after it acc->n_candidates and
+// acc->bad_values are final; launch_rest: the pairs (n_candidates > 0 only), the keys and the summary.  The grids are the sequences' to choose.
 void launch_filter(void* stream, const SnArgs& A);
 void launch_rest(void* stream, const SnArgs& A, uint32_t n_candidates);
 
 // The call's one arena, in order: what the host makes (ONE image, one copy: the head, then the reads' micro-op columns, gathered), what
 // starts as zeros, what starts as all ones, what the kernels write in full.
 struct SnArena {
-  LgRegion acc, accounts, acct_pos, row_cum;                                                              // the head
-  LgRegion mop_id, mop_a, mop_b, mop_flags;                                                                       // the caller's
-  LgRegion val, chk, cand_flag, skew_count;                                                                  // zeroed
-  LgRegion skew_first;                                                                                            // all ones
-  LgRegion summary, sort_key[2], sort_perm[2], hist, off, cmax, cmin, cand_list, skew_key, snap_flags;
+  Region acc, accounts, acct_pos, row_cum;                                                              // the head
+  Region mop_id, mop_a, mop_b, mop_flags;                                                                       // the caller's
+  Region val, chk, cand_flag, skew_count;                                                                  // zeroed
+  Region skew_first;                                                                                            // all ones
+  Region summary, sort_key[2], sort_perm[2], hist, off, cmax, cmin, cand_list, skew_key, snap_flags;
   size_t bytes = 0;
   size_t image_bytes() const { return val.at; }
   size_t zero_bytes() const { return skew_first.at - val.at; }
   size_t ones_bytes() const { return summary.at - skew_first.at; }
 };
 
-// micro-ops src .. src + n of the caller's columns lie at dst .. dst + n of the device's
-struct Span { uint64_t src, dst, n; };
-
-struct Plan {
+// (its Spans: the micro-ops the device gets are those of the :ok reads)
+struct Plan : oneshot::Spans {
   uint32_t n_reads = 0, n_class = 0, n_words = 0;
-  uint64_t n_mops = 0;                                // the micro-ops the device gets: those of the :ok reads
-  std::vector<Span> spans;                            // ... in the caller's order, neighbours merged
   std::vector<uint64_t> row_cum{0};                   // the reads' lengths summed: the device's columns hold the reads' micro-ops and nothing else
   std::vector<int64_t> accounts;                      // sorted
   std::vector<uint32_t> acct_pos;
@@ -90,11 +86,8 @@ inline bool plan(const char* fn, const tbc_ledger_in* in, Plan& P, std::string& 
   P = Plan{};
   for (uint32_t i = 0; i < in->n_ops; i++) {
     if (in->type[i] != TBC_LEDGER_T_OK || in->kind[i] != TBC_LEDGER_K_READ) continue;
-    const uint64_t lo = in->mop_off[i], n = in->mop_off[i + 1] - lo;
-    P.row_cum.push_back(P.n_mops + n);
-    if (n && !P.spans.empty() && P.spans.back().src + P.spans.back().n == lo) P.spans.back().n += n;
-    else if (n) P.spans.push_back(Span{lo, P.n_mops, n});
-    P.n_mops += n;
+    P.push(in->mop_off[i], in->mop_off[i + 1] - in->mop_off[i]);
+    P.row_cum.push_back(P.n_mops);
   }
   P.n_reads = (uint32_t)P.row_cum.size() - 1u;
   const uint32_t nA = in->n_accounts;
@@ -110,19 +103,17 @@ inline bool plan(const char* fn, const tbc_ledger_in* in, Plan& P, std::string& 
     err = buf;
     return false;
   }
-  P.acct_pos.resize(nA);
-  for (uint32_t k = 0; k < nA; k++) P.acct_pos[k] = k;
-  std::sort(P.acct_pos.begin(), P.acct_pos.end(), [&](uint32_t a, uint32_t b) { return in->accounts[a] < in->accounts[b]; });
+  P.acct_pos = oneshot::sorted_accounts(in->accounts, nA);
   P.accounts.resize(nA);
   for (uint32_t k = 0; k < nA; k++) P.accounts[k] = in->accounts[P.acct_pos[k]];
   // the sort's chunks: whole wavefronts' worth of reads, sort_chunks_cap of them at most
-  const uint64_t R = P.n_reads, waves = (R + 63u) / 64u, cap = std::max<uint32_t>(1u, std::min(sort_chunks_cap, kSnSortChunksMax));
-  P.sort_chunk_entries = (uint32_t)(64u * std::max<uint64_t>(1, (waves + cap - 1u) / cap));
+  const uint64_t R = P.n_reads;
+  P.sort_chunk_entries = oneshot::chunk_size(R, std::max<uint32_t>(1u, std::min(sort_chunks_cap, kSnSortChunksMax)));
   P.sort_chunks = (uint32_t)((R + P.sort_chunk_entries - 1u) / P.sort_chunk_entries);
   P.scan_rows = std::max<uint32_t>(1u, scan_rows);
   P.scan_chunks = (uint32_t)((R + P.scan_rows - 1u) / P.scan_rows);
   SnArena& A = P.arena;
-  LgCursor c;
+  oneshot::Cursor c;
   const size_t nm = (size_t)P.n_mops, C = P.n_class;
   A.acc = c.take(sizeof(SnAcc)); A.accounts = c.take((size_t)nA * 8); A.acct_pos = c.take((size_t)nA * 4);
   A.row_cum = c.take((R + 1) * 8);
@@ -151,12 +142,10 @@ inline std::vector<unsigned char> image(const tbc_ledger_in* in, const Plan& P) 
   const SnArena& A = P.arena;
   std::vector<unsigned char> img(A.image_bytes(), 0);
   const SnAcc a = acc_start();
-  const auto put = [&](const LgRegion& r, const void* src) { if (r.bytes) std::copy((const unsigned char*)src, (const unsigned char*)src + r.bytes, img.begin() + r.at); };
+  const auto put = [&](const Region& r, const void* src) { oneshot::put(img, r, src); };
   put(A.acc, &a);
   put(A.accounts, P.accounts.data()); put(A.acct_pos, P.acct_pos.data()); put(A.row_cum, P.row_cum.data());
-  const auto gather = [&](const LgRegion& r, const void* src, size_t width) {
-    for (const Span& s : P.spans) std::copy((const unsigned char*)src + s.src * width, (const unsigned char*)src + (s.src + s.n) * width, img.begin() + r.at + s.dst * width);
-  };
+  const auto gather = [&](const Region& r, const void* src, size_t width) { P.gather(img, r, src, width); };
   gather(A.mop_id, in->mop_id, 8); gather(A.mop_a, in->mop_a, 8); gather(A.mop_b, in->mop_b, 8); gather(A.mop_flags, in->mop_flags, 1);
   return img;
 }
@@ -164,7 +153,7 @@ inline std::vector<unsigned char> image(const tbc_ledger_in* in, const Plan& P) 
 // the kernels' arguments over an arena at `base`
 inline SnArgs args(const tbc_ledger_in* in, const Plan& P, char* base) {
   const SnArena& L = P.arena;
-  const auto at = [&](const LgRegion& r) { return base + r.at; };
+  const auto at = [&](const Region& r) { return base + r.at; };
   SnArgs A{};
   A.acc = (SnAcc*)at(L.acc); A.summary = (tbc_ledger_snap_summary*)at(L.summary);
   A.mop_id = (const long long*)at(L.mop_id); A.mop_a = (const long long*)at(L.mop_a); A.mop_b = (const long long*)at(L.mop_b);

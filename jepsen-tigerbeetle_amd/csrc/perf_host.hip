@@ -1,11 +1,7 @@
-// perf_host.hip -- tbc_perf_series and tbc_perf_plan_sizes, the entry points of the perf series (include/tbcheck.h): every rule of the
-// input on the host, the plan (perf_plan.h), ONE device allocation laid out by it, the zeroed head, the plan's partner column and the
-// caller's columns straight to their regions, the kernels (perf.hip) between two events, and the results back in one copy per array the
-// caller asked for.  One-shot and re-entrant: the stream, the events and the arena are the call's own and are gone on every path out.
-#include <hip/hip_runtime.h>
-#include <algorithm>
-#include <cstdint>
-#include <new>
+// perf_host.hip -- tbc_perf_series and tbc_perf_plan_sizes, the entry points of the perf series (include/tbcheck.h), the former over the
+// call frame of oneshot_call.h: every rule of the input on the host, the plan (perf_plan.h), the zeroed head, the plan's partner column
+// and the caller's columns straight to their regions, the kernels (perf.hip), and the results back in one copy per array the caller
+// asked for.
 #include <string>
 #include "oneshot_call.h"
 #include "perf_plan.h"
@@ -16,51 +12,24 @@ namespace {
 
 tbc_status pf_series(const char* fn, const tbc_perf_in* in, tbc_perf_out* out) {
   std::string err;
-  tbc_status st = pf::validate(fn, in, err);
-  if (st != TBC_OK) { set_error("%s", err.c_str()); return st; }
   pf::Plan P;
-  st = pf::plan(fn, in, P, err);
+  tbc_status st = pf::validate(fn, in, err);
+  if (st == TBC_OK) st = pf::plan(fn, in, P, err);
   if (st != TBC_OK) { set_error("%s", err.c_str()); return st; }
-  st = oneshot_check_device(in->device);
-  if (st != TBC_OK) return st;
   const pf::PfArena& L = P.arena;
   OneShotCall C;
-  TBC_ONESHOT_TRY(hipGetDevice(&C.device_before));
-  TBC_ONESHOT_TRY(hipSetDevice((int)in->device));
-  TBC_ONESHOT_TRY(hipMalloc(&C.arena, std::max<size_t>(L.bytes, 256)));
-  TBC_ONESHOT_TRY(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
-  TBC_ONESHOT_TRY(hipEventCreate(&C.ev0)); TBC_ONESHOT_TRY(hipEventCreate(&C.ev1));
-  char* const base = static_cast<char*>(C.arena);
-  const auto at = [&](const pf::PfRegion& r) { return base + r.at; };
-  uint64_t bytes_in = 0;
-  const auto put = [&](const pf::PfRegion& r, const void* src) {
-    bytes_in += r.bytes;
-    return r.bytes ? hipMemcpyAsync(at(r), src, r.bytes, hipMemcpyHostToDevice, C.stream) : hipSuccess;
-  };
-  // (the copies read pageable memory of the caller's and the plan's: the synchronise below ends them before the call returns)
-  TBC_ONESHOT_TRY(hipMemsetAsync(base, 0, L.zero_bytes(), C.stream));
-  TBC_ONESHOT_TRY(put(L.partner, P.partner.data()));
-  TBC_ONESHOT_TRY(put(L.time, in->time)); TBC_ONESHOT_TRY(put(L.process, in->process)); TBC_ONESHOT_TRY(put(L.type, in->type));
-  TBC_ONESHOT_TRY(put(L.f, in->f));
-  const pf::PfArgs A = pf::args(P, base);
-  TBC_ONESHOT_TRY(hipEventRecord(C.ev0, C.stream));
-  pf::launch(C.stream, A);
-  TBC_ONESHOT_TRY(hipGetLastError());
-  TBC_ONESHOT_TRY(hipEventRecord(C.ev1, C.stream));
-  const auto get = [&](void* dst, const pf::PfRegion& r) {
-    return dst && r.bytes ? hipMemcpyAsync(dst, at(r), r.bytes, hipMemcpyDeviceToHost, C.stream) : hipSuccess;
-  };
-  TBC_ONESHOT_TRY(get(out->op_latency, L.op_latency)); TBC_ONESHOT_TRY(get(out->op_outcome, L.op_outcome));
-  TBC_ONESHOT_TRY(get(out->op_open_after, L.op_open_after));
-  TBC_ONESHOT_TRY(get(out->q_count, L.q_count)); TBC_ONESHOT_TRY(get(out->q_value, L.q_value));
-  TBC_ONESHOT_TRY(get(out->rate_count, L.rate_count));
-  TBC_ONESHOT_TRY(get(out->open_last, L.open_last)); TBC_ONESHOT_TRY(get(out->open_fill, L.open_fill));
-  TBC_ONESHOT_TRY(get(&out->summary, L.summary));
-  TBC_ONESHOT_TRY(hipStreamSynchronize(C.stream));
-  float ms = 0;
-  TBC_ONESHOT_TRY(hipEventElapsedTime(&ms, C.ev0, C.ev1));
-  out->summary.ns_device = (uint64_t)(ms * 1e6);
-  out->summary.bytes_in = bytes_in;
+  if (C.open(in->device, L.bytes) != TBC_OK) return C.status;
+  C.fill(L.acc, 0, L.zero_bytes());
+  C.put(L.partner, P.partner.data());
+  C.put(L.time, in->time); C.put(L.process, in->process); C.put(L.type, in->type); C.put(L.f, in->f);
+  C.timed([&] { pf::launch(C.stream, pf::args(P, C.base())); });
+  C.get(out->op_latency, L.op_latency); C.get(out->op_outcome, L.op_outcome); C.get(out->op_open_after, L.op_open_after);
+  C.get(out->q_count, L.q_count); C.get(out->q_value, L.q_value); C.get(out->rate_count, L.rate_count);
+  C.get(out->open_last, L.open_last); C.get(out->open_fill, L.open_fill);
+  C.get(&out->summary, L.summary);
+  if (C.sync() != TBC_OK) return C.status;
+  out->summary.ns_device = C.ns_device();
+  out->summary.bytes_in = C.bytes_in;
   return TBC_OK;
 }
 
@@ -76,13 +45,4 @@ extern "C" tbc_status tbc_perf_plan_sizes(const tbc_perf_in* in, tbc_perf_sizes*
   return st;
 }
 
-extern "C" tbc_status tbc_perf_series(const tbc_perf_in* in, tbc_perf_out* out) {
-  const char* fn = "tbc_perf_series";
-  if (!in || !out) { set_error("%s: null argument", fn); return TBC_ERR_INVALID_ARG; }
-  try {
-    return pf_series(fn, in, out);
-  } catch (const std::bad_alloc&) {
-    set_error("%s: host memory", fn);
-    return TBC_ERR_OOM;
-  }
-}
+extern "C" tbc_status tbc_perf_series(const tbc_perf_in* in, tbc_perf_out* out) { return oneshot_entry("tbc_perf_series", in, out, pf_series); }

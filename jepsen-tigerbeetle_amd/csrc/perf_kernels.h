@@ -1,5 +1,6 @@
 // perf_kernels.h -- the O(ops) part of tbc_perf_series on the MI355X (gfx950): the kernel bodies.  perf.hip compiles them into
-// libtbcheck.so and launches them; the host plan (the partner column, t_max, the cell numbering, the chunks, the arena) is perf_plan.h.
+// libtbcheck.so; their launches are pf::sequence at the end of this file; the host plan (the partner column, t_max, the cell
+// numbering, the chunks, the arena) is perf_plan.h.
 // In launch order -- the kernel boundary is the only ordering between them, no kernel holds an agent-scope fence, none uses scratch:
 //
 //   pf_classify_kernel      lane = op (grid-stride).  Outcome (an invocation's: its partner's type; a completion's: its own), latency
@@ -36,7 +37,7 @@
 //                           lane shuffle --, else what the step before carried on)
 //   pf_summary_kernel       one thread: the counts, n_f, nb_all, n_plot, t_max
 // Ballots, lane reads, the workgroup barrier and index / thread go through wave_env.h / wave_env_wg.h; the atomics (on LDS words and on
-// global memory) and the lane shuffles (rs_pick's, the fill's) are plain HIP, which tests/emu/emu_perf.cpp states for the host emulator -- these very
+// global memory) and the lane shuffles (rs_pick's, the fill's) are plain HIP, which tests/emu/oneshot_emu.h and tests/emu/emu_perf.cpp state for the host emulator -- these very
 // kernels run there lane by lane, with a tile of 32 latencies, against the host statement of jepsen/perf.py (tests/test_perf_emu.py).
 #pragma once
 #include "wave_env_wg.h"
@@ -332,3 +333,31 @@ __global__ __launch_bounds__(64) void pf_summary_kernel(PfArgs A) {
 }
 
 }  // namespace
+
+namespace pf {
+
+// Every kernel of the call in order, over a launcher (oneshot_plan.h): THE statement of the launches -- the library runs it over a
+// stream (perf.hip), the tests over the emulator and over a recorder.  A kernel with nothing to do is not launched: no ops, no f's
+// (no client op: no cells and no classes).  (The two single-workgroup kernels ask for one block under a cap of one: exact from any launcher.)
+template <class Launcher>
+void sequence(Launcher& go, PfArgs A) {
+  const auto run = [&](void (*kernel)(PfArgs), uint64_t blocks, uint32_t cap, uint32_t threads) {
+    if (!blocks) return;
+    A.grid = go.grid(blocks, cap);
+    go.launch(kernel, A.grid, threads, A);
+  };
+  const uint64_t op_blocks = ((uint64_t)A.n_ops + 255u) / 256u;
+  run(pf_classify_kernel, op_blocks, 8192u, 256u);
+  if (A.n_class) run(pf_open_totals_kernel, A.n_chunks, 4096u, 64u);
+  run(pf_open_carry_kernel, A.n_chunks ? A.n_class : 0u, 16384u, 256u);
+  run(pf_open_scan_kernel, A.n_chunks, 4096u, 64u);                         // (without a client op it writes the zeros of op_open_after)
+  run(pf_cell_sum_kernel, A.n_scan_tiles, 8192u, 256u);
+  run(pf_tile_scan_kernel, A.n_scan_tiles ? 1u : 0u, 1u, 256u);
+  run(pf_cell_offsets_kernel, A.n_scan_tiles, 8192u, 256u);
+  run(pf_gather_kernel, A.n_cells ? op_blocks : 0u, 8192u, 256u);
+  run(pf_select_kernel, A.n_cells, 16384u, 256u);
+  run(pf_fill_kernel, A.n_class, 16384u, 64u);
+  run(pf_summary_kernel, 1u, 1u, 64u);
+}
+
+}  // namespace pf

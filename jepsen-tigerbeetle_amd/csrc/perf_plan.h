@@ -16,6 +16,7 @@
 #include <unordered_map>
 #include <vector>
 #include "../../include/tbcheck.h"
+#include "oneshot_plan.h"
 
 #ifndef PF_SELECT_TILE
 #define PF_SELECT_TILE TBC_PERF_SELECT_TILE
@@ -47,20 +48,20 @@ struct PfArgs {
   uint32_t* rate_count; uint32_t* carry; unsigned long long* open_word; int32_t *open_last, *open_fill;
 };
 
-// Every kernel of the call on `stream` (a hipStream_t: this header names no HIP type), in the order perf_kernels.h gives; defined in
-// perf.hip, the unit that holds the kernels.  The grids are its to choose (`grid` of `A` is ignored).
+// Every kernel of the call on `stream` (a hipStream_t: this header names no HIP type): pf::sequence of perf_kernels.h over the library's
+// launcher; defined in perf.hip, the unit that holds the kernels.  The grids are the sequence's to choose (`grid` of `A` is ignored).
 void launch(void* stream, PfArgs A);
 
-struct PfRegion { size_t at = 0, bytes = 0; };
-struct PfCursor { size_t at = 0; PfRegion take(size_t bytes) { const PfRegion r{at, bytes}; at += (bytes + 255) & ~(size_t)255; return r; } };
+using oneshot::Region;
+using PfRegion = Region;                   // (the name it had while this header held it: programs written against that still build)
 
 // The call's one arena, in order: what the device adds up or claims (zeroed before the kernels), the summary, the plan's partner
 // column and the caller's columns (copied in), and what the kernels write in full.
 struct PfArena {
-  PfRegion acc, q_count, rate_count, carry, open_word;                                       // zeroed
-  PfRegion summary;                                                                          // (the end of the zeroed part)
-  PfRegion partner, time, process, type, f;                                                  // copied in
-  PfRegion op_latency, op_outcome, op_open_after, q_off, q_cur, tile_sum, lat_cell, q_value, open_last, open_fill;
+  Region acc, q_count, rate_count, carry, open_word;                                       // zeroed
+  Region summary;                                                                          // (the end of the zeroed part)
+  Region partner, time, process, type, f;                                                  // copied in
+  Region op_latency, op_outcome, op_open_after, q_off, q_cur, tile_sum, lat_cell, q_value, open_last, open_fill;
   size_t bytes = 0;
   size_t zero_bytes() const { return summary.at; }
 };
@@ -135,13 +136,12 @@ inline tbc_status plan(const char* fn, const tbc_perf_in* in, Plan& P, std::stri
     open.erase(it);
   }
   // the open scan: chunks of whole wavefronts' worth of ops, as many as keep chunks x classes words of carried totals within bounds
-  const uint64_t waves = ((uint64_t)P.n_ops + 63u) / 64u;
   const uint64_t chunks_max = std::max<uint64_t>(1, std::min<uint64_t>(kPfChunksMax, kPfCarryWords / std::max<uint32_t>(1u, P.n_class)));
-  P.chunk_ops = (uint32_t)(64u * std::max<uint64_t>(1, (waves + chunks_max - 1u) / chunks_max));
+  P.chunk_ops = oneshot::chunk_size(P.n_ops, chunks_max);
   P.n_chunks = (uint32_t)(((uint64_t)P.n_ops + P.chunk_ops - 1u) / P.chunk_ops);
   P.n_scan_tiles = (P.n_cells + kPfScanTile - 1u) / kPfScanTile;
   PfArena& A = P.arena;
-  PfCursor c;
+  oneshot::Cursor c;
   const size_t n = P.n_ops, cells = P.n_cells, ccells = (size_t)P.n_class * P.nb_all;
   A.acc = c.take(sizeof(PfAcc)); A.q_count = c.take(cells * 4); A.rate_count = c.take(ccells * 4);
   A.carry = c.take((size_t)P.n_chunks * P.n_class * 4); A.open_word = c.take(ccells * 8);
@@ -158,7 +158,7 @@ inline tbc_status plan(const char* fn, const tbc_perf_in* in, Plan& P, std::stri
 // the kernels' arguments over an arena at `base`
 inline PfArgs args(const Plan& P, char* base) {
   const PfArena& L = P.arena;
-  const auto at = [&](const PfRegion& r) { return base + r.at; };
+  const auto at = [&](const Region& r) { return base + r.at; };
   PfArgs A{};
   A.acc = (PfAcc*)at(L.acc); A.summary = (tbc_perf_summary*)at(L.summary);
   A.time = (const long long*)at(L.time); A.process = (const int32_t*)at(L.process); A.type = (const uint8_t*)at(L.type);

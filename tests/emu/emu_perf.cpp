@@ -1,31 +1,16 @@
 // TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  emu_perf.cpp: tbc_perf_series on the CPU -- the validation and the host plan of
-// csrc/perf_plan.h, the arena laid out and filled as csrc/perf_host.hip does it (the zeroed head, the partner column, the caller's
-// columns; everything else a pattern, so that what a kernel does not write shows), and the kernels of csrc/perf_kernels.h (the very file
-// hipcc compiles into libtbcheck.so) under the wavefront / workgroup emulator, in the order and under the conditions of pf::launch
-// (csrc/perf.hip).  The select's LDS tile is PF_SELECT_TILE = 32 latencies here (the library's is TBC_PERF_SELECT_TILE), so that a cell
-// of a few dozen takes the radix select; every grid is capped at `grid_cap` workgroups, so that the grid strides run.
+// csrc/perf_plan.h, the arena laid out and filled in the steps of csrc/perf_host.hip (the zeroed head, the partner column, the caller's
+// columns), and the kernels of csrc/perf_kernels.h (the very file hipcc compiles into libtbcheck.so) under the wavefront / workgroup
+// emulator, launched by pf::sequence of that file -- the library's own statement -- over the emulator's launcher (oneshot_emu.h).  The
+// select's LDS tile is PF_SELECT_TILE = 32 latencies here (the library's is TBC_PERF_SELECT_TILE), so that a cell of a few dozen takes
+// the radix select; every grid that strides is capped at `grid_cap` workgroups, so that the strides run.
 // Built as a shared object by tests/test_perf_emu.py, which compares what comes back with the host statement of jepsen/perf.py.
-// The emulator headers have ballots, lane reads and the workgroup barrier; the atomics and the lane shuffle the kernels use are stated
-// here (between two rendezvous the emulator runs one lane at a time).
-#include <algorithm>
-#include <cstdint>
-#include <cstring>
-#include <functional>
-#include <string>
-#include <vector>
+// The lane shuffle the kernels use is stated here.
 #ifndef PF_SELECT_TILE
 #define PF_SELECT_TILE 32u
 #endif
-#include "tbcheck.h"
-#define TBC_EMU 1
-#include "wave_env_emu.h"
-#include "wave_env_wg_emu.h"
+#include "oneshot_emu.h"
 
-#define __global__
-#define __launch_bounds__(...)
-#define __forceinline__ inline
-#define __shared__ static
-#define __popcll(x) __builtin_popcountll(x)
 struct uint4 { uint32_t x, y, z, w; };
 static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
 // a lane shuffle is a rendezvous: every lane deposits, each reads its partner's deposit
@@ -36,15 +21,12 @@ static inline uint64_t emu_shfl(uint64_t v, int src_of_me, int site) {
 }
 #define __shfl_up(v, d) ((decltype(v))emu_shfl((uint64_t)(uint32_t)(v), (int)wv::lane_id() - (d), 300000 + __LINE__))
 #define __shfl(v, src) ((decltype(v))emu_shfl((uint64_t)(uint32_t)(v), (int)(src), 400000 + __LINE__))
-static inline uint32_t atomicMax(uint32_t* p, uint32_t v) { const uint32_t o = *p; if (v > o) *p = v; return o; }
-static inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) { const unsigned long long o = *p; if (v > o) *p = v; return o; }
 
 #include "perf_plan.h"
 #include "perf_kernels.h"
 
 namespace {
 std::string g_err;
-void trampoline(void* arg, uint32_t) { (*static_cast<std::function<void()>*>(arg))(); }
 }  // namespace
 
 // TBC_OK: done; otherwise the status the library gives (emu_pf_error says why)
@@ -56,44 +38,18 @@ extern "C" int emu_pf_series(const tbc_perf_in* in, tbc_perf_out* out, uint32_t 
   st = pf::plan("emu_pf_series", in, P, g_err);
   if (st != TBC_OK) return st;
   const pf::PfArena& L = P.arena;
-  std::vector<unsigned char> arena(L.bytes + 256, 0xA5);
-  char* const base = reinterpret_cast<char*>(arena.data());
-  const auto at = [&](const pf::PfRegion& r) { return base + r.at; };
-  std::memset(base, 0, L.zero_bytes());
-  const auto put = [&](const pf::PfRegion& r, const void* src) { if (r.bytes) std::memcpy(at(r), src, r.bytes); };
-  put(L.partner, P.partner.data()); put(L.time, in->time); put(L.process, in->process); put(L.type, in->type); put(L.f, in->f);
-  pf::PfArgs A = pf::args(P, base);
-  // ---- pf::launch, with every grid capped
-  uint64_t launches = 0;
-  const auto go = [&](void (*kernel)(pf::PfArgs), uint64_t blocks, bool capped, int waves) {
-    if (!blocks) return;
-    A.grid = (uint32_t)(capped ? std::min<uint64_t>(blocks, grid_cap ? grid_cap : 1u) : blocks);
-    std::function<void()> body = [&] { kernel(A); };
-    for (uint32_t b = 0; b < A.grid; b++) wv::run_workgroup(trampoline, &body, waves, b, seed + 1000u * launches + b);
-    launches++;
-  };
-  const uint64_t op_blocks = ((uint64_t)A.n_ops + 255u) / 256u;
-  go(pf_classify_kernel, op_blocks, true, 4);
-  if (A.n_class) go(pf_open_totals_kernel, A.n_chunks, true, 1);
-  go(pf_open_carry_kernel, A.n_chunks ? A.n_class : 0u, true, 4);
-  go(pf_open_scan_kernel, A.n_chunks, true, 1);
-  go(pf_cell_sum_kernel, A.n_scan_tiles, true, 4);
-  go(pf_tile_scan_kernel, A.n_scan_tiles ? 1u : 0u, true, 4);
-  go(pf_cell_offsets_kernel, A.n_scan_tiles, true, 4);
-  go(pf_gather_kernel, A.n_cells ? op_blocks : 0u, true, 4);
-  go(pf_select_kernel, A.n_cells, true, 4);
-  go(pf_fill_kernel, A.n_class, true, 1);
-  go(pf_summary_kernel, 1u, true, 1);
+  emu::Arena C(L.bytes);
+  C.fill(L.acc, 0, L.zero_bytes());
+  C.put(L.partner, P.partner.data()); C.put(L.time, in->time); C.put(L.process, in->process); C.put(L.type, in->type); C.put(L.f, in->f);
+  const pf::PfArgs A = pf::args(P, C.base());
+  emu::Launcher go(grid_cap, seed);
+  pf::sequence(go, A);
   // every cell's cursor has come to the end of the cell
-  {
-    const uint32_t *off = A.q_off, *cur = A.q_cur, *cnt = A.q_count;
-    for (uint32_t c = 0; c < A.n_cells; c++)
-      if (cur[c] != off[c] + cnt[c]) { g_err = "a cell's cursor is not at the cell's end"; return -1; }
-  }
-  const auto get = [&](void* dst, const pf::PfRegion& r) { if (dst && r.bytes) std::memcpy(dst, at(r), r.bytes); };
-  get(out->op_latency, L.op_latency); get(out->op_outcome, L.op_outcome); get(out->op_open_after, L.op_open_after);
-  get(out->q_count, L.q_count); get(out->q_value, L.q_value); get(out->rate_count, L.rate_count);
-  get(out->open_last, L.open_last); get(out->open_fill, L.open_fill); get(&out->summary, L.summary);
+  for (uint32_t c = 0; c < A.n_cells; c++)
+    if (A.q_cur[c] != A.q_off[c] + A.q_count[c]) { g_err = "a cell's cursor is not at the cell's end"; return -1; }
+  C.get(out->op_latency, L.op_latency); C.get(out->op_outcome, L.op_outcome); C.get(out->op_open_after, L.op_open_after);
+  C.get(out->q_count, L.q_count); C.get(out->q_value, L.q_value); C.get(out->rate_count, L.rate_count);
+  C.get(out->open_last, L.open_last); C.get(out->open_fill, L.open_fill); C.get(&out->summary, L.summary);
   out->summary.ns_device = 0; out->summary.bytes_in = 0;
   return 0;
 }

@@ -1,10 +1,12 @@
 // TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  ledger_plan.cpp: the host side of tbc_ledger_check without a device -- the validation and
 // the plan of csrc/ledger_plan.h (the very functions ledger_host.hip runs every call through) in a program of its own, the one to build
 // with -fsanitize=address,undefined (tests/test_ledger_columns.py does):
-//   g++ -std=c++17 -g -fsanitize=address,undefined -I include -I jepsen-tigerbeetle_amd/csrc tests/emu/ledger_plan.cpp -o ledger_plan && ./ledger_plan
+//   g++ -std=c++17 -g -fsanitize=address,undefined -I include -I tests/emu -I jepsen-tigerbeetle_amd/csrc tests/emu/ledger_plan.cpp -o ledger_plan && ./ledger_plan
 // It builds ledgers of many shapes (seeded), plans them and checks what can be checked without Python: the row tables against a plain
 // walk of the ops, the runs, the transfer ids, the arena's regions; then it breaks each rule of tbc_ledger_in in turn and looks at
-// the message.  The columns are exactly as long as the struct says, so a read past an end is the sanitizer's to see.
+// the message.  The columns are exactly as long as the struct says, so a read past an end is the sanitizer's to see.  And because it
+// includes the emulator program of the kernels (emu_ledger.cpp), it holds lg::sequence -- the launches the library makes -- to the list
+// of (kernel, grid, threads) written out below by hand, under the device's caps, on the edge shapes.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -12,7 +14,7 @@
 #include <set>
 #include <string>
 #include <vector>
-#include "ledger_plan.h"
+#include "emu_ledger.cpp"
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED %s (line %d)\n", #c, __LINE__); std::exit(1); } } while (0)
 
@@ -88,8 +90,8 @@ void look(const Ledger& L) {
   }
   for (size_t k = 1; k < P.accounts.size(); k++) CHECK(P.accounts[k - 1] < P.accounts[k]);
   // the arena: regions in order, 256 B starts, none overlapping, sized for what they hold
-  const lg::LgRegion* reg = reinterpret_cast<const lg::LgRegion*>(&P.arena);
-  const size_t n_reg = offsetof(lg::LgArena, bytes) / sizeof(lg::LgRegion);
+  const oneshot::Region* reg = reinterpret_cast<const oneshot::Region*>(&P.arena);
+  const size_t n_reg = offsetof(lg::LgArena, bytes) / sizeof(oneshot::Region);
   for (size_t k = 0; k < n_reg; k++) CHECK(reg[k].at % 256 == 0 && reg[k].at + reg[k].bytes <= (k + 1 < n_reg ? reg[k + 1].at : P.arena.bytes));
   CHECK(P.arena.mop_id.bytes == P.n_mops * 8 && P.arena.mop_flags.bytes == P.n_mops && P.arena.slots.bytes == P.tab_slots * 16);
   CHECK(P.arena.fr_unlike.bytes % 4 == 0 && P.arena.fr_unlike.bytes >= P.n_final_reads && P.arena.fl_unlike.bytes % 4 == 0 && P.arena.fl_unlike.bytes >= P.n_final_lookups);
@@ -100,6 +102,32 @@ void look(const Ledger& L) {
   std::memcpy(&acc, img.data() + P.arena.acc.at, sizeof acc);
   CHECK(acc.first[3] == 0xFFFFFFFFu && acc.lowest_key == ~0ull && acc.highest_key == 0 && acc.count[1] == 0);
   if (P.n_reads) CHECK(std::memcmp(img.data() + P.arena.read_lo.at, P.read_lo.data(), P.n_reads * 8) == 0);
+}
+
+// ---- the launches: lg::sequence over the recorder (it reads the plan's numbers alone, so the arguments are made directly)
+lg::LgArgs shape(uint32_t reads, uint32_t runs, uint32_t transfers, uint32_t final_reads, uint32_t final_lookups) {
+  lg::LgArgs A{};
+  A.n_reads = reads; A.n_runs = runs; A.n_transfers = transfers; A.n_final_reads = final_reads; A.n_final_lookups = final_lookups;
+  return A;
+}
+
+void launches() {
+  using R = emu::Recorder;
+  const R::Kernel si = R::of(lg_si_kernel), build = R::of(lg_table_build_kernel), lookup = R::of(lg_lookup_kernel<EMU_W>), rows = R::of(lg_rows_equal_kernel),
+                  finish = R::of(lg_finish_kernel), summary = R::of(lg_summary_kernel);
+  const auto record = [](const lg::LgArgs& A, uint64_t fr_mops, uint64_t fl_mops) { R go; lg::sequence<EMU_W>(go, A, fr_mops, fl_mops); return go; };
+  // no ops: only the summary
+  CHECK(record(shape(0, 0, 0, 0, 0), 0, 0).is({{summary, 1, 64}}));
+  // reads and nothing else; invoked transfers and nothing else (the table is built, nobody looks anything up)
+  CHECK(record(shape(5, 2, 0, 0, 0), 0, 0).is({{si, 2, 256}, {finish, 1, 256}, {summary, 1, 64}}));
+  CHECK(record(shape(0, 0, 300, 0, 0), 0, 0).is({{build, 2, 256}, {summary, 1, 64}}));
+  // fewer than two final rows of either kind: no comparison; one final lookup is still looked up
+  CHECK(record(shape(1, 1, 300, 1, 1), 8, 300).is({{si, 1, 256}, {build, 2, 256}, {lookup, 1, 256}, {finish, 1, 256}, {summary, 1, 64}}));
+  // two final rows of each kind, the reads' without a micro-op (one workgroup all the same); no invoked transfer: no lookup kernel
+  CHECK(record(shape(2, 1, 0, 2, 2), 0, 600).is({{si, 1, 256}, {rows, 1, 256}, {rows, 3, 256}, {finish, 1, 256}, {summary, 1, 64}}));
+  // one past each cap: 16,385 runs, 4,097 final lookups, 8,193 x 256 - 255 micro-ops of final lookups; 8,192 x 256 of final reads are at it
+  CHECK(record(shape(20000, 16385, 70000, 2, 4097), 8192ull * 256, 8192ull * 256 + 1).is(
+      {{si, 16384, 256}, {build, 274, 256}, {lookup, 4096, 256}, {rows, 8192, 256}, {rows, 8192, 256}, {finish, 79, 256}, {summary, 1, 64}}));
 }
 
 void refuse(tbc_ledger_in in, const char* needle) {
@@ -137,6 +165,7 @@ int main() {
   { Ledger M = L; M.mop_flags[5] = 2; refuse(M.in(), "unknown micro-op flags"); }
   { Ledger M = L; M.accounts = {5, 10, 5}; refuse(M.in(), "account 5 is listed twice"); }
   { Ledger M = L; M.id[7] = 15; refuse(M.in(), "op 5 (index"); refuse(M.in(), "names an id twice"); }
-  std::printf("%d ledgers planned and checked, 16 refusals\n", planned + 1);
+  launches();
+  std::printf("%d ledgers planned and checked, 16 refusals, the launches of 6 shapes\n", planned + 1);
   return 0;
 }

@@ -1,12 +1,14 @@
 // TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  ledger_rt_plan.cpp: the host side of tbc_ledger_realtime without a device -- the validation
 // and the plan of csrc/ledger_rt_plan.h (the very functions ledger_rt_host.hip runs every call through) in a program of its own, the one
 // to build with -fsanitize=address,undefined (tests/test_ledger_realtime_plan.py does):
-//   g++ -std=c++17 -g -fsanitize=address,undefined -I include -I jepsen-tigerbeetle_amd/csrc tests/emu/ledger_rt_plan.cpp -o ledger_rt_plan && ./ledger_rt_plan
+//   g++ -std=c++17 -g -fsanitize=address,undefined -I include -I tests/emu -I jepsen-tigerbeetle_amd/csrc tests/emu/ledger_rt_plan.cpp -o ledger_rt_plan && ./ledger_rt_plan
 // It builds ledgers of many shapes (seeded), plans them and checks what can be checked without Python: pairing and statuses against a
 // plain restatement, the three streams (order, positions, running lengths), the reads' invocations, the gathered micro-ops (spans, image), the sorted accounts
 // with init permuted, the chunks, the arena's regions; then it breaks each rule in turn and looks at the message.  The columns are exactly as
 // long as the struct says, so a read past an end is the sanitizer's to see -- and the transfers' micro-op columns are NOT THERE AT ALL
-// where only transfers have micro-ops (null pointers behind a fence of the reads' own), so the plan cannot have read one.
+// where only transfers have micro-ops (null pointers behind a fence of the reads' own), so the plan cannot have read one.  And because
+// it includes the emulator program of the kernels (emu_ledger_rt.cpp), it holds lgrt::sequence -- the launches the library makes -- to
+// the list of (kernel, grid, threads) written out below by hand, under the device's caps, on the edge shapes.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -14,7 +16,7 @@
 #include <map>
 #include <string>
 #include <vector>
-#include "ledger_rt_plan.h"
+#include "emu_ledger_rt.cpp"
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED %s (line %d)\n", #c, __LINE__); std::exit(1); } } while (0)
 
@@ -87,7 +89,7 @@ void look(const Ledger& L) {
   {
     uint64_t covered = 0;
     for (size_t k = 0; k < P.spans.size(); k++) {
-      const lgrt::Span& s = P.spans[k];
+      const oneshot::Span& s = P.spans[k];
       CHECK(s.n > 0 && s.dst == covered && (k == 0 || P.spans[k - 1].src + P.spans[k - 1].n < s.src));       // (neighbours are merged)
       for (uint64_t j = 0; j < s.n; j++) CHECK(src[s.dst + j] == s.src + j);
       covered += s.n;
@@ -131,8 +133,8 @@ void look(const Ledger& L) {
     CHECK(P.init[k] == (rin.init_credits ? rin.init_credits[src] : 0) && P.init[in.n_accounts + k] == (rin.init_debits ? rin.init_debits[src] : 0));
   }
   // the arena: regions in order, 256 B starts, none overlapping, sized for what they hold
-  const lg::LgRegion* reg = reinterpret_cast<const lg::LgRegion*>(&P.arena);
-  const size_t n_reg = offsetof(lgrt::RtArena, bytes) / sizeof(lg::LgRegion);
+  const oneshot::Region* reg = reinterpret_cast<const oneshot::Region*>(&P.arena);
+  const size_t n_reg = offsetof(lgrt::RtArena, bytes) / sizeof(oneshot::Region);
   for (size_t k = 0; k < n_reg; k++) CHECK(reg[k].at % 256 == 0 && reg[k].at + reg[k].bytes <= (k + 1 < n_reg ? reg[k + 1].at : P.arena.bytes));
   const lgrt::RtArena& A = P.arena;
   CHECK(A.mop_id.bytes == P.n_mops * 8 && A.mop_flags.bytes == P.n_mops && A.rt_bits.bytes % 4 == 0 && A.rt_bits.bytes >= P.n_reads && A.rt_miss.bytes == (size_t)P.n_reads * 24);
@@ -158,6 +160,39 @@ void look(const Ledger& L) {
   std::vector<char> fake(16);
   const lgrt::RtArgs K = lgrt::args(&rin, P, fake.data());
   CHECK((const char*)K.mop_floor == fake.data() + A.mop_floor.at && K.s[lgrt::kReads].n_entries == 2 * P.rows[lgrt::kReads].mops() && K.n_read_mops == P.rows[lgrt::kReads].mops());
+}
+
+// ---- the launches: lgrt::sequence over the recorder (it reads the plan's numbers alone, so the arguments are made directly)
+struct StreamShape { uint64_t entries; uint32_t chunks; };
+lgrt::RtArgs shape(StreamShape definite, StreamShape possible, StreamShape reads, uint32_t n_class, uint64_t read_mops, uint32_t n_reads) {
+  lgrt::RtArgs A{};
+  const StreamShape s[lgrt::kStreams] = {definite, possible, reads};
+  for (int k = 0; k < lgrt::kStreams; k++) { A.s[k].n_entries = s[k].entries; A.s[k].n_chunks = s[k].chunks; }
+  A.n_class = n_class; A.n_read_mops = read_mops; A.n_reads = n_reads;
+  return A;
+}
+
+void launches() {
+  using R = emu::Recorder;
+  const R::Kernel number = R::of(rt_number_kernel<false>), carry = R::of(rt_carry_kernel<false>), scan = R::of(rt_scan_kernel<false>),
+                  number_r = R::of(rt_number_kernel<true>), carry_r = R::of(rt_carry_kernel<true>), scan_r = R::of(rt_scan_kernel<true>),
+                  offsets = R::of(rt_offsets_kernel), query = R::of(rt_query_kernel), count = R::of(rt_count_kernel), worst = R::of(rt_worst_kernel),
+                  summary = R::of(rt_summary_kernel);
+  const auto record = [](const lgrt::RtArgs& A) { R go; lgrt::sequence(go, A); return go; };
+  // no ops: only the summary
+  CHECK(record(shape({0, 0}, {0, 0}, {0, 0}, 0, 0, 0)).is({{summary, 1, 64}}));
+  // no accounts: of a stream the numbering only (it counts the sides and the amounts); reads without a micro-op are counted still
+  CHECK(record(shape({10, 1}, {200, 4}, {0, 0}, 0, 0, 3)).is({{number, 1, 64}, {number, 4, 64}, {count, 1, 256}, {worst, 1, 256}, {summary, 1, 64}}));
+  // all of it: three streams of four kernels, the query, the counts
+  CHECK(record(shape({200, 2}, {300, 3}, {600, 5}, 6, 300, 40)).is(
+      {{number, 2, 64}, {carry, 6, 256}, {offsets, 1, 256}, {scan, 2, 64}, {number, 3, 64}, {carry, 6, 256}, {offsets, 1, 256}, {scan, 3, 64},
+       {number_r, 5, 64}, {carry_r, 6, 256}, {offsets, 1, 256}, {scan_r, 5, 64}, {query, 2, 256}, {count, 1, 256}, {worst, 1, 256}, {summary, 1, 64}}));
+  // transfers but no read: two streams, no query, no counts
+  CHECK(record(shape({128, 2}, {128, 2}, {0, 0}, 2, 0, 0)).is(
+      {{number, 2, 64}, {carry, 2, 256}, {offsets, 1, 256}, {scan, 2, 64}, {number, 2, 64}, {carry, 2, 256}, {offsets, 1, 256}, {scan, 2, 64}, {summary, 1, 64}}));
+  // one past each cap: 8,193 chunks, 4,097 classes, 16,385 x 256 read micro-ops, 16,385 x 256 reads
+  CHECK(record(shape({0, 0}, {0, 0}, {8193ull * 64, 8193}, 4097, 16385ull * 256, 16385u * 256u)).is(
+      {{number_r, 8192, 64}, {carry_r, 4096, 256}, {offsets, 1, 256}, {scan_r, 8192, 64}, {query, 16384, 256}, {count, 16384, 256}, {worst, 16384, 256}, {summary, 1, 64}}));
 }
 
 void refuse(tbc_ledger_rt_in in, const char* needle) {
@@ -235,6 +270,7 @@ int main() {
     for (const lgrt::Rows& R : P.rows) CHECK(R.n_chunks <= 2 && R.chunk_entries % 64 == 0 && (uint64_t)R.n_chunks * R.chunk_entries >= 2 * R.mops());
     CHECK(P.rows[lgrt::kReads].chunk_entries > 64);
   }
-  std::printf("%d ledgers planned and checked, 15 refusals\n", planned + 1);
+  launches();
+  std::printf("%d ledgers planned and checked, 15 refusals, the launches of 5 shapes\n", planned + 1);
   return 0;
 }

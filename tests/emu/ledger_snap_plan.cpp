@@ -7,7 +7,9 @@
 // scan, the arena's regions; it shows that the plan reads no micro-op (the columns are not there); it breaks each rule in turn and looks
 // at the message, the plan's own two refusals included.  And because it includes the emulator program of the kernels
 // (emu_ledger_snap.cpp), it runs every kernel of csrc/ledger_snap_kernels.h on each ledger under the sanitizers too -- an index past an
-// array's end in a kernel is the sanitizer's to see -- and holds the result to a plain pair-by-pair restatement of the rules.
+// array's end in a kernel is the sanitizer's to see -- and holds the result to a plain pair-by-pair restatement of the rules; and it
+// holds lgsn::filter_sequence and lgsn::rest_sequence -- the launches the library makes -- to the list of (kernel, grid, threads) written
+// out below by hand, under the device's caps, on the edge shapes.
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -79,7 +81,7 @@ void look(const Ledger& L, uint32_t grid_cap, uint32_t sort_cap, uint32_t scan_r
   CHECK(P.n_mops == src.size() && P.row_cum == cum && P.n_reads == cum.size() - 1);
   uint64_t covered = 0;
   for (size_t k = 0; k < P.spans.size(); k++) {
-    const lgsn::Span& s = P.spans[k];
+    const oneshot::Span& s = P.spans[k];
     CHECK(s.n > 0 && s.dst == covered && (k == 0 || P.spans[k - 1].src + P.spans[k - 1].n < s.src));       // (neighbours are merged)
     for (uint64_t j = 0; j < s.n; j++) CHECK(src[s.dst + j] == s.src + j);
     covered += s.n;
@@ -96,8 +98,8 @@ void look(const Ledger& L, uint32_t grid_cap, uint32_t sort_cap, uint32_t scan_r
   CHECK(P.sort_chunk_entries % 64 == 0 && P.sort_chunk_entries >= 64 && P.sort_chunks <= lgsn::kSnSortChunksMax);
   CHECK(P.sort_chunks == (R + P.sort_chunk_entries - 1) / P.sort_chunk_entries && P.scan_rows == lgsn::kSnScanRows && P.scan_chunks == (R + 63) / 64);
   // the arena: regions in order, 256 B starts, none overlapping, sized for what they hold
-  const lg::LgRegion* reg = reinterpret_cast<const lg::LgRegion*>(&P.arena);
-  const size_t n_reg = offsetof(lgsn::SnArena, bytes) / sizeof(lg::LgRegion);
+  const oneshot::Region* reg = reinterpret_cast<const oneshot::Region*>(&P.arena);
+  const size_t n_reg = offsetof(lgsn::SnArena, bytes) / sizeof(oneshot::Region);
   for (size_t k = 0; k < n_reg; k++) CHECK(reg[k].at % 256 == 0 && reg[k].at + reg[k].bytes <= (k + 1 < n_reg ? reg[k + 1].at : P.arena.bytes));
   const lgsn::SnArena& A = P.arena;
   CHECK(A.mop_id.bytes == P.n_mops * 8 && A.mop_flags.bytes == P.n_mops && A.val.bytes == R * P.n_class * 8 && A.chk.bytes == R * P.n_words * 4);
@@ -159,6 +161,46 @@ void look(const Ledger& L, uint32_t grid_cap, uint32_t sort_cap, uint32_t scan_r
   const tbc_ledger_snap_summary& s = out.summary;
   CHECK(s.read_count == R && s.n_partial == n_partial && s.valid == (n_skewed == 0) && s.bad_values == 0 && s.n_candidates == n_cand);
   CHECK(s.n_checked == n_checked && s.n_pairs == sum / 2 && s.skewed.count == n_skewed && s.bytes_in == img.size());
+}
+
+// ---- the launches: the two sequences over the recorder (they read the plan's numbers alone, so the arguments are made directly)
+lgsn::SnArgs shape(uint32_t reads, uint32_t n_class, uint32_t sort_chunks, uint32_t scan_chunks) {
+  lgsn::SnArgs A{};
+  A.n_reads = reads; A.n_class = n_class; A.sort_chunks = sort_chunks; A.scan_chunks = scan_chunks;
+  return A;
+}
+
+void launches() {
+  using R = emu::Recorder;
+  const R::Kernel layout = R::of(sn_layout_kernel), hist = R::of(sn_hist_kernel), carry = R::of(sn_carry_kernel), scatter = R::of(sn_scatter_kernel),
+                  extremes = R::of(sn_extremes_kernel), scan_carry = R::of(sn_scan_carry_kernel), flag = R::of(sn_flag_kernel), compact = R::of(sn_compact_kernel),
+                  pair = R::of(sn_pair_kernel), keys = R::of(sn_keys_kernel), count = R::of(sn_count_kernel), worst = R::of(sn_worst_kernel), summary = R::of(sn_summary_kernel);
+  const auto filter = [](const lgsn::SnArgs& A) { R go; lgsn::filter_sequence(go, A); return go; };
+  const auto rest = [](const lgsn::SnArgs& A, uint32_t n_candidates) { R go; lgsn::rest_sequence(go, A, n_candidates); return go; };
+  // the sort: eight passes of three kernels over `chunks` chunks
+  const auto with_sort = [&](R::Launch first, uint32_t chunks, std::vector<R::Launch> then) {
+    std::vector<R::Launch> all{first};
+    for (int pass = 0; pass < 8; pass++) { all.push_back({hist, chunks, 64}); all.push_back({carry, 1, 256}); all.push_back({scatter, chunks, 64}); }
+    all.insert(all.end(), then.begin(), then.end());
+    return all;
+  };
+  // no reads: only the summary
+  CHECK(filter(shape(0, 6, 0, 0)).is({}));
+  CHECK(rest(shape(0, 6, 0, 0), 0).is({{summary, 1, 64}}));
+  // no accounts: the layout only (it counts the partial reads); no sort, no scan, no candidate
+  CHECK(filter(shape(10, 0, 1, 1)).is({{layout, 3, 256}}));
+  CHECK(rest(shape(10, 0, 1, 1), 0).is({{keys, 1, 256}, {count, 1, 256}, {worst, 1, 256}, {summary, 1, 64}}));
+  // reads and accounts: the whole filter; then no candidate -- no pair kernel --, and one candidate: a slice per tile of 64 reads
+  CHECK(filter(shape(130, 4, 3, 3)).is(with_sort({layout, 33, 256}, 3, {{extremes, 1, 256}, {scan_carry, 4, 256}, {flag, 1, 256}, {compact, 1, 256}})));
+  CHECK(rest(shape(130, 4, 3, 3), 0).is({{keys, 1, 256}, {count, 1, 256}, {worst, 1, 256}, {summary, 1, 64}}));
+  CHECK(rest(shape(130, 4, 3, 3), 1).is({{pair, 3, 256}, {keys, 1, 256}, {count, 1, 256}, {worst, 1, 256}, {summary, 1, 64}}));
+  // one past each cap: 16,385 x 256 reads (the layout's 4,096 workgroups of four reads too), 4,097 counters, chunks x counters past
+  // 16,384 x 256; the sort's chunks are the plan's 256 at most
+  const lgsn::SnArgs big = shape(16385u * 256u, 4097, 256, 65540);
+  CHECK(filter(big).is(with_sort({layout, 4096, 256}, 256, {{extremes, 16384, 256}, {scan_carry, 4096, 256}, {flag, 16384, 256}, {compact, 16384, 256}})));
+  // ... the pairs: 4 blocks of candidates x 512 slices = 2,048 workgroups; 2,049 blocks and more take one slice each
+  CHECK(rest(big, 1000).is({{pair, 2048, 256}, {keys, 16384, 256}, {count, 16384, 256}, {worst, 16384, 256}, {summary, 1, 64}}));
+  CHECK(rest(big, 2049u * 256u).is({{pair, 2049, 256}, {keys, 16384, 256}, {count, 16384, 256}, {worst, 16384, 256}, {summary, 1, 64}}));
 }
 
 void refuse(const tbc_ledger_in& in, const char* needle, bool by_plan = false) {
@@ -243,6 +285,7 @@ int main() {
     CHECK(lgsn::plan("plan", &s, P, err) && P.sort_chunk_entries == 192 && P.sort_chunks == 209 && P.scan_chunks == 625);
     CHECK(lgsn::plan("plan", &s, P, err, 2, 1) && P.sort_chunks == 2 && P.sort_chunk_entries == 20032 && P.scan_chunks == 40000);
   }
-  std::printf("%d ledgers planned, run and checked, %d refusals\n", planned + 1, refusals);
+  launches();
+  std::printf("%d ledgers planned, run and checked, %d refusals, the launches of 4 shapes\n", planned + 1, refusals);
   return 0;
 }

@@ -1,11 +1,13 @@
 // TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  perf_plan.cpp: the host side of tbc_perf_series without a device -- the validation and the
 // plan of csrc/perf_plan.h (the very functions perf_host.hip runs every call through) in a program of its own, the one to build with
 // -fsanitize=address,undefined (tests/test_perf_host.py does):
-//   g++ -std=c++17 -g -fsanitize=address,undefined -I include -I jepsen-tigerbeetle_amd/csrc tests/emu/perf_plan.cpp -o perf_plan && ./perf_plan
+//   g++ -std=c++17 -g -fsanitize=address,undefined -I include -I tests/emu -I jepsen-tigerbeetle_amd/csrc tests/emu/perf_plan.cpp -o perf_plan && ./perf_plan
 // It builds histories of many shapes (seeded), plans them and checks what can be checked without Python: the partner column against a
 // plain quadratic pairing, t_max / nb_all / n_plot at the bucket edges, the chunks, the arena's regions; then it breaks each rule of
 // tbc_perf_in in turn and looks at the status and the message.  The columns are exactly as long as the struct says, so a read past an
-// end is the sanitizer's to see.
+// end is the sanitizer's to see.  And because it includes the emulator program of the kernels (emu_perf.cpp), it holds pf::sequence --
+// the launches the library makes -- to the list of (kernel, grid, threads) written out below by hand, under the device's caps, on the
+// edge shapes.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -13,7 +15,7 @@
 #include <initializer_list>
 #include <string>
 #include <vector>
-#include "perf_plan.h"
+#include "emu_perf.cpp"
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED %s (line %d)\n", #c, __LINE__); std::exit(1); } } while (0)
 
@@ -82,8 +84,8 @@ void look(const History& H) {
   CHECK(P.n_chunks <= 1u || (uint64_t)P.n_chunks * P.n_class <= pf::kPfCarryWords);
   CHECK(P.n_chunks <= pf::kPfChunksMax);
   // the arena: regions in order, 256 B starts, none overlapping, sized for what they hold
-  const pf::PfRegion* reg = reinterpret_cast<const pf::PfRegion*>(&P.arena);
-  const size_t n_reg = offsetof(pf::PfArena, bytes) / sizeof(pf::PfRegion);
+  const oneshot::Region* reg = reinterpret_cast<const oneshot::Region*>(&P.arena);
+  const size_t n_reg = offsetof(pf::PfArena, bytes) / sizeof(oneshot::Region);
   for (size_t k = 0; k < n_reg; k++) CHECK(reg[k].at % 256 == 0 && reg[k].at + reg[k].bytes <= (k + 1 < n_reg ? reg[k + 1].at : P.arena.bytes));
   const pf::PfArena& A = P.arena;
   CHECK(A.time.bytes == (size_t)n * 8 && A.partner.bytes == (size_t)n * 4 && A.f.bytes == (size_t)n * 2 && A.op_outcome.bytes == n);
@@ -92,6 +94,32 @@ void look(const History& H) {
   CHECK(A.zero_bytes() == A.summary.at && A.acc.at == 0);
   tbc_perf_sizes z{};
   CHECK(pf::sizes("plan", &in, z, err) == TBC_OK && z.n_ops == n && z.n_f == in.n_f && z.nb_all == P.nb_all && z.n_plot == P.n_plot && z.t_max == t_max);
+}
+
+// ---- the launches: pf::sequence over the recorder (it reads the plan's numbers alone, so the arguments are made directly)
+pf::PfArgs shape(uint32_t n_ops, uint32_t n_class, uint32_t n_chunks, uint32_t n_cells, uint32_t n_scan_tiles) {
+  pf::PfArgs A{};
+  A.n_ops = n_ops; A.n_class = n_class; A.n_chunks = n_chunks; A.n_cells = n_cells; A.n_scan_tiles = n_scan_tiles;
+  return A;
+}
+
+void launches() {
+  using R = emu::Recorder;
+  const R::Kernel classify = R::of(pf_classify_kernel), totals = R::of(pf_open_totals_kernel), carry = R::of(pf_open_carry_kernel), scan = R::of(pf_open_scan_kernel),
+                  cell_sum = R::of(pf_cell_sum_kernel), tile_scan = R::of(pf_tile_scan_kernel), offsets = R::of(pf_cell_offsets_kernel), gather = R::of(pf_gather_kernel),
+                  select = R::of(pf_select_kernel), fill = R::of(pf_fill_kernel), summary = R::of(pf_summary_kernel);
+  const auto record = [](const pf::PfArgs& A) { R go; pf::sequence(go, A); return go; };
+  // no ops: only the summary
+  CHECK(record(shape(0, 0, 0, 0, 0)).is({{summary, 1, 64}}));
+  // ops but no f (no client op): no cells and no classes; the open scan still writes the zeros of op_open_after
+  CHECK(record(shape(300, 0, 5, 0, 0)).is({{classify, 2, 256}, {scan, 5, 64}, {summary, 1, 64}}));
+  // all of it: 300 ops of 2 f's over 3 seconds
+  CHECK(record(shape(300, 6, 5, 6, 1)).is({{classify, 2, 256}, {totals, 5, 64}, {carry, 6, 256}, {scan, 5, 64}, {cell_sum, 1, 256}, {tile_scan, 1, 256},
+                                           {offsets, 1, 256}, {gather, 2, 256}, {select, 6, 256}, {fill, 6, 64}, {summary, 1, 64}}));
+  // one past each cap: 8,193 x 256 ops, 4,097 chunks, 16,385 classes, 16,385 cells, 8,193 tiles of cells
+  CHECK(record(shape(8193u * 256u, 16385, 4097, 16385, 8193)).is(
+      {{classify, 8192, 256}, {totals, 4096, 64}, {carry, 16384, 256}, {scan, 4096, 64}, {cell_sum, 8192, 256}, {tile_scan, 1, 256},
+       {offsets, 8192, 256}, {gather, 8192, 256}, {select, 16384, 256}, {fill, 16384, 64}, {summary, 1, 64}}));
 }
 
 void refuse(const tbc_perf_in& in, tbc_status want, const char* needle) {
@@ -146,6 +174,7 @@ int main() {
   { History M = L; M.time[1] = (1ll << 52) - 1; M.n_f = 200; refuse(M.in(), TBC_ERR_UNSUPPORTED, "2^31 cells or more"); }
   { History M = L; M.time[1] = (1ll << 52) - 1; M.n_f = 2; std::string err; tbc_perf_sizes z{}; const tbc_perf_in s = M.in();
     CHECK(pf::validate("p", &s, err) == TBC_OK && pf::sizes("p", &s, z, err) == TBC_OK && z.nb_all == 4503600u); }
-  std::printf("%d histories planned and checked, 12 refusals\n", planned + 1);
+  launches();
+  std::printf("%d histories planned and checked, 12 refusals, the launches of 4 shapes\n", planned + 1);
   return 0;
 }

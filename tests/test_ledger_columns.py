@@ -159,8 +159,10 @@ def test_valid_input_without_a_device_is_no_device(native):
 
 def test_the_plan_program_under_address_and_undefined_sanitizers(tmp_path):
     exe = str(tmp_path / "ledger_plan")
-    subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "jepsen-tigerbeetle_amd", "csrc"),
+    subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-Wno-unused-parameter",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "emu"), "-I", os.path.join(ROOT, "jepsen-tigerbeetle_amd", "csrc"),
                            os.path.join(ROOT, "tests", "emu", "ledger_plan.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "planned and checked" in out.stdout and not out.stderr, (out.stdout, out.stderr)
+    assert "the launches of 6 shapes" in out.stdout, out.stdout          # (lg::sequence over the recording launcher, against lists written by hand)

@@ -3,7 +3,8 @@ arena) in a stand-alone program, tests/emu/ledger_snap_plan.cpp, built with -fsa
 it plans is checked against a plain restatement, every refusal message is looked at -- validate's and the plan's own two (reads x
 counters of 2^31, 2^31 micro-ops of reads) --, and the plan is shown never to read a micro-op.  The program includes the emulator build
 of the kernels, so each planned ledger also runs through every kernel under the sanitizers and is held to the rules restated pair by
-pair."""
+pair; and it holds the two launch sequences the library runs over a recording launcher to hand-written lists of (kernel, grid,
+threads) on the edge shapes."""
 import os
 import subprocess
 
@@ -18,4 +19,4 @@ def test_the_plan_program_under_address_and_undefined_sanitizers(tmp_path):
                            os.path.join(ROOT, "tests", "emu", "ledger_snap_plan.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
-    assert "50 ledgers planned, run and checked, 11 refusals" in out.stdout, out.stdout
+    assert "50 ledgers planned, run and checked, 11 refusals, the launches of 4 shapes" in out.stdout, out.stdout

@@ -156,8 +156,10 @@ def test_perf_composes_three_members_that_answer_valid():
 
 def test_the_plan_program_under_address_and_undefined_sanitizers(tmp_path):
     exe = str(tmp_path / "perf_plan")
-    subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "jepsen-tigerbeetle_amd", "csrc"),
+    subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-Wno-unused-parameter",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "emu"), "-I", os.path.join(ROOT, "jepsen-tigerbeetle_amd", "csrc"),
                            os.path.join(ROOT, "tests", "emu", "perf_plan.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "planned and checked" in out.stdout and not out.stderr, (out.stdout, out.stderr)
+    assert "the launches of 4 shapes" in out.stdout, out.stdout          # (pf::sequence over the recording launcher, against lists written by hand)
