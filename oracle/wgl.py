@@ -482,21 +482,32 @@ def check_restart_pipeline(ops, model, width=4, budget=None, want_witness=False)
     return -1, r["fail_op"], r, tot, "no pass ended"
 
 
-def check_count_pipeline(ops, model, width=4, budget=None, want_witness=False, round_pairs=64, relaxed_sweep=False):
+def check_count_pipeline(ops, model, width=4, budget=None, want_witness=False, round_pairs=64, relaxed_sweep=False, pass_cap=0, on_pass=None):
     """What the library does with a history in count form (tbc_api.hip, batch_run_impl), pass by pass over wgl_count.c: the exact
     search under a budget of probes (the library: 32 per op of the batch's longest history); past it the RELAXED search (every
     class an unlimited supply: a superset of the linearizations), whose INVALID verdict bounds the failing completion from above;
     then the exact search of the PREFIX before that completion -- a linearization of it pins the failing op without exhausting
     the exact config space.  Returns (valid, fail_op, result of the last pass, counters summed over the passes, which passes ran),
-    or None where the count form does not apply."""
+    or None where the count form does not apply.
+    on_pass(name, result): called with every depth-first pass as it ends ("budgeted", "relaxed", "exact, no budget", "prefix") -- the library's
+    passes one by one.  pass_cap (a study knob, scripts/count_form_arm_hunt.py; the library has none): at most so many probes in each pass
+    after the budgeted one; a pass that runs into it ends the pipeline UNKNOWN, the arm named "<pass>, over the cap"."""
     n = len(ops["f"])
     budget = 32 * n if budget is None else budget
     tot = {"probes": 0, "visited": 0, "expanded": 0}
 
-    def add(r):
+    def add(r, name):
         for k in tot:
             tot[k] += r[k]
+        if on_pass is not None:
+            on_pass(name, r)
         return r
+
+    def late(name, **kw):
+        return add(check_count(ops, model, width=width, round_pairs=round_pairs, max_probes=pass_cap, **kw), name)
+
+    def over(r, name):
+        return -1, r["fail_op"], r, tot, name + ", over the cap"
     # relaxed_sweep (the library for a handful of histories, nobody asking for a witness or a schedule: tbc_batch::rsweep): the RELAXED
     # LEVEL SWEEP in front -- a refuted history goes straight to the prefix search (it is never searched exactly under a budget, nor
     # relaxed depth-first), one it finds valid under the relaxation skips the relaxed depth-first search; the sweep's own probes are not
@@ -510,7 +521,9 @@ def check_count_pipeline(ops, model, width=4, budget=None, want_witness=False, r
             t = completion_rank(ops, sw["fail_op"])
             if t == 0:
                 return 0, sw["fail_op"], sw, tot, "relaxed sweep"
-            g = add(check_count(ops, model, width=width, want_witness=False, target=t, round_pairs=round_pairs))
+            g = late("prefix", want_witness=False, target=t)
+            if g["valid"] == -1 and pass_cap:
+                return over(g, "prefix")
             if g["valid"] == 1:
                 return 0, sw["fail_op"], g, tot, "relaxed sweep, prefix"
             return g["valid"], g["fail_op"], g, tot, "relaxed sweep, prefix exhausted"
@@ -518,20 +531,24 @@ def check_count_pipeline(ops, model, width=4, budget=None, want_witness=False, r
     g = check_count(ops, model, width=width, want_witness=want_witness, max_probes=budget, round_pairs=round_pairs)
     if g is None:
         return None
-    add(g)
+    add(g, "budgeted")
     if g["valid"] != -1:
         return g["valid"], g["fail_op"], g, tot, "exact"
-    if swept_valid:
-        g = add(check_count(ops, model, width=width, want_witness=want_witness, round_pairs=round_pairs))
-        return g["valid"], g["fail_op"], g, tot, "exact, no budget"
-    r = add(check_count(ops, model, width=width, want_witness=False, relaxed=True, round_pairs=round_pairs))
-    if r["valid"] == 1:
-        g = add(check_count(ops, model, width=width, want_witness=want_witness, round_pairs=round_pairs))
+    if not swept_valid:
+        r = late("relaxed", want_witness=False, relaxed=True)
+        if r["valid"] == -1 and pass_cap:
+            return over(r, "relaxed")
+    if swept_valid or r["valid"] == 1:
+        g = late("exact, no budget", want_witness=want_witness)
+        if g["valid"] == -1 and pass_cap:
+            return over(g, "exact, no budget")
         return g["valid"], g["fail_op"], g, tot, "exact, no budget"
     t = completion_rank(ops, r["fail_op"])
     if t == 0:
         return 0, r["fail_op"], r, tot, "relaxed"
-    g = add(check_count(ops, model, width=width, want_witness=False, target=t, round_pairs=round_pairs))
+    g = late("prefix", want_witness=False, target=t)
+    if g["valid"] == -1 and pass_cap:
+        return over(g, "prefix")
     if g["valid"] == 1:
         return 0, r["fail_op"], g, tot, "prefix"
     return g["valid"], g["fail_op"], g, tot, "prefix exhausted"
