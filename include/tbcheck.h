@@ -43,7 +43,8 @@ extern "C" {
  * Still 2, additive: the word that was reserved0 (must be 0) is tbc_opts.list_order, 0 = the library's choice; tbc_batch_list_order().
  * Still 2, additive (round 6): tbc_batch_map_input / _submit_input / _reload / _input_info (fresh histories into a batch's arenas),
  * tbc_comm_* (the sharded sweep's exchange behind the C-ABI); tbc_setfull_create_rows takes its exception lists in any order again.
- * Still 2, additive: tbc_ledger_snapshots and its structs. */
+ * Still 2, additive: tbc_ledger_snapshots and its structs.
+ * Still 2, additive: tbc_ledger_journal and its structs. */
 #define TBC_ABI_VERSION 2u
 
 /* ------------------------------------------------------------------ status */
@@ -990,6 +991,66 @@ typedef struct tbc_ledger_snap_out {      /* arrays caller-allocated, each optio
   tbc_ledger_snap_summary summary;
 } tbc_ledger_snap_out;
 tbc_status tbc_ledger_snapshots(const tbc_ledger_in* in, tbc_ledger_snap_out* out);
+
+/* ------------------------------------------------------------------- ledger: the journal audit
+ * An :ok :l-t lookup returns the ledger's JOURNAL: every transfer's id, debit-acct, credit-acct and amount.  tbc_ledger_check asks one
+ * thing of it, and only of the final lookups (does it hold every invoked id).  This entry point audits EVERY :ok lookup, entry by
+ * entry, against the transfers as they were invoked, against real time, and against the balances the reads returned.  THE RULES ARE
+ * STATED ONCE, in the docstring of jepsen/ledger.py ("Journal audit"): records, lookups, entry_bits, present / repeated / failed /
+ * early / lost / vanished, the books, reads ahead of and behind a lookup, the summary, the ranges.
+ * Input: a tbc_ledger_rt_in, as tbc_ledger_realtime takes it (the columns, process, the inits, ok_transfers_apply).
+ * Rows: transfer micro-ops are those of the ops with INVOKE && kind == TRANSFER, in column order; lookups are the ops with OK && kind ==
+ * LOOKUP, final or not, in history order (tbc_ledger_check numbers only the final ones); entries are the lookups' micro-ops in column
+ * order; reads are numbered as for tbc_ledger_check.
+ *   entry_bits[e]        1 unknown, 2 altered
+ *   lk_counts[l][k]      k = TBC_LEDGER_JN_*: entries (unknown, altered, repeated), records (failed, early, lost, vanished), reads
+ *                        (ahead, behind)
+ *   lk_present[l]        the records present in lookup l
+ *   lk_vector[l][c]      the books of lookup l, c = 2 x (the account's position in `accounts`) + (0 credits-posted, 1 debits-posted)
+ *   rd_bits[r]           1 ahead of some lookup, 2 behind some lookup;  rd_first[r][2]  the least lookup number of each, TBC_NO_OP
+ *   xfer_present / early / lost / vanished[m]   per transfer micro-op, numbers of lookups; 0 for a reinvoked micro-op
+ *   xfer_flags[m]        1 reinvoked, 2 nil
+ * The host plans what is O(ops) (csrc/ledger_journal_plan.h) and reads no transfer or lookup micro-op; the device gets id, a, b, c and
+ * flags of the transfer micro-ops and of the entries (33 bytes each) and id, a, b and flags of the reads' (25 bytes), and does the rest
+ * (csrc/ledger_journal_kernels.h).  Every rule of tbc_ledger_realtime's input, and fewer than 2^31 transfer micro-ops, fewer than 2^31
+ * entries a lookup, lookups x ceil(transfer micro-ops / 32) < 2^31 and reads x counters < 2^31: TBC_ERR_INVALID_ARG before any device
+ * call, the message names the entry point and the op.  An amount of a non-nil record outside [0, 2^31) is counted ON THE DEVICE:
+ * TBC_ERR_UNSUPPORTED, no results, summary.bad_amounts says how many.  No gfx950 device: TBC_ERR_NO_DEVICE (no CPU fallback).
+ * One-shot and re-entrant as tbc_ledger_check is. */
+enum { TBC_LEDGER_JN_UNKNOWN = 0, TBC_LEDGER_JN_ALTERED = 1, TBC_LEDGER_JN_REPEATED = 2, TBC_LEDGER_JN_FAILED = 3, TBC_LEDGER_JN_EARLY = 4,
+       TBC_LEDGER_JN_LOST = 5, TBC_LEDGER_JN_VANISHED = 6, TBC_LEDGER_JN_AHEAD = 7, TBC_LEDGER_JN_BEHIND = 8, TBC_LEDGER_JN_KINDS = 9 };
+#define TBC_LEDGER_JN_ENTRY_UNKNOWN 1u
+#define TBC_LEDGER_JN_ENTRY_ALTERED 2u
+#define TBC_LEDGER_JN_XFER_REINVOKED 1u
+#define TBC_LEDGER_JN_XFER_NIL 2u
+#define TBC_LEDGER_JN_READ_AHEAD 1u
+#define TBC_LEDGER_JN_READ_BEHIND 2u
+
+typedef struct tbc_ledger_journal_summary {
+  uint32_t n_lookups, n_xfer_mops, n_records, n_reinvoked;
+  uint32_t foreign_sides;                                 /* sides of the records that name no account (a nil record: both); skipped */
+  uint32_t bad_amounts;                                   /* amounts of non-nil records outside [0, 2^31) */
+  uint32_t read_count, valid;                             /* valid: every total is 0 */
+  tbc_ledger_errors errors[TBC_LEDGER_JN_KINDS];          /* lookup numbers; worst = the greatest count, ties the earliest */
+  uint64_t totals[TBC_LEDGER_JN_KINDS];                   /* lk_counts summed over the lookups */
+  uint64_t n_entries;
+  uint64_t n_checked;                                     /* read micro-ops checked */
+  uint64_t ns_device;                                     /* the kernels, between HIP events */
+  uint64_t bytes_in;                                      /* copied to the device */
+} tbc_ledger_journal_summary;
+
+typedef struct tbc_ledger_journal_out {   /* arrays caller-allocated, each optional (NULL = not wanted) */
+  uint8_t* entry_bits;                    /* [n_entries] */
+  uint32_t* lk_counts;                    /* [n_lookups][TBC_LEDGER_JN_KINDS] */
+  uint32_t* lk_present;                   /* [n_lookups] */
+  int64_t* lk_vector;                     /* [n_lookups][2 * n_accounts] */
+  uint8_t* rd_bits;                       /* [n_ok_reads] */
+  uint32_t* rd_first;                     /* [n_ok_reads][2] */
+  uint32_t *xfer_present, *xfer_early, *xfer_lost, *xfer_vanished;   /* [n_xfer_mops] */
+  uint8_t* xfer_flags;                    /* [n_xfer_mops] */
+  tbc_ledger_journal_summary summary;
+} tbc_ledger_journal_out;
+tbc_status tbc_ledger_journal(const tbc_ledger_rt_in* in, tbc_ledger_journal_out* out);
 
 /* ------------------------------------------------------------------- perf: the series behind the reference's perf plots
  * checker/perf.clj composes latency-graph, rate-graph and open-ops-graph into every test.  What it PLOTS is out of scope (gnuplot,

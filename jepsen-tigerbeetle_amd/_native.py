@@ -270,6 +270,29 @@ class LedgerSnapOut(C.Structure):
                 ("snap_flags", C.POINTER(C.c_uint8)), ("summary", LedgerSnapSummary)]
 
 
+# tbc_ledger_journal: the lookups of a ledger audited against the transfers, real time and the reads (include/tbcheck.h); its input is
+# a LedgerRtIn
+(LEDGER_JN_UNKNOWN, LEDGER_JN_ALTERED, LEDGER_JN_REPEATED, LEDGER_JN_FAILED, LEDGER_JN_EARLY, LEDGER_JN_LOST, LEDGER_JN_VANISHED,
+ LEDGER_JN_AHEAD, LEDGER_JN_BEHIND, LEDGER_JN_KINDS) = range(10)
+LEDGER_JN_ENTRY_UNKNOWN, LEDGER_JN_ENTRY_ALTERED = 1, 2
+LEDGER_JN_XFER_REINVOKED, LEDGER_JN_XFER_NIL = 1, 2
+LEDGER_JN_READ_AHEAD, LEDGER_JN_READ_BEHIND = 1, 2
+
+
+class LedgerJournalSummary(C.Structure):
+    _fields_ = [("n_lookups", C.c_uint32), ("n_xfer_mops", C.c_uint32), ("n_records", C.c_uint32), ("n_reinvoked", C.c_uint32),
+                ("foreign_sides", C.c_uint32), ("bad_amounts", C.c_uint32), ("read_count", C.c_uint32), ("valid", C.c_uint32),
+                ("errors", LedgerErrors * LEDGER_JN_KINDS), ("totals", C.c_uint64 * LEDGER_JN_KINDS), ("n_entries", C.c_uint64),
+                ("n_checked", C.c_uint64), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64)]
+
+
+class LedgerJournalOut(C.Structure):
+    _fields_ = [("entry_bits", C.POINTER(C.c_uint8)), ("lk_counts", C.POINTER(C.c_uint32)), ("lk_present", C.POINTER(C.c_uint32)),
+                ("lk_vector", C.POINTER(C.c_int64)), ("rd_bits", C.POINTER(C.c_uint8)), ("rd_first", C.POINTER(C.c_uint32)),
+                ("xfer_present", C.POINTER(C.c_uint32)), ("xfer_early", C.POINTER(C.c_uint32)), ("xfer_lost", C.POINTER(C.c_uint32)),
+                ("xfer_vanished", C.POINTER(C.c_uint32)), ("xfer_flags", C.POINTER(C.c_uint8)), ("summary", LedgerJournalSummary)]
+
+
 # tbc_perf_series: the series behind the reference's perf plots from op columns (include/tbcheck.h TBC_PERF_*)
 PERF_T_INVOKE, PERF_T_OK, PERF_T_FAIL, PERF_T_INFO = 0, 1, 2, 3
 PERF_O_NONE = 0
@@ -373,6 +396,7 @@ SYMBOLS = {
     "tbc_ledger_check": (C.c_int, [C.POINTER(LedgerIn), C.POINTER(LedgerOut)]),
     "tbc_ledger_realtime": (C.c_int, [C.POINTER(LedgerRtIn), C.POINTER(LedgerRtOut)]),
     "tbc_ledger_snapshots": (C.c_int, [C.POINTER(LedgerIn), C.POINTER(LedgerSnapOut)]),
+    "tbc_ledger_journal": (C.c_int, [C.POINTER(LedgerRtIn), C.POINTER(LedgerJournalOut)]),
     "tbc_perf_plan_sizes": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfSizes)]),
     "tbc_perf_series": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfOut)]),
     "tbc_batch_destroy": (None, [C.c_void_p]),

@@ -113,23 +113,30 @@ inline bool validate(const char* fn, const tbc_ledger_rt_in* in, std::string& er
   return true;
 }
 
-// (the input has passed `validate`.)  false: too much for one call (`err` says what)
-// chunks_cap: the most chunks a stream is cut into (the tests' emulator passes a few, so that a chunk is several wavefronts' worth)
-inline bool plan(const char* fn, const tbc_ledger_rt_in* rin, Plan& P, std::string& err, uint32_t chunks_cap = kRtChunksMax) {
+// Pairing by process (knossos.history/pair-index), which tbc_ledger_journal's plan shares: partner[i] the row of op i's completion /
+// invocation, kRtNone; status[i] of an invoked transfer the TBC_LEDGER_T_* of its completion, TBC_LEDGER_T_INVOKE = open
+inline void pair(const tbc_ledger_rt_in* rin, std::vector<uint32_t>& partner, std::vector<uint8_t>& status) {
   const tbc_ledger_in* in = &rin->ledger;
-  P = Plan{};
-  P.partner.assign(in->n_ops, kRtNone);
-  P.status.assign(in->n_ops, TBC_LEDGER_T_INVOKE);
+  partner.assign(in->n_ops, kRtNone);
+  status.assign(in->n_ops, TBC_LEDGER_T_INVOKE);
   std::unordered_map<int32_t, uint32_t> open;         // process -> its open invocation
   for (uint32_t i = 0; i < in->n_ops; i++) {
     if (in->type[i] == TBC_LEDGER_T_INVOKE) { open[rin->process[i]] = i; continue; }
     const auto it = open.find(rin->process[i]);
     if (it == open.end()) continue;
     const uint32_t inv = it->second;
-    P.partner[inv] = i; P.partner[i] = inv;
-    if (in->kind[inv] == TBC_LEDGER_K_TRANSFER) P.status[inv] = in->type[i];
+    partner[inv] = i; partner[i] = inv;
+    if (in->kind[inv] == TBC_LEDGER_K_TRANSFER) status[inv] = in->type[i];
     open.erase(it);
   }
+}
+
+// (the input has passed `validate`.)  false: too much for one call (`err` says what)
+// chunks_cap: the most chunks a stream is cut into (the tests' emulator passes a few, so that a chunk is several wavefronts' worth)
+inline bool plan(const char* fn, const tbc_ledger_rt_in* rin, Plan& P, std::string& err, uint32_t chunks_cap = kRtChunksMax) {
+  const tbc_ledger_in* in = &rin->ledger;
+  P = Plan{};
+  pair(rin, P.partner, P.status);
   // the micro-ops the device gets, numbered in the caller's order: at[i] = where op i's begin there
   std::vector<uint64_t> at(in->n_ops, 0);
   for (uint32_t i = 0; i < in->n_ops; i++) {

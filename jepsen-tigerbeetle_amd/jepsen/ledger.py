@@ -75,6 +75,46 @@ monotonic-key-graph in the reference's unfinished elle/core.clj.  THE RULES, sta
     legal.  ValueError here; tbc_ledger_snapshots counts offending reads on the device and answers TBC_ERR_UNSUPPORTED.
   OPTIONS: "accounts".
 
+Journal audit (`journal_host` the specification, `journal_numpy` the vectorised statement the device is compared with, `JournalAudit`
+the checker, `check_journal_native` / `journal_result_map` the device route over tbc_ledger_journal; `test(journal=True)` composes the
+member "journal").  Not in the reference: an :ok :l-t lookup returns the ledger's JOURNAL -- every transfer's id, debit-acct, credit-acct
+and amount -- and lookup-transfers asks one thing of it, and only of the final lookups: does it hold every invoked id.  A bit flipped
+in an amount in every final lookup alike, a failed transfer journalled, an acknowledged transfer missing from a lookup, and balances
+that hold a transfer twice (a duplicated packet keeps :SI's total, stays a chain, and hides under the slack :info transfers leave in
+realtime's hi) pass every member above.  THE RULES, stated once here:
+
+  Positions, client ops, pairing by process, a TRANSFER (its inv, ret and status), a READ (numbering, checked micro-ops, inv, ret), a
+    COUNTER c = 2 k + x and init are those of the realtime and snapshot rules.
+  RECORDS.  The micro-ops of the transfers (client invocations of kind "t"), in column order, are numbered 0 .. M-1.  The RECORD of an id
+    is the first of them with that id; its OWNER is that micro-op's transfer.  A later micro-op with the same id is REINVOKED: counted
+    in the summary, not a record.  A record may be nil.
+  LOOKUPS.  A lookup is every :ok completion whose op_txn_f is "l-t", final or not, numbered in history order (tbc_ledger_check numbers
+    only the final ones).  ret(L) is its index, inv(L) its invocation's index, -1 if it has none: nothing is before such a lookup.  Its
+    micro-ops are its ENTRIES.
+  PER ENTRY, entry_bits: 1 UNKNOWN its id has no record; 2 ALTERED its id has a record and the entry or the record is nil, or
+    (debit-acct, credit-acct, amount) differ.  Both are judged entry by entry, so neither depends on order.
+  PER LOOKUP AND RECORD.  A record is PRESENT in L if some entry of L has its id; present[L] the number of records present; REPEATED the
+    entries with a record minus present[L].  A present record is FAILED if its owner's status is fail, EARLY if inv(owner) > ret(L).
+    An absent record is LOST if its owner's status is ok, ret(owner) < inv(L) and "ok-transfers-apply?" holds (default true, as in
+    realtime); VANISHED if some lookup L' with ret(L') < inv(L) has it present: the journal only grows.
+  BOOKS.  J_L[c] = init[c] + the RECORD's amount for every record present in L that is not nil, on counter 2 k for its credit-acct and on
+    2 k' + 1 for its debit-acct.  A side that names no account is skipped.  Altered and unknown entries are reported above and do not
+    move the vector.  `foreign_sides` counts, over the records, the sides that name no account, a nil record counting as two.
+  READS AGAINST BOOKS.  For a read R, a lookup L and a counter c that R checks: ret(R) < inv(L) and v_R[c] > J_L[c]: R is AHEAD of L (it
+    saw money a later journal does not explain); ret(L) < inv(R) and v_R[c] < J_L[c]: R is BEHIND L.  Per lookup the number of reads
+    ahead of it and behind it; per read rd_bits (1 ahead of some lookup, 2 behind some lookup) and rd_first[2], the least lookup number
+    of each, NO_OP if none.
+  KINDS: unknown, altered, repeated (entries), failed, early, lost, vanished (records), ahead, behind (reads): lk_counts[L][9].  Per
+    transfer micro-op xfer_present, xfer_early, xfer_lost, xfer_vanished: numbers of lookups, 0 for a reinvoked micro-op; xfer_flags
+    bit 1 reinvoked, bit 2 nil.
+  SUMMARY: n_lookups, n_entries, n_xfer_mops, n_records, n_reinvoked, foreign_sides, bad_amounts, read_count, n_checked (the read
+    micro-ops checked); per kind count, first, last, worst over the LOOKUPS with a non-zero count (worst: the greatest count; ties go
+    to the earliest, as everywhere here) and the total; valid = every total is 0.
+  CROSS-CHECK: for a :final? lookup, n_records - present[L] is lookup_missing of tbc_ledger_check.
+  RANGES: every amount of a non-nil record in [0, 2^31); M < 2^31; fewer than 2^31 entries a lookup; |init| < 2^61.  ValueError here;
+    tbc_ledger_journal counts offending amounts on the device and answers TBC_ERR_UNSUPPORTED.
+  OPTIONS: those of realtime.
+
 History ops are the dicts `edn.read_history` gives: "type" "f" "value" "process" "index" "time" "final?", keywords as strings; a
 :value is a vector of micro-ops [f id m] with f in "t" "r" "l-t".
 
@@ -727,22 +767,28 @@ def _sat_sub(a, b):
     return np.where(over, np.where(a < 0, _I64_MIN, _I64_MAX), d)
 
 
+def _partner_rows(cols):
+    """pairing (knossos.history.pair_index) over a LedgerColumns: per row the row of its completion / invocation, -1 if it has none.
+    Along one process an invocation is completed by the very next op when that is a completion."""
+    n = len(cols)
+    order = np.argsort(cols.process, kind="stable")
+    p, t = cols.process[order], cols.type[order]
+    match = (p[1:] == p[:-1]) & (t[:-1] == N.LEDGER_T_INVOKE) & (t[1:] != N.LEDGER_T_INVOKE) if n > 1 else np.zeros(0, bool)
+    partner = np.full(n, -1, np.int64)
+    partner[order[1:][match]] = order[:-1][match]
+    partner[order[:-1][match]] = order[1:][match]
+    return partner
+
+
 def realtime_numpy_columns(cols, accounts, init, apply_ok=True):
     """realtime_host's arrays from a LedgerColumns in O(n log n): a stable sort by (account, position), cumsum / maximum.accumulate along it,
     and searchsorted for every read micro-op.  The reference at sizes the quadratic statement cannot reach."""
     T_INV, T_OK, T_FAIL = N.LEDGER_T_INVOKE, N.LEDGER_T_OK, N.LEDGER_T_FAIL
     _rt_ranges([], 0, init)
     acct, init_c, init_d = _rt_init_arrays(accounts, init)
-    n = len(cols)
     index, typ, kind = cols.index.astype(np.int64), cols.type, cols.kind
     off = cols.mop_off.astype(np.int64)
-    # pairing (knossos.history.pair_index): along one process an invocation is completed by the very next op when that is a completion
-    order = np.argsort(cols.process, kind="stable")
-    p, t = cols.process[order], typ[order]
-    match = (p[1:] == p[:-1]) & (t[:-1] == T_INV) & (t[1:] != T_INV) if n > 1 else np.zeros(0, bool)
-    partner = np.full(n, -1, np.int64)
-    partner[order[1:][match]] = order[:-1][match]
-    partner[order[:-1][match]] = order[1:][match]
+    partner = _partner_rows(cols)
     tr = np.flatnonzero((typ == T_INV) & (kind == N.LEDGER_K_TRANSFER))
     status = np.where(partner[tr] >= 0, typ[partner[tr]], T_INV)                 # (T_INV: open)
     ret = np.where(partner[tr] >= 0, index[partner[tr]], -1)
@@ -1145,11 +1191,344 @@ class _SnapshotDevice(jc.Checker):
         return snapshots_result_map(history, cols, dev, accounts)
 
 
-def test(opts=None, linear=False, realtime=False, device_route=True, snapshots=False):
+# ---------------------------------------------------------------- the journal audit of the lookups
+
+JN_KINDS = ("unknown", "altered", "repeated", "failed", "early", "lost", "vanished", "ahead", "behind")       # by TBC_LEDGER_JN_*
+JN_RECORD_KINDS = ("failed", "early", "lost", "vanished")
+JN_ARRAYS = ("entry_bits", "lk_counts", "lk_present", "lk_vector", "rd_bits", "rd_first", "xfer_present", "xfer_early", "xfer_lost",
+             "xfer_vanished", "xfer_flags")
+
+
+def _jn_model(history):
+    """(transfer micro-ops, lookups) of a history.  A transfer micro-op: {"id", "fields": (debit-acct, credit-acct, amount) | None, "inv",
+    "ret", "status"} (its owner's); a lookup: {"inv", "ret", "entries": [(id, fields | None)]}."""
+    pairs = H.pair_index(history)
+    fields = lambda m: None if m[2] is None else (m[2]["debit-acct"], m[2]["credit-acct"], m[2]["amount"])
+    xfers, lookups = [], []
+    for i, op in enumerate(history):
+        if not H.client_op(op):
+            continue
+        f, j = op_txn_f(op), pairs.get(i)
+        if f == "t" and op["type"] == "invoke":
+            status = "open" if j is None else (history[j]["type"] if history[j]["type"] in ("ok", "fail") else "info")
+            xfers.extend({"id": m[1], "fields": fields(m), "inv": i, "ret": j, "status": status} for m in op["value"])
+        elif f == "l-t" and op["type"] == "ok":
+            lookups.append({"inv": -1 if j is None else j, "ret": i, "entries": [(m[1], fields(m)) for m in op["value"]]})
+    return xfers, lookups
+
+
+def _jn_ranges(amounts, n_xfer_mops, entries_per_lookup, init):
+    for amount in amounts:
+        if not 0 <= amount < 2 ** 31:
+            raise ValueError(f"journal: a journalled transfer's amount {amount!r} is not in [0, 2^31)")
+    if n_xfer_mops >= 2 ** 31:
+        raise ValueError("journal: 2^31 or more transfer micro-ops")
+    if any(n >= 2 ** 31 for n in entries_per_lookup):
+        raise ValueError("journal: a lookup of 2^31 or more entries")
+    for a, cd in init.items():
+        for x in cd:
+            if not isinstance(x, (int, np.integer)) or isinstance(x, (bool, np.bool_)) or not abs(x) < 2 ** 61:
+                raise ValueError(f"journal: initial value {x!r} of account {a!r} is not an int with |x| < 2^61")
+
+
+def _jn_summary(res, n_records, n_reinvoked, foreign_sides, n_checked):
+    """the summary of tbc_ledger_journal_summary (without ns_device and bytes_in) from the arrays"""
+    counts = res["lk_counts"]
+    s = {"n_lookups": len(counts), "n_xfer_mops": len(res["xfer_flags"]), "n_records": n_records, "n_reinvoked": n_reinvoked,
+         "foreign_sides": foreign_sides, "bad_amounts": 0, "read_count": len(res["rd_bits"]), "n_entries": len(res["entry_bits"]),
+         "n_checked": n_checked, "errors": {}, "totals": {}}
+    for k, kind in enumerate(JN_KINDS):
+        has = np.flatnonzero(counts[:, k])
+        e = {"count": len(has), "first": N.NO_OP, "last": N.NO_OP, "worst": N.NO_OP}
+        if len(has):
+            e.update({"first": int(has[0]), "last": int(has[-1]), "worst": int(has[np.argmax(counts[has, k])])})     # (argmax: the earliest of equals)
+        s["errors"][kind], s["totals"][kind] = e, int(counts[:, k].astype(np.int64).sum())
+    s["valid"] = int(not any(s["totals"].values()))
+    return s
+
+
+def journal_host(history, opts=None):
+    """The specification of the journal audit (module docstring), plain loops, one rule a line.  The arrays of tbc_ledger_journal_out by
+    name (JN_ARRAYS) and the "summary"."""
+    accounts, init, apply_ok = _rt_opts(None, opts)
+    pos = {a: k for k, a in enumerate(accounts)}
+    xfers, lookups = _jn_model(history)
+    _transfers, reads = _rt_model(history)
+    record = {}
+    for m, x in enumerate(xfers):
+        record.setdefault(x["id"], m)                                   # the first micro-op with the id
+    is_record = [record[x["id"]] == m for m, x in enumerate(xfers)]
+    _jn_ranges([x["fields"][2] for m, x in enumerate(xfers) if is_record[m] and x["fields"] is not None], len(xfers),
+               [len(L["entries"]) for L in lookups], init)
+    M, NL, R, C = len(xfers), len(lookups), len(reads), 2 * len(accounts)
+    entry_bits = []
+    counts, present_n, vector = np.zeros((NL, 9), np.uint32), np.zeros(NL, np.uint32), np.zeros((NL, C), np.int64)
+    x_present, x_early, x_lost, x_vanished = (np.zeros(M, np.uint32) for _ in range(4))
+    present = []
+    for l, L in enumerate(lookups):
+        here = set()
+        for ident, fields in L["entries"]:
+            if ident not in record:
+                entry_bits.append(1); counts[l, 0] += 1                 # UNKNOWN
+                continue
+            rec = xfers[record[ident]]
+            altered = fields is None or rec["fields"] is None or fields != rec["fields"]
+            entry_bits.append(2 if altered else 0); counts[l, 1] += altered         # ALTERED
+            counts[l, 2] += record[ident] in here                       # REPEATED
+            here.add(record[ident])
+        present.append(here)
+        present_n[l] = len(here)
+        J = {c: init[accounts[c // 2]][c % 2] for c in range(C)}
+        for m, x in enumerate(xfers):
+            if not is_record[m]:
+                continue
+            if m in here:
+                x_present[m] += 1
+                failed, early = x["status"] == "fail", x["inv"] > L["ret"]
+                counts[l, 3] += failed; counts[l, 4] += early; x_early[m] += early
+                if x["fields"] is not None:                             # BOOKS
+                    debit, credit, amount = x["fields"]
+                    if credit in pos:
+                        J[2 * pos[credit]] += amount
+                    if debit in pos:
+                        J[2 * pos[debit] + 1] += amount
+            else:
+                lost = apply_ok and x["status"] == "ok" and x["ret"] < L["inv"]
+                vanished = any(lookups[k]["ret"] < L["inv"] and m in present[k] for k in range(l))
+                counts[l, 5] += lost; counts[l, 6] += vanished; x_lost[m] += lost; x_vanished[m] += vanished
+        vector[l] = [J[c] for c in range(C)]
+    rd_bits, rd_first = np.zeros(R, np.uint8), np.full((R, 2), N.NO_OP, np.uint32)
+    n_checked = 0
+    for r, Rd in enumerate(reads):
+        checked = [(ident, cr, db) for ident, cr, db, nil in Rd["mops"] if not nil and ident in pos]
+        n_checked += len(checked)
+        for l, L in enumerate(lookups):
+            ahead = Rd["ret"] < L["inv"] and any(v > vector[l, 2 * pos[a] + x] for a, *cd in checked for x, v in enumerate(cd))
+            behind = L["ret"] < Rd["inv"] and any(v < vector[l, 2 * pos[a] + x] for a, *cd in checked for x, v in enumerate(cd))
+            for k, hit in enumerate((ahead, behind)):
+                if hit:
+                    counts[l, 7 + k] += 1
+                    rd_bits[r] |= 1 << k
+                    rd_first[r, k] = min(rd_first[r, k], l)
+    flags = np.array([(0 if is_record[m] else 1) | (2 if x["fields"] is None else 0) for m, x in enumerate(xfers)], np.uint8).reshape(-1)
+    foreign = sum(2 if x["fields"] is None else (x["fields"][0] not in pos) + (x["fields"][1] not in pos) for m, x in enumerate(xfers) if is_record[m])
+    res = {"entry_bits": np.array(entry_bits, np.uint8).reshape(-1), "lk_counts": counts, "lk_present": present_n, "lk_vector": vector,
+           "rd_bits": rd_bits, "rd_first": rd_first, "xfer_present": x_present, "xfer_early": x_early, "xfer_lost": x_lost,
+           "xfer_vanished": x_vanished, "xfer_flags": flags}
+    res["summary"] = _jn_summary(res, sum(is_record), M - sum(is_record), foreign, n_checked)
+    return res
+
+
+def journal_numpy_columns(cols, accounts, init, apply_ok=True):
+    """journal_host's arrays from a LedgerColumns, vectorised: the records by np.unique, a lookups x transfer-micro-ops presence matrix,
+    the reads as the dense rows of the snapshot statement.  What the device is held to."""
+    T_INV, T_OK, T_FAIL = N.LEDGER_T_INVOKE, N.LEDGER_T_OK, N.LEDGER_T_FAIL
+    acct, init_c, init_d = _rt_init_arrays(accounts, init)
+    A, C2 = len(acct), 2 * len(acct)
+    index, typ, kind = cols.index.astype(np.int64), cols.type, cols.kind
+    off = cols.mop_off.astype(np.int64)
+    partner = _partner_rows(cols)
+    p_index = np.where(partner >= 0, index[np.maximum(partner, 0)], -1)
+    # the transfer micro-ops and their owners
+    tr = np.flatnonzero((typ == T_INV) & (kind == N.LEDGER_K_TRANSFER))
+    xm, xrow = _expand(off[tr], off[tr + 1] - off[tr])
+    M = len(xm)
+    x_id, x_nil = cols.mop_id[xm], (cols.mop_flags[xm] & N.LEDGER_M_NIL) != 0
+    x_inv, x_ret = index[tr][xrow], p_index[tr][xrow]
+    x_status = np.where(partner[tr] >= 0, typ[np.maximum(partner[tr], 0)], T_INV)[xrow]
+    uniq, first_idx, inverse = np.unique(x_id, return_index=True, return_inverse=True)
+    is_record = first_idx[inverse.reshape(-1)] == np.arange(M) if M else np.zeros(0, bool)
+    # the lookups and their entries
+    lk = np.flatnonzero((typ == T_OK) & (kind == N.LEDGER_K_LOOKUP))
+    NL = len(lk)
+    l_ret, l_inv = index[lk], p_index[lk]
+    em, erow = _expand(off[lk], off[lk + 1] - off[lk])
+    _jn_ranges(cols.mop_c[xm][is_record & ~x_nil][(cols.mop_c[xm][is_record & ~x_nil] < 0) | (cols.mop_c[xm][is_record & ~x_nil] >= 2 ** 31)][:1].tolist(),
+               M, (off[lk + 1] - off[lk]).tolist(), init)
+    e_id = cols.mop_id[em]
+    at = np.minimum(np.searchsorted(uniq, e_id), max(len(uniq) - 1, 0))
+    known = uniq[at] == e_id if M else np.zeros(len(em), bool)
+    rec = first_idx[at] if M else np.zeros(len(em), np.int64)
+    e_nil = (cols.mop_flags[em] & N.LEDGER_M_NIL) != 0
+    xs = xm[rec] if M else em
+    differ = e_nil | x_nil[rec] | (cols.mop_a[em] != cols.mop_a[xs]) | (cols.mop_b[em] != cols.mop_b[xs]) | (cols.mop_c[em] != cols.mop_c[xs]) if M else known
+    entry_bits = np.where(known, np.where(differ, 2, 0), 1).astype(np.uint8)
+    counts = np.zeros((NL, 9), np.uint32)
+    counts[:, 0] = np.bincount(erow[~known], minlength=NL)
+    counts[:, 1] = np.bincount(erow[known & differ], minlength=NL)
+    P = np.zeros((NL, M), bool)
+    P[erow[known], rec[known]] = True
+    present_n = P.sum(axis=1).astype(np.uint32)
+    counts[:, 2] = np.bincount(erow[known], minlength=NL) - present_n
+    absent = ~P & is_record
+    seen = P.any(axis=0)
+    seen_ret = np.where(seen, l_ret[np.argmax(P, axis=0)] if NL else 0, np.iinfo(np.int64).max)       # (lookups are numbered by ret: the first that shows it has the least)
+    failed, early = P & (x_status == T_FAIL), P & (x_inv[None, :] > l_ret[:, None])
+    lost = absent & (x_status == T_OK) & (x_ret[None, :] < l_inv[:, None]) & bool(apply_ok)
+    vanished = absent & (seen_ret[None, :] < l_inv[:, None])
+    for k, what in ((3, failed), (4, early), (5, lost), (6, vanished)):
+        counts[:, k] = what.sum(axis=1)
+    # the books
+    perm = np.argsort(acct, kind="stable")
+
+    def counter(ids, x):
+        k = np.minimum(np.searchsorted(acct[perm], ids), max(A - 1, 0))
+        return np.where(acct[perm][k] == ids, 2 * perm[k] + x, -1) if A else np.full(len(ids), -1, np.int64)
+
+    cc, dc = counter(cols.mop_b[xm], 0), counter(cols.mop_a[xm], 1)
+    moves = is_record & ~x_nil
+    vector = np.zeros((NL, C2), np.int64)
+    vector[:, 0::2], vector[:, 1::2] = init_c, init_d
+    amount = cols.mop_c[xm]
+    for l in range(NL):
+        for side in (cc, dc):
+            m = np.flatnonzero(P[l] & moves & (side >= 0))
+            np.add.at(vector[l], side[m], amount[m])
+    foreign = int(2 * np.count_nonzero(is_record & x_nil) + np.count_nonzero(moves & (cc < 0)) + np.count_nonzero(moves & (dc < 0)))
+    # the reads against the books
+    V, K = _snap_dense(cols, accounts)
+    rd = np.flatnonzero((typ == T_OK) & (kind == N.LEDGER_K_READ))
+    r_ret, r_inv = index[rd], p_index[rd]
+    R = len(rd)
+    rd_bits, rd_first = np.zeros(R, np.uint8), np.full((R, 2), N.NO_OP, np.uint32)
+    for l in range(NL - 1, -1, -1):                                     # (descending: the least lookup number is written last)
+        ahead = (r_ret < l_inv[l]) & (K & (V > vector[l])).any(axis=1)
+        behind = (l_ret[l] < r_inv) & (K & (V < vector[l])).any(axis=1)
+        for k, hit in enumerate((ahead, behind)):
+            counts[l, 7 + k] = np.count_nonzero(hit)
+            rd_bits[hit] |= np.uint8(1 << k)
+            rd_first[hit, k] = l
+    x_flags = (np.where(is_record, 0, 1) | np.where(x_nil, 2, 0)).astype(np.uint8)
+    res = {"entry_bits": entry_bits, "lk_counts": counts, "lk_present": present_n, "lk_vector": vector, "rd_bits": rd_bits, "rd_first": rd_first,
+           "xfer_present": P.sum(axis=0).astype(np.uint32) * is_record.astype(np.uint32), "xfer_early": early.sum(axis=0).astype(np.uint32),
+           "xfer_lost": lost.sum(axis=0).astype(np.uint32), "xfer_vanished": vanished.sum(axis=0).astype(np.uint32), "xfer_flags": x_flags}
+    res["summary"] = _jn_summary(res, int(np.count_nonzero(is_record)), int(M - np.count_nonzero(is_record)), foreign, int(K.sum()) // 2)
+    return res
+
+
+def journal_numpy(history, opts=None):
+    """journal_host(history, opts), vectorised (journal_numpy_columns over the history's LedgerColumns)."""
+    accounts, init, apply_ok = _rt_opts(None, opts)
+    return journal_numpy_columns(LedgerColumns(history), accounts, init, apply_ok)
+
+
+def _jn_lookup_ops(cols):
+    """which op (position in the history) is which lookup of the journal audit"""
+    return cols.index[(cols.type == N.LEDGER_T_OK) & (cols.kind == N.LEDGER_K_LOOKUP)]
+
+
+def _jn_map(history, res):
+    """the journal result map from the arrays and the summary (the host statement's or the device's): per kind count, total, and first,
+    last, worst as the lookup ops; for the record kinds up to 10 offending ids"""
+    s = res["summary"]
+    out = {"valid?": bool(s["valid"]), "lookup-count": s["n_lookups"], "entry-count": s["n_entries"], "record-count": s["n_records"],
+           "reinvoked-count": s["n_reinvoked"], "errors": {}}
+    if s["valid"]:                                      # (nothing to name: no pass over the history)
+        return out
+    hist = _indexed(history) if any("index" not in op for op in history) else history
+    xfers, lookups = _jn_model(history)
+    failed = np.array([x["status"] == "fail" for x in xfers], bool).reshape(-1)
+    offending = {"failed": (res["xfer_present"] > 0) & failed, "early": res["xfer_early"] > 0, "lost": res["xfer_lost"] > 0,
+                 "vanished": res["xfer_vanished"] > 0}
+    for kind in JN_KINDS:
+        e = s["errors"][kind]
+        if not e["count"]:
+            continue
+        m = {"count": e["count"], "total": s["totals"][kind]}
+        m.update({k: hist[lookups[e[k]]["ret"]] for k in ("first", "last", "worst")})
+        if kind in JN_RECORD_KINDS:
+            m["ids"] = [xfers[int(i)]["id"] for i in np.flatnonzero(offending[kind])[:10]]
+        out["errors"][kind] = m
+    return out
+
+
+class JournalAudit(jc.Checker):
+    """journal: every :ok lookup audited entry by entry against the transfers as invoked, against real time and against the balances the
+    reads returned (module docstring, "Journal audit").  opts: those of RealtimeBounds."""
+
+    def __init__(self, opts=None):
+        self.opts = dict(opts or {})
+
+    def check(self, test, history, opts=None):
+        accounts, init, _apply_ok = _rt_opts(test, self.opts)
+        o = dict(self.opts, accounts=accounts, initial={a: dict(zip(RT_FIELDS, cd)) for a, cd in init.items()})
+        return _jn_map(history, journal_host(history, o))
+
+
+def jn_summary_dict(s):
+    d = {f: int(getattr(s, f)) for f, _ in N.LedgerJournalSummary._fields_ if f not in ("errors", "totals")}
+    d["errors"] = {JN_KINDS[k]: {f: int(getattr(s.errors[k], f)) for f in ("count", "first", "last", "worst")} for k in range(9)}
+    d["totals"] = {JN_KINDS[k]: int(s.totals[k]) for k in range(9)}
+    return d
+
+
+def journal_shapes(cols):
+    """(entries, lookups, reads, transfer micro-ops) of a LedgerColumns: what sizes tbc_ledger_journal's output arrays"""
+    n = (cols.mop_off[1:].astype(np.int64) - cols.mop_off[:-1].astype(np.int64))
+    lk = (cols.type == N.LEDGER_T_OK) & (cols.kind == N.LEDGER_K_LOOKUP)
+    tr = (cols.type == N.LEDGER_T_INVOKE) & (cols.kind == N.LEDGER_K_TRANSFER)
+    return int(n[lk].sum()), int(np.count_nonzero(lk)), len(cols.read_ops), int(n[tr].sum())
+
+
+def journal_out(cols, n_accounts):
+    """A tbc_ledger_journal_out over fresh arrays sized for the columns: (out, {name: array}, {name: true shape})"""
+    E, NL, R, M = journal_shapes(cols)
+    shape = {"entry_bits": (E,), "lk_counts": (NL, 9), "lk_present": (NL,), "lk_vector": (NL, 2 * n_accounts), "rd_bits": (R,), "rd_first": (R, 2),
+             "xfer_present": (M,), "xfer_early": (M,), "xfer_lost": (M,), "xfer_vanished": (M,), "xfer_flags": (M,)}
+    dtype = {"entry_bits": np.uint8, "rd_bits": np.uint8, "xfer_flags": np.uint8, "lk_vector": np.int64}
+    arr = {f: np.zeros(max(1, int(np.prod(shape[f]))), dtype.get(f, np.uint32)) for f in JN_ARRAYS}
+    ct = {np.dtype(np.uint8): C.c_uint8, np.dtype(np.int64): C.c_int64, np.dtype(np.uint32): C.c_uint32}
+    out = N.LedgerJournalOut()
+    for f, x in arr.items():
+        setattr(out, f, _ptr(x, ct[x.dtype]))
+    return out, arr, shape
+
+
+def check_journal_native(cols, accounts, init, apply_ok=True, device=0, call=None):
+    """tbc_ledger_journal over the columns -> journal_host's arrays and the summary (with ns_device and bytes_in).  call(in, out): another
+    implementation of the entry point (the tests' emulator build of the same kernels).  An amount out of range is the device's to find
+    (TBC_ERR_UNSUPPORTED): ValueError here too."""
+    s, keep = ledger_rt_in(cols, accounts, init, apply_ok, device)
+    out, arr, shape = journal_out(cols, len(list(accounts)))
+    if call is None:
+        st = N.lib().tbc_ledger_journal(C.byref(s), C.byref(out))
+        if st == N.ERR_UNSUPPORTED:
+            raise ValueError("journal: " + N.lib().tbc_last_error().decode())
+        N.check_status(st)
+    else:
+        call(s, out)
+    del keep
+    res = {f: arr[f][:int(np.prod(shape[f]))].reshape(shape[f]) for f in JN_ARRAYS}
+    res["summary"] = jn_summary_dict(out.summary)
+    return res
+
+
+def journal_result_map(history, cols, dev):
+    """JournalAudit's result map from tbc_ledger_journal's arrays and summary: the lookups it names come from the history (a valid
+    history: none, and no pass over it)."""
+    assert dev["summary"]["n_lookups"] == len(_jn_lookup_ops(cols))
+    return _jn_map(history, dev)
+
+
+class _JournalDevice(jc.Checker):
+    """the journal member on the device route: columns -> tbc_ledger_journal -> JournalAudit's map.  No host route behind it."""
+
+    def __init__(self, opts):
+        self.opts = dict(opts or {})
+
+    def check(self, test, history, opts=None):
+        accounts, init, apply_ok = _rt_opts(test, self.opts)
+        cols = LedgerColumns(history)
+        dev = check_journal_native(cols, accounts, init, apply_ok, device=(opts or {}).get("device", 0))
+        return journal_result_map(history, cols, dev)
+
+
+def test(opts=None, linear=False, realtime=False, device_route=True, snapshots=False, journal=False):
     """The ledger test map (tests/ledger.clj:341-369) without generators: accounts, max-transfer, total-amount and the composed checker
     -- SI, lookup-transfers, final-reads, unexpected-ops, with linear=True the member clj/patches/ledger.patch adds, and with
     realtime=True the member "realtime" (RealtimeBounds; opts "initial", "ok-transfers-apply?") and with snapshots=True the member
-    "snapshots" (SnapshotOrder), each on the device or as the host statement according to device_route.
+    "snapshots" (SnapshotOrder) and with journal=True the member "journal" (JournalAudit; realtime's opts), each on the device or as the
+    host statement according to device_route.
     device_route=True (the default: the whole call measured 1.7-1.8 s against the host statement's 6.6-6.7 s on a ledger of 64 workers and 50k
     transfers, profiles/NOTES_ledger.md) answers the first three from one check_columns call; False runs the host statement."""
     opts = dict(opts if opts is not None else {"negative-balances?": False})
@@ -1166,6 +1545,8 @@ def test(opts=None, linear=False, realtime=False, device_route=True, snapshots=F
         members["realtime"] = _RealtimeDevice(opts) if device_route else RealtimeBounds(opts)
     if snapshots:
         members["snapshots"] = _SnapshotDevice(opts) if device_route else SnapshotOrder(opts)
+    if journal:
+        members["journal"] = _JournalDevice(opts) if device_route else JournalAudit(opts)
     if linear:
         members["linear"] = _Linear(opts["accounts"], bool(opts.get("negative-balances?", False)))
     return dict(opts, checker=jc.compose(members))
