@@ -44,7 +44,8 @@ extern "C" {
  * Still 2, additive (round 6): tbc_batch_map_input / _submit_input / _reload / _input_info (fresh histories into a batch's arenas),
  * tbc_comm_* (the sharded sweep's exchange behind the C-ABI); tbc_setfull_create_rows takes its exception lists in any order again.
  * Still 2, additive: tbc_ledger_snapshots and its structs.
- * Still 2, additive: tbc_ledger_journal and its structs. */
+ * Still 2, additive: tbc_ledger_journal and its structs.
+ * Still 2, additive: tbc_ledger_cycles and its structs. */
 #define TBC_ABI_VERSION 2u
 
 /* ------------------------------------------------------------------ status */
@@ -1051,6 +1052,48 @@ typedef struct tbc_ledger_journal_out {   /* arrays caller-allocated, each optio
   tbc_ledger_journal_summary summary;
 } tbc_ledger_journal_out;
 tbc_status tbc_ledger_journal(const tbc_ledger_rt_in* in, tbc_ledger_journal_out* out);
+
+/* ------------------------------------------------------------------- ledger: cycles through partial reads
+ * tbc_ledger_snapshots plus the regressed bit of tbc_ledger_realtime are the whole cycle search over monotonic-key and realtime edges
+ * only while every read is complete.  This entry point decides the graph itself, partial reads included: the strongly connected
+ * components of the :ok reads under MONOTONIC edges (R -> R' when both check a counter and R is below R' on it) and REALTIME edges
+ * (ret(R) < inv(R')).  THE RULES ARE STATED ONCE, in the docstring of jepsen/ledger.py ("Cycle search"): reads, counters, complete /
+ * partial, inv and ret, the edges, clean and core reads, the summary, the ranges; the reduction the device computes is
+ * cycles_dense_numpy there.
+ * Input: a tbc_ledger_rt_in; pairing uses `process`; init_credits, init_debits and ok_transfers_apply are validated and not read.
+ * Rows: reads are numbered as for tbc_ledger_check.
+ *   scc[r]         the least read number of r's strongly connected component when it has two or more reads, TBC_NO_OP otherwise
+ *   cyc_flags[r]   TBC_LEDGER_CYC_PARTIAL | TBC_LEDGER_CYC_ON_CYCLE | TBC_LEDGER_CYC_CORE
+ * The host plans what is O(ops) (csrc/ledger_cycles_plan.h: the snapshot plan, and inv / ret by pairing).  The device repeats the
+ * layout, sort and scan of tbc_ledger_snapshots, separates the CLEAN reads -- complete, comparable with every complete read, not
+ * contradicted by real time: a chain of classes that is acyclic by itself -- from the CORE (every other read), describes each core read by
+ * the classes it reaches and is reached from, builds the core's m x m bit matrix of direct and clean-mediated edges, closes it by
+ * boolean squaring (summary.closure_rounds), and joins the clean reads to the components that enclose them
+ * (csrc/ledger_cycles_kernels.h).  A history without core reads allocates no matrix and launches no closure or membership kernel.
+ * Validation and errors are those of tbc_ledger_realtime's input and of tbc_ledger_snapshots: TBC_ERR_INVALID_ARG before any device
+ * call; a read whose sum of |v| reaches 2^63 is counted on the device: TBC_ERR_UNSUPPORTED, no results, summary.bad_values.  A core of
+ * more than TBC_LEDGER_CYCLES_MAX_CORE reads (two matrices of m^2 / 8 bytes: 64 MB at the cap): TBC_ERR_UNSUPPORTED with
+ * summary.n_core (and read_count, n_partial) filled and no arrays.  One-shot and re-entrant as tbc_ledger_check is. */
+#define TBC_LEDGER_CYCLES_MAX_CORE 16384u
+#define TBC_LEDGER_CYC_PARTIAL  1u
+#define TBC_LEDGER_CYC_ON_CYCLE 2u
+#define TBC_LEDGER_CYC_CORE     4u
+
+typedef struct tbc_ledger_cycles_summary {
+  uint32_t read_count, n_partial, n_core, valid;          /* valid: no read is on a cycle */
+  uint32_t n_on_cycle, n_components, first, largest;      /* first: the least read on a cycle; largest: the label of the largest component (ties the earliest); TBC_NO_OP */
+  uint32_t largest_size, closure_rounds, bad_values, reserved0;   /* closure_rounds: squarings of the core's matrix, the one that changed nothing included */
+  uint64_t n_checked;                                     /* read micro-ops checked */
+  uint64_t ns_device;                                     /* the kernels, between HIP events */
+  uint64_t bytes_in;                                      /* copied to the device */
+} tbc_ledger_cycles_summary;
+
+typedef struct tbc_ledger_cycles_out {    /* arrays caller-allocated, each optional (NULL = not wanted) */
+  uint32_t* scc;                          /* [n_ok_reads] */
+  uint8_t* cyc_flags;                     /* [n_ok_reads] */
+  tbc_ledger_cycles_summary summary;
+} tbc_ledger_cycles_out;
+tbc_status tbc_ledger_cycles(const tbc_ledger_rt_in* in, tbc_ledger_cycles_out* out);
 
 /* ------------------------------------------------------------------- perf: the series behind the reference's perf plots
  * checker/perf.clj composes latency-graph, rate-graph and open-ops-graph into every test.  What it PLOTS is out of scope (gnuplot,

@@ -270,6 +270,23 @@ class LedgerSnapOut(C.Structure):
                 ("snap_flags", C.POINTER(C.c_uint8)), ("summary", LedgerSnapSummary)]
 
 
+# tbc_ledger_cycles: the cycle search over monotonic-key and realtime edges of a ledger's reads, partial reads included
+# (include/tbcheck.h); its input is a LedgerRtIn
+LEDGER_CYC_PARTIAL, LEDGER_CYC_ON_CYCLE, LEDGER_CYC_CORE = 1, 2, 4
+LEDGER_CYCLES_MAX_CORE = 16384
+
+
+class LedgerCyclesSummary(C.Structure):
+    _fields_ = [("read_count", C.c_uint32), ("n_partial", C.c_uint32), ("n_core", C.c_uint32), ("valid", C.c_uint32),
+                ("n_on_cycle", C.c_uint32), ("n_components", C.c_uint32), ("first", C.c_uint32), ("largest", C.c_uint32),
+                ("largest_size", C.c_uint32), ("closure_rounds", C.c_uint32), ("bad_values", C.c_uint32), ("reserved0", C.c_uint32),
+                ("n_checked", C.c_uint64), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64)]
+
+
+class LedgerCyclesOut(C.Structure):
+    _fields_ = [("scc", C.POINTER(C.c_uint32)), ("cyc_flags", C.POINTER(C.c_uint8)), ("summary", LedgerCyclesSummary)]
+
+
 # tbc_ledger_journal: the lookups of a ledger audited against the transfers, real time and the reads (include/tbcheck.h); its input is
 # a LedgerRtIn
 (LEDGER_JN_UNKNOWN, LEDGER_JN_ALTERED, LEDGER_JN_REPEATED, LEDGER_JN_FAILED, LEDGER_JN_EARLY, LEDGER_JN_LOST, LEDGER_JN_VANISHED,
@@ -397,6 +414,7 @@ SYMBOLS = {
     "tbc_ledger_realtime": (C.c_int, [C.POINTER(LedgerRtIn), C.POINTER(LedgerRtOut)]),
     "tbc_ledger_snapshots": (C.c_int, [C.POINTER(LedgerIn), C.POINTER(LedgerSnapOut)]),
     "tbc_ledger_journal": (C.c_int, [C.POINTER(LedgerRtIn), C.POINTER(LedgerJournalOut)]),
+    "tbc_ledger_cycles": (C.c_int, [C.POINTER(LedgerRtIn), C.POINTER(LedgerCyclesOut)]),
     "tbc_perf_plan_sizes": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfSizes)]),
     "tbc_perf_series": (C.c_int, [C.POINTER(PerfIn), C.POINTER(PerfOut)]),
     "tbc_batch_destroy": (None, [C.c_void_p]),

@@ -1,5 +1,5 @@
 // oneshot_call.h -- the host call frame of the one-shot entry points that take op columns (tbc_ledger_check, tbc_ledger_realtime,
-// tbc_ledger_snapshots, tbc_perf_series): the HIP error macro, the extern "C" wrapper, and OneShotCall -- what one call makes on the
+// tbc_ledger_snapshots, tbc_ledger_cycles, tbc_perf_series): the HIP error macro, the extern "C" wrapper, and OneShotCall -- what one call makes on the
 // device (ONE arena laid out by the plan, a stream and two events of its own) and the steps every such call takes, released on every
 // path out.  One-shot and re-entrant: nothing outlives the call.
 #pragma once

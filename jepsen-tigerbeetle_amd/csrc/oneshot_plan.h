@@ -4,7 +4,7 @@
 // sorted order, the chunk size of a scan over whole wavefronts, and the one rule of a strided kernel's grid.
 //
 // THE LAUNCHER CONVENTION.  Each checker states its kernels' order, conditions, grids and block sizes ONCE, as a template at the end of
-// its kernels header (lg::sequence, lgrt::sequence, lgsn::filter_sequence / rest_sequence, pf::sequence), written against a launcher
+// its kernels header (lg::sequence, lgrt::sequence, lgsn::filter_sequence / rest_sequence, lgcy::prepare_sequence .. finish_sequence, pf::sequence), written against a launcher
 // that names no HIP type:
 //   go.launch(kernel, grid, threads, args...)   one launch of `grid` workgroups of `threads` threads
 //   go.grid(blocks, cap)                        the workgroups of a kernel that STRIDES: the blocks wanted, `cap` at most

@@ -75,6 +75,29 @@ monotonic-key-graph in the reference's unfinished elle/core.clj.  THE RULES, sta
     legal.  ValueError here; tbc_ledger_snapshots counts offending reads on the device and answers TBC_ERR_UNSUPPORTED.
   OPTIONS: "accounts".
 
+Cycle search (`cycles_host` the specification -- the explicit graph and Tarjan --, `cycles_numpy` the reduction the device computes,
+`CycleSearch` the checker, `check_cycles_native` / `cycles_result_map` the device route over tbc_ledger_cycles; `test(cycles=True)`
+composes the member "cycles").  The snapshot rule is the whole cycle search only while every read is complete; a read that comes back
+short is what a fault produces, and a cycle through partial reads needs no skewed pair and no regressed read.  This member decides
+the graph the reference's unfinished elle/core.clj and doc/LASS.md ask for, partial reads included.  THE RULES, stated once here:
+
+  READS, their numbering, their checked micro-ops, the COUNTERS c = 2 k + x and COMPLETE / PARTIAL are those of the snapshot rules;
+    inv(R) and ret(R) those of the realtime rules, inv = -1 when a read has no invocation.
+  EDGES over the reads.  MONOTONIC R -> R' on c: both check c and v_R[c] < v_R'[c].  REALTIME R -> R': ret(R) < inv(R'); a read with
+    inv = -1 has no incoming realtime edge.  (The reachability of monotonic-key-graph united with Elle's realtime graph.)
+  PER READ: scc[r] the least read number of r's strongly connected component when that component has two or more reads, NO_OP
+    otherwise; cyc_flags[r] bit 1 partial, bit 2 on a cycle, bit 4 core.
+  CORE.  U: the complete reads skewed with no complete read (each is comparable with every complete read).  C' in U is RT-FLAGGED if
+    some C in U has ret(C) < inv(C') and sum(C) > sum(C') (sum: over all counters).  CLEAN = U minus the rt-flagged; CORE = every other
+    read: partial, skewed with a complete read, or rt-flagged.  The clean reads alone are acyclic: every cycle passes through the core.
+  SUMMARY: read_count, n_partial, n_core; n_on_cycle, n_components; first = the least read on a cycle; largest = the label of the
+    largest component and largest_size its size (ties go to the earliest, as everywhere here); valid = (n_on_cycle == 0);
+    closure_rounds = the boolean squarings of the core's m x m matrix A <- A | A.A, the one that changes nothing included (0 when the
+    core is empty); n_checked = the read micro-ops checked; bad_values as in the snapshot rules.
+  RANGES: those of the snapshot rules.  The device takes a core of at most 16,384 reads (TBC_LEDGER_CYCLES_MAX_CORE); above it
+    tbc_ledger_cycles answers TBC_ERR_UNSUPPORTED with n_core filled, and the member answers "valid?" "unknown".
+  OPTIONS: "accounts".
+
 Journal audit (`journal_host` the specification, `journal_numpy` the vectorised statement the device is compared with, `JournalAudit`
 the checker, `check_journal_native` / `journal_result_map` the device route over tbc_ledger_journal; `test(journal=True)` composes the
 member "journal").  Not in the reference: an :ok :l-t lookup returns the ledger's JOURNAL -- every transfer's id, debit-acct, credit-acct
@@ -1191,6 +1214,332 @@ class _SnapshotDevice(jc.Checker):
         return snapshots_result_map(history, cols, dev, accounts)
 
 
+# ---------------------------------------------------------------- cycles over monotonic and realtime edges, partial reads included
+
+CYC_PARTIAL, CYC_ON_CYCLE, CYC_CORE = 1, 2, 4
+CYCLES_MAX_CORE = N.LEDGER_CYCLES_MAX_CORE    # TBC_LEDGER_CYCLES_MAX_CORE
+CYC_ARRAYS = ("scc", "flags")
+
+
+def _cyc_model(history, accounts):
+    """per :ok read its vector {counter: value}, its history index, inv and ret (the snapshot and the realtime rules' own statements)"""
+    vectors, index = _snap_vectors(history, accounts)
+    reads = _rt_model(history)[1]
+    assert [R["ret"] for R in reads] == index
+    return vectors, index, [R["inv"] for R in reads], [R["ret"] for R in reads]
+
+
+def _cyc_edge(vectors, inv, ret, a, b):
+    """the edge a -> b of the rules: None, or ("realtime",) / ("monotonic", counter) -- realtime named first, then the least counter"""
+    if ret[a] < inv[b]:
+        return ("realtime",)
+    below = sorted(c for c in vectors[a] if c in vectors[b] and vectors[a][c] < vectors[b][c])
+    return ("monotonic", below[0]) if below else None
+
+
+def _tarjan(n, succ):
+    """the strongly connected components of 0 .. n-1 (succ[v]: v's successors), iteratively: comp[v] = the least vertex of v's component"""
+    index, low, on, stack, comp = [None] * n, [0] * n, [False] * n, [], list(range(n))
+    count = 0
+    for root in range(n):
+        if index[root] is not None:
+            continue
+        work = [(root, 0)]
+        while work:
+            v, k = work.pop()
+            if k == 0:
+                index[v] = low[v] = count
+                count += 1
+                stack.append(v)
+                on[v] = True
+            for k2 in range(k, len(succ[v])):
+                w = succ[v][k2]
+                if index[w] is None:
+                    work.append((v, k2 + 1))
+                    work.append((w, 0))
+                    break
+                if on[w]:
+                    low[v] = min(low[v], index[w])
+            else:
+                if low[v] == index[v]:
+                    members = []
+                    while True:
+                        w = stack.pop()
+                        on[w] = False
+                        members.append(w)
+                        if w == v:
+                            break
+                    for w in members:
+                        comp[w] = min(members)
+                if work:
+                    u = work[-1][0]
+                    low[u] = min(low[u], low[v])
+    return comp
+
+
+def _cyc_summary(scc, flags, n_checked, closure_rounds):
+    """the summary of tbc_ledger_cycles_summary (without ns_device and bytes_in) from the per-read arrays"""
+    on = np.flatnonzero(flags & CYC_ON_CYCLE)
+    labels, sizes = np.unique(scc[on], return_counts=True)
+    s = {"read_count": len(scc), "n_partial": int(np.count_nonzero(flags & CYC_PARTIAL)), "n_core": int(np.count_nonzero(flags & CYC_CORE)),
+         "n_on_cycle": len(on), "n_components": len(labels), "first": N.NO_OP, "largest": N.NO_OP, "largest_size": 0, "valid": int(not len(on)),
+         "closure_rounds": closure_rounds, "bad_values": 0, "n_checked": n_checked}
+    if len(on):
+        s.update({"first": int(on[0]), "largest": int(labels[np.argmax(sizes)]), "largest_size": int(sizes.max())})     # (argmax: the earliest of equals)
+    return s
+
+
+def cycles_vectors_host(vectors, inv, ret, n_accounts):
+    """The specification of the cycle search (module docstring) over vectors {counter: value} with inv and ret: the explicit graph, edge by
+    edge, and Tarjan; O(R^2 C).  Per read "scc" and "flags", and the "summary" tbc_ledger_cycles gives but for closure_rounds, which only
+    the reduction has (None here)."""
+    R = len(vectors)
+    succ = [[b for b in range(R) if b != a and _cyc_edge(vectors, inv, ret, a, b)] for a in range(R)]
+    comp = _tarjan(R, succ)
+    size = np.bincount(np.array(comp, np.int64), minlength=R) if R else np.zeros(0, np.int64)
+    below = lambda a, b: any(c in b and a[c] < b[c] for c in a)
+    complete = [len(v) == 2 * n_accounts for v in vectors]
+    total = [sum(v.values()) for v in vectors]
+    U = [complete[i] and not any(complete[j] and below(vectors[i], vectors[j]) and below(vectors[j], vectors[i]) for j in range(R)) for i in range(R)]
+    rt_flagged = [U[i] and any(U[j] and ret[j] < inv[i] and total[j] > total[i] for j in range(R)) for i in range(R)]
+    scc, flags = np.full(R, N.NO_OP, np.uint32), np.zeros(R, np.uint8)
+    for r in range(R):
+        on = size[comp[r]] >= 2
+        if on:
+            scc[r] = comp[r]
+        flags[r] = (0 if complete[r] else CYC_PARTIAL) | (CYC_ON_CYCLE if on else 0) | (0 if U[r] and not rt_flagged[r] else CYC_CORE)
+    return {"scc": scc, "flags": flags, "summary": _cyc_summary(scc, flags, sum(len(v) // 2 for v in vectors), None)}
+
+
+def cycles_host(history, opts=None):
+    """cycles_vectors_host over the history's :ok reads (LedgerColumns' read_ops numbering).  opts: "accounts"."""
+    accounts = _snap_accounts(None, opts)
+    vectors, _index, inv, ret = _cyc_model(history, accounts)
+    return cycles_vectors_host(vectors, inv, ret, len(accounts))
+
+
+def _bool_square(A):
+    """A | A.A over booleans"""
+    f = A.astype(np.float32)
+    return A | ((f @ f) > 0)
+
+
+def cycles_dense_numpy(V, K, inv, ret):
+    """The REDUCTION the device computes, over dense rows (V, K as snapshots_dense_numpy takes them) with inv and ret [R] (ret ascending:
+    reads are numbered in history order).  The clean reads -- complete, comparable with every complete read, not rt-flagged -- form a
+    chain of CLASSES (the ranks of their distinct sums) along which every edge runs upwards, so they are never laid out as a graph: a core
+    read P keeps s_out (the least class it has an edge to), s_in (the greatest class with an edge to it) and whether a monotonic edge
+    realises each; the m x m matrix over the core has the direct edges and the edges mediated by clean reads; boolean squaring closes
+    it; a clean read joins the core component whose (lo, hi) descriptors enclose it.  Held to cycles_host array by array."""
+    R, C = V.shape
+    inv, ret = np.asarray(inv, np.int64), np.asarray(ret, np.int64)
+    near = np.flatnonzero((np.abs(V.astype(np.float64)) * K).sum(axis=1) >= 2.0 ** 62)       # (the few rows worth exact arithmetic)
+    if any(sum(abs(int(x)) for x in V[r][K[r]]) >= 2 ** 63 for r in near):
+        raise ValueError("cycles: a read's |credits| + |debits| reach 2^63")
+    complete = K.all(axis=1)
+    total = V.sum(axis=1) if C else np.zeros(R, np.int64)
+    flagged = np.zeros(R, bool)
+    full = np.flatnonzero(complete)
+    if len(full) and C:
+        order = full[np.lexsort((full, total[full]))]
+        S = V[order]
+        before = np.vstack([np.full((1, C), _I64_MIN, np.int64), np.maximum.accumulate(S, axis=0)[:-1]])
+        after = np.vstack([np.minimum.accumulate(S[::-1], axis=0)[::-1][1:], np.full((1, C), _I64_MAX, np.int64)])
+        flagged[order] = (before > S).any(axis=1) | (after < S).any(axis=1)
+    U = complete & ~flagged
+    # rt-flagged: the greatest sum over the reads of U that returned before this one was invoked is above its own
+    n_before = np.searchsorted(ret, inv, side="left")                      # reads with ret < inv(r)
+    pmax = np.maximum.accumulate(np.where(U, total, _I64_MIN)) if R else np.zeros(0, np.int64)
+    best = np.where(n_before > 0, pmax[np.maximum(n_before, 1) - 1], _I64_MIN) if R else pmax
+    clean = U & ~(best > total)
+    core = np.flatnonzero(~clean)
+    cl = np.flatnonzero(clean)
+    m = len(core)
+    scc, on = np.full(R, N.NO_OP, np.int64), np.zeros(R, bool)
+    rounds = 0
+    if m:
+        # the classes, and one vector per class
+        sums, first_of, cls_of = np.unique(total[cl], return_index=True, return_inverse=True) if len(cl) else (np.zeros(0, np.int64),) * 3
+        n_cls = len(sums)
+        Vc = V[cl[first_of]] if n_cls else np.zeros((0, C), np.int64)
+        cls = np.full(R, -1, np.int64)
+        cls[cl] = cls_of
+        INF = n_cls                                                               # +inf of s_out; -1 is the -inf of s_in
+        Vp, Kp = V[core], K[core]
+        mono_out, mono_in = np.full(m, INF, np.int64), np.full(m, -1, np.int64)
+        for c in range(C):
+            up = np.searchsorted(Vc[:, c], Vp[:, c], side="right")                # the least class above P on c
+            dn = np.searchsorted(Vc[:, c], Vp[:, c], side="left") - 1            # the greatest class below P on c
+            mono_out = np.where(Kp[:, c], np.minimum(mono_out, up), mono_out)
+            mono_in = np.where(Kp[:, c], np.maximum(mono_in, dn), mono_in)
+        by_inv = cl[np.argsort(inv[cl], kind="stable")]
+        sufmin = np.minimum.accumulate(cls[by_inv][::-1])[::-1] if len(cl) else np.zeros(0, np.int64)
+        at = np.searchsorted(inv[by_inv], ret[core], side="right")              # the first clean read invoked after P returned
+        rt_out = np.where(at < len(cl), np.append(sufmin, INF)[at], INF)
+        premax = np.maximum.accumulate(cls[cl]) if len(cl) else np.zeros(0, np.int64)
+        nb = np.searchsorted(ret[cl], inv[core], side="left")                   # the clean reads that returned before P was invoked
+        rt_in = np.where(nb > 0, np.append(premax, -1)[nb - 1], -1)
+        s_out, s_in = np.minimum(mono_out, rt_out), np.maximum(mono_in, rt_in)
+        m_out, m_in = (mono_out == s_out) & (s_out < INF), (mono_in == s_in) & (s_in >= 0)
+        A = np.zeros((m, m), bool)
+        for i in range(m):
+            both = Kp & Kp[i]
+            A[i] = (both & (Vp[i] < Vp)).any(axis=1) | (ret[core[i]] < inv[core])
+            A[i] |= (s_out[i] < s_in) | ((s_out[i] == s_in) & (m_out[i] | m_in))
+        while True:
+            B = _bool_square(A)
+            rounds += 1
+            if (B == A).all():
+                break
+            A = B
+        S = A & A.T
+        np.fill_diagonal(S, True)
+        rep = S.argmax(axis=1)                                                   # the least core read of P's component
+        for k in np.flatnonzero(rep == np.arange(m)):
+            mem = np.flatnonzero(rep == k)
+            lo, hi = s_out[mem].min(), s_in[mem].max()
+            at_lo, at_hi = mem[s_out[mem] == lo], mem[s_in[mem] == hi]
+            lo_mono, hi_mono = m_out[at_lo].any(), m_in[at_hi].any()
+            lo_ret, hi_inv = ret[core[at_lo]].min(), inv[core[at_hi]].max()
+            inside = ((cls[cl] > lo) | ((cls[cl] == lo) & (lo_mono | (inv[cl] > lo_ret)))) & ((cls[cl] < hi) | ((cls[cl] == hi) & (hi_mono | (ret[cl] < hi_inv))))
+            assert not on[cl[inside]].any()                                      # (components are disjoint: a clean read joins one)
+            members = np.concatenate([core[mem], cl[inside]])
+            if len(members) >= 2:
+                scc[members], on[members] = members.min(), True
+    flags = (np.where(complete, 0, CYC_PARTIAL) | np.where(on, CYC_ON_CYCLE, 0) | np.where(clean, 0, CYC_CORE)).astype(np.uint8)
+    scc = scc.astype(np.uint32)
+    return {"scc": scc, "flags": flags, "summary": _cyc_summary(scc, flags, int(K.sum()) // 2, rounds)}
+
+
+def _cyc_times(cols):
+    """inv and ret of the :ok reads of a LedgerColumns (pairing by process, as the realtime rules state it)"""
+    rd = np.flatnonzero((cols.type == N.LEDGER_T_OK) & (cols.kind == N.LEDGER_K_READ))
+    partner = _partner_rows(cols)[rd]
+    index = cols.index.astype(np.int64)
+    return np.where(partner >= 0, index[np.maximum(partner, 0)], -1), index[rd]
+
+
+def cycles_numpy(history, opts=None):
+    """cycles_host(history, opts) by the reduction (cycles_dense_numpy over the history's LedgerColumns), closure_rounds included."""
+    accounts = _snap_accounts(None, opts)
+    cols = LedgerColumns(history)
+    return cycles_dense_numpy(*_snap_dense(cols, accounts), *_cyc_times(cols))
+
+
+def _cyc_witness(vectors, inv, ret, members, label):
+    """one shortest cycle through `label` inside its component, by BFS: [(from, to, edge)]"""
+    inside = set(members)
+    prev, frontier = {}, [label]
+    while frontier:
+        nxt = []
+        for a in frontier:
+            for b in sorted(inside):
+                if b != a and b not in prev and _cyc_edge(vectors, inv, ret, a, b):
+                    prev[b] = a
+                    if b == label:
+                        path = [label]
+                        while True:
+                            path.append(prev[path[-1]])
+                            if path[-1] == label:
+                                break
+                        path.reverse()
+                        return [(a2, b2, _cyc_edge(vectors, inv, ret, a2, b2)) for a2, b2 in zip(path, path[1:])]
+                    nxt.append(b)
+        frontier = nxt
+    return []
+
+
+def _cyc_map(history, res, accounts):
+    """the cycles result map from the per-read arrays and the summary (the host statement's or the device's)"""
+    s = res["summary"]
+    out = {"valid?": bool(s["valid"]), "exact?": True, "read-count": s["read_count"], "partial-count": s["n_partial"], "core-count": s["n_core"],
+           "on-cycle-count": s["n_on_cycle"], "component-count": s["n_components"], "largest-size": s["largest_size"], "components": [], "witness": None}
+    if not s["n_on_cycle"]:                             # (no read to name: no pass over the history)
+        return out
+    hist = _indexed(history) if any("index" not in op for op in history) else history
+    vectors, index, inv, ret = _cyc_model(history, accounts)
+    scc = res["scc"]
+    labels = np.unique(scc[scc != N.NO_OP])
+    for label in labels[:10]:
+        members = np.flatnonzero(scc == label)
+        out["components"].append({"label": hist[index[int(label)]], "size": len(members), "ops": [hist[index[int(r)]] for r in members[:10]]})
+    members = np.flatnonzero(scc == labels[0])
+    if len(members) <= 4096:
+        counter = lambda c: [accounts[int(c) // 2], RT_FIELDS[int(c) % 2]]
+        steps = []
+        for a, b, e in _cyc_witness(vectors, inv, ret, [int(r) for r in members], int(labels[0])):
+            step = {"from": hist[index[a]], "to": hist[index[b]], "type": e[0]}
+            if e[0] == "monotonic":
+                step.update({"key": counter(e[1]), "value": vectors[a][e[1]], "value'": vectors[b][e[1]]})
+            steps.append(step)
+        out["witness"] = steps
+    return out
+
+
+class CycleSearch(jc.Checker):
+    """cycles: the graph of monotonic-key and realtime edges over the :ok reads is acyclic, partial reads included (module docstring,
+    "Cycle search") -- the host statement: the explicit graph and Tarjan.  opts: "accounts"."""
+
+    def __init__(self, opts=None):
+        self.opts = dict(opts or {})
+
+    def check(self, test, history, opts=None):
+        accounts = _snap_accounts(test, self.opts)
+        vectors, _index, inv, ret = _cyc_model(history, accounts)
+        return _cyc_map(history, cycles_vectors_host(vectors, inv, ret, len(accounts)), accounts)
+
+
+def cyc_summary_dict(s):
+    return {f: int(getattr(s, f)) for f, _ in N.LedgerCyclesSummary._fields_ if f != "reserved0"}
+
+
+def check_cycles_native(cols, accounts, device=0, call=None):
+    """tbc_ledger_cycles over the columns -> cycles_host's arrays and the summary (with closure_rounds, ns_device and bytes_in).
+    call(in, out) -> status: another implementation of the entry point (the tests' emulator build of the same kernels).  A read out of
+    range is the device's to find: ValueError here too.  A core above TBC_LEDGER_CYCLES_MAX_CORE: {"unsupported": True, "summary"} with
+    n_core filled and no arrays."""
+    init = {a: (0, 0) for a in accounts}
+    s, keep = ledger_rt_in(cols, accounts, init, True, device)
+    R = len(cols.read_ops)
+    arr = {"scc": np.zeros(max(1, R), np.uint32), "cyc_flags": np.zeros(max(1, R), np.uint8)}
+    out = N.LedgerCyclesOut()
+    out.scc, out.cyc_flags = _ptr(arr["scc"], C.c_uint32), _ptr(arr["cyc_flags"], C.c_uint8)
+    st = N.lib().tbc_ledger_cycles(C.byref(s), C.byref(out)) if call is None else call(s, out)
+    del keep
+    summary = cyc_summary_dict(out.summary)
+    if st == N.ERR_UNSUPPORTED and not summary["bad_values"]:                # (the only other refusal the device makes: the core is above the cap)
+        return {"unsupported": True, "summary": summary}
+    if st == N.ERR_UNSUPPORTED:
+        raise ValueError("cycles: " + (N.lib().tbc_last_error().decode() if call is None else "reads hold counters whose magnitudes add up to 2^63 or more"))
+    if call is None:
+        N.check_status(st)
+    else:
+        assert st == 0, st
+    return {"scc": arr["scc"][:R], "flags": arr["cyc_flags"][:R], "summary": summary}
+
+
+def cycles_result_map(history, cols, dev, accounts):
+    """CycleSearch's result map from tbc_ledger_cycles' arrays and summary; the components it names and the witness come from the history
+    on the host (a valid history: none, and no pass over it).  Above the cap: "valid?" "unknown"."""
+    assert dev["summary"]["read_count"] == len(cols.read_ops)
+    if dev.get("unsupported"):
+        return {"valid?": "unknown", "searched?": False, "n-core": dev["summary"]["n_core"]}
+    return _cyc_map(history, dev, list(accounts))
+
+
+class _CycleDevice(jc.Checker):
+    """the cycles member on the device route: columns -> tbc_ledger_cycles -> CycleSearch's map.  No host route behind it."""
+
+    def __init__(self, opts):
+        self.opts = dict(opts or {})
+
+    def check(self, test, history, opts=None):
+        accounts = _snap_accounts(test, self.opts)
+        cols = LedgerColumns(history)
+        dev = check_cycles_native(cols, accounts, device=(opts or {}).get("device", 0))
+        return cycles_result_map(history, cols, dev, accounts)
+
+
 # ---------------------------------------------------------------- the journal audit of the lookups
 
 JN_KINDS = ("unknown", "altered", "repeated", "failed", "early", "lost", "vanished", "ahead", "behind")       # by TBC_LEDGER_JN_*
@@ -1523,12 +1872,12 @@ class _JournalDevice(jc.Checker):
         return journal_result_map(history, cols, dev)
 
 
-def test(opts=None, linear=False, realtime=False, device_route=True, snapshots=False, journal=False):
+def test(opts=None, linear=False, realtime=False, device_route=True, snapshots=False, journal=False, cycles=False):
     """The ledger test map (tests/ledger.clj:341-369) without generators: accounts, max-transfer, total-amount and the composed checker
     -- SI, lookup-transfers, final-reads, unexpected-ops, with linear=True the member clj/patches/ledger.patch adds, and with
     realtime=True the member "realtime" (RealtimeBounds; opts "initial", "ok-transfers-apply?") and with snapshots=True the member
-    "snapshots" (SnapshotOrder) and with journal=True the member "journal" (JournalAudit; realtime's opts), each on the device or as the
-    host statement according to device_route.
+    "snapshots" (SnapshotOrder) and with journal=True the member "journal" (JournalAudit; realtime's opts) and with cycles=True the member "cycles"
+    (CycleSearch), each on the device or as the host statement according to device_route.
     device_route=True (the default: the whole call measured 1.7-1.8 s against the host statement's 6.6-6.7 s on a ledger of 64 workers and 50k
     transfers, profiles/NOTES_ledger.md) answers the first three from one check_columns call; False runs the host statement."""
     opts = dict(opts if opts is not None else {"negative-balances?": False})
@@ -1547,6 +1896,8 @@ def test(opts=None, linear=False, realtime=False, device_route=True, snapshots=F
         members["snapshots"] = _SnapshotDevice(opts) if device_route else SnapshotOrder(opts)
     if journal:
         members["journal"] = _JournalDevice(opts) if device_route else JournalAudit(opts)
+    if cycles:
+        members["cycles"] = _CycleDevice(opts) if device_route else CycleSearch(opts)
     if linear:
         members["linear"] = _Linear(opts["accounts"], bool(opts.get("negative-balances?", False)))
     return dict(opts, checker=jc.compose(members))
