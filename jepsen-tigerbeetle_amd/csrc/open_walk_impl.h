@@ -24,8 +24,9 @@
 // call open at my front?" for the ~6 x 64 times the answer is yes.  The sparse form has no loop over the candidates with lane = front: a
 // call is open at fronts inv .. ret, so with lane = candidate it toggles a bit ON at the first of them and OFF behind the last in a 64-entry
 // array in LDS, and with lane = front an inclusive XOR scan over the lanes gives every front its set of open calls.  Three kinds of set:
-// bit = place in list order (each lane then walks ITS bits and stores its front's list entries; a twin mask comes down a chain that links
-// the calls of one effect by completion, phase B2), bit = process slot per read-row entry present (the scan is the row entry), bit =
+// bit = place in list order (the fronts leave their sets in LDS and the list entries are stored with lane = ENTRY, 64 consecutive entries of
+// the chunk a store instruction -- whole lines of lst / twn: an entry lane finds its front and takes the k-th set bit of the front's words,
+// sparse_lists; a twin mask comes down a chain that links the calls of one effect by completion, phase B2), bit = process slot per read-row entry present (the scan is the row entry), bit =
 // process slot per produced value some front needs (the scan is the producer mask).  The producer distance comes from byte counters of the
 // invocation ranks, per produced value.  The tables it leaves are the dense loop's, word for word.
 // What keeps the dense loop, decided per chunk by a uniform condition (`sparse` in walk_chunk):
@@ -134,11 +135,23 @@ constexpr uint32_t kStatWalkSparse = 43, kStatWalkDense = 44, kStatWalkEmitTrips
 constexpr uint32_t kStatWalkCands = 49;     // + 0 / 1 / 2: chunks of at most 64, of 65 .. kSparseCand, of more candidates
 // what the WAVEFRONT runs of the two per-lane loops, i.e. the longest lane's steps: of B2's bucket walk (per pass and set), of the twin chain (per trip)
 constexpr uint32_t kStatWalkFindWave = 52, kStatWalkChainWave = 53;
+// the sparse form's stores with lane = entry (its emission trips are passes of 64 entries): list entries of the chunks, fronts whose off[] is not
+// where the running sum of the counts puts them, entries that have no candidate (both zero unless a mutation is planted), entries whose place in
+// list order is in the second set of 64
+constexpr uint32_t kStatWalkEntries = 54, kStatWalkNotContiguous = 55, kStatWalkBadPlace = 56, kStatWalkSecondSet = 57;
+constexpr uint32_t kStatWalkLstLines = 58;  // the 128-byte lines of lst the form's store instructions touch, summed over the instructions
 #if defined(TBC_EMU)
 // (emulated build) the largest n over the lanes, added to a count: one ballot per step of the longest lane
 #define WV_STAT_WAVE_MAX(id, n) do { for (uint32_t k_ = 1u; wv::ballot((n) >= k_) != 0ull; k_++) if (lane == 0u) wv::stat((id), 1); } while (0)
+// (emulated build) the different 128-byte lines one store instruction touches -- `on`: the lane stores, at byte `at` of its table -- added to a count
+#define WV_STAT_WAVE_LINES(id, on, at) do { uint32_t n_ = 0u; uint64_t seen_[64]; \
+    for (uint32_t j_ = 0u; j_ < 64u; j_++) { const uint64_t l_ = wv::readlane64((on) ? ((uint64_t)(at) >> 7) + 1ull : 0ull, j_); bool new_ = l_ != 0ull; \
+      for (uint32_t i_ = 0u; i_ < n_; i_++) new_ = new_ && seen_[i_] != l_; \
+      if (new_) seen_[n_++] = l_; } \
+    if (lane == 0u) wv::stat((id), n_); } while (0)
 #else
 #define WV_STAT_WAVE_MAX(id, n) do { (void)(n); } while (0)
+#define WV_STAT_WAVE_LINES(id, on, at) do { } while (0)
 #endif
 
 // ---- the sparse form of phase C: what it is made of
@@ -616,15 +629,48 @@ WV_DEV void sparse_producers(const Chunk& K, uint32_t NC, uint32_t lane, const F
   }
   store_look(K, f, pm, dmin);
 }
-// sparse_lists: bit = the candidate's place in list order, listed candidates only, 64 places a pass: a front's list entries, ascending bit =
-// list order.  The entries: each lane walks the set bits of its words, lowest first, and takes the candidate's record from the table at an
-// address of its own; the wavefront goes on while any lane has a bit left -- the longest list of the pass, not NC.  The twin mask of an entry
-// at front F: down the chain of its effect (link_twins) from the call itself, the slots of the calls open at F -- the chain is in order of
-// completion, so it ends at the first call that completed before F.
-// pos: where the front's next list entry goes (lst, twn)
-WV_DEV uint32_t sparse_lists(const Chunk& K, uint32_t NC, uint32_t lane, const Front& f, const uint32_t (&c_fl)[kSparseSets], bool by_ret, uint32_t pos) {
+// sparse_lists: bit = the candidate's place in list order, listed candidates only, 64 places a round: a front's list entries, ascending bit =
+// list order.  The entries are then stored with LANE = ENTRY.  A chunk's entries are one contiguous piece of lst / twn -- off[] is the
+// running sum of the fronts' counts, so front F's entries follow front F - 1's -- and a store instruction with consecutive lane = consecutive
+// entry writes 1 KB (lst) resp. 512 B (twn) of whole lines, where lane = front wrote 64 pieces some 100 B apart.
+//   * The front lanes leave their sets in the round buffer (a front's four toggle words are its two sets of 64 places: the rounds are over) and
+//     keep their count; an add-scan over the lanes gives each front the chunk-relative position of its first entry.
+//   * The entries are taken 64 at a time.  A front whose first entry lies in the pass marks it: its number in the byte of that entry (the
+//     bytes lie over the rank counters of sparse_producers, which is done).  An entry lane finds its front by a max-scan over the lanes of
+//     (front, lane of the mark) -- both grow with the lane -- or, before the pass's first mark, takes the front the pass before ended in;
+//     its rank k within the front is its distance from the mark.
+//   * It takes the k-th set bit of the front's words (kth_set_bit), which is its candidate's place, the candidate's record from the table at an
+//     address of its own, and walks the twin chain: the twin mask of an entry at front F is, down the chain of its effect (link_twins) from the
+//     call itself, the slots of the calls open at F -- the chain is in order of completion, so it ends at the first call that completed before F.
+// Returns where the lane's front's list ends (lst, twn).
+// the place (0 .. 127) of the k-th set bit, k from 0, of the 128 bits t.x | t.y << 32 | t.z << 64 | t.w << 96, which have more than k bits set
+WV_DEV uint32_t kth_set_bit(const wv::u32x4& t, uint32_t k) {
+  const uint32_t c0 = (uint32_t)__builtin_popcount(t.x), c1 = c0 + (uint32_t)__builtin_popcount(t.y), c2 = c1 + (uint32_t)__builtin_popcount(t.z);
+  uint32_t w = t.x, p = 0u;
+  if (k >= c2) { w = t.w; p = 96u; k -= c2; } else if (k >= c1) { w = t.z; p = 64u; k -= c1; } else if (k >= c0) { w = t.y; p = 32u; k -= c0; }
+  WV_UNROLL
+  for (uint32_t s = 16u; s != 0u; s >>= 1) {
+    const uint32_t c = (uint32_t)__builtin_popcount(w & ((1u << s) - 1u));
+    if (k >= c) { k -= c; w >>= s; p += s; }
+  }
+  return p;
+}
+// an inclusive max-scan over the 64 lanes (xor_scan's form; 0 is below everything scanned)
+WV_DEV uint32_t max_scan(uint32_t x, uint32_t lane) {
+  const auto mx = [](uint32_t a, uint32_t b) { return a > b ? a : b; };
+  x = mx(x, wv::row_shr0<1>(x)); x = mx(x, wv::row_shr0<2>(x)); x = mx(x, wv::row_shr0<4>(x)); x = mx(x, wv::row_shr0<8>(x));
+  const uint32_t t0 = wv::readlane(x, 15u), t1 = wv::readlane(x, 31u), t2 = wv::readlane(x, 47u);
+  return mx(mx(x, lane >= 16u ? t0 : 0u), mx(lane >= 32u ? t1 : 0u, lane >= 48u ? t2 : 0u));
+}
+// (planted by tests/emu, see test_walk_lines_emu.py: the rank within the front one too high; a front whose first entry is a pass's first is not marked there)
+#if !defined(TBC_EMU) && (defined(TBC_WALK_RANK_OFF_BY_ONE) || defined(TBC_WALK_FRONT_LE))
+#error "the planted mutations of the front walk are for tests/emu (TBC_EMU) only"
+#endif
+WV_DEV uint32_t sparse_lists(const Chunk& K, uint32_t NC, uint32_t lane, const Front& f, const uint32_t (&c_fl)[kSparseSets], bool by_ret) {
+  static_assert(kSparseSets == 2 && kTogWords == 64u * 4u && kRankCntWords >= 16u, "a front's two sets are its four toggle words; 64 mark bytes");
   const uint32_t* const cand = K.cand;
-  const uint32_t F = f.F;
+  uint32_t* const mark = K.rcnt;
+  uint64_t open[kSparseSets] = {0ull, 0ull};
   WV_UNROLL
   for (int g = 0; g < kSparseSets; g++) {
     if (64u * (uint32_t)g >= NC) continue;
@@ -633,40 +679,89 @@ WV_DEV uint32_t sparse_lists(const Chunk& K, uint32_t NC, uint32_t lane, const F
     WV_UNROLL
     for (int s = 0; s < kSparseSets; s++)
       if ((c_fl[s] & kCList) && ((c_fl[s] >> 9) & 3u) == (uint32_t)g) { const uint32_t* e = cand + (lane + 64u * (uint32_t)s) * kCandWords; toggle_slot(K.tog, K.F_lo, e[0], e[1], (c_fl[s] >> 18) & 63u); }
-    const uint64_t open = open_bits(K.tog, lane, true);
-    uint64_t cur = f.active ? open : 0ull;
+    const uint64_t o = open_bits(K.tog, lane, true);
+    open[g] = f.active ? o : 0ull;
     wv::barrier();
-    WV_NOUNROLL
-    while (wv::ballot(cur != 0ull) != 0ull) {
-      if (lane == 0u) wv::stat(kStatWalkEmitTrips, 1);
-      uint32_t chain_steps = 0u;                                    // (counted for the emulated build's statistics only)
-      if (cur != 0ull) {
-        const uint32_t p = 64u * (uint32_t)g + (uint32_t)__builtin_ctzll(cur);
-        cur &= cur - 1ull;
-        const uint32_t* e = cand + (by_ret ? (uint32_t)K.perm[p] : p) * kCandWords;
-        OpRec o; o.op = e[2]; o.f_slot = e[3] | (e[1] == F ? kAtFront : 0u); o.a = (int32_t)e[4]; o.b = (int32_t)e[5];
-        K.lst[pos] = o;
-        if (K.twn) {
-          uint64_t tw = 0ull;
-          for (uint32_t u = e[7] & 0xFFu; u != 0xFFu;) {
-            const uint32_t* eu = cand + u * kCandWords;
-            wv::stat(kStatWalkTwinSteps, 1);
-            chain_steps++;
-            if (eu[1] < F) break;
-            if (eu[0] <= F) tw |= 1ull << ((eu[3] >> 8) & 63u);
-#if defined(TBC_WALK_TWIN_LE)
-            if ((eu[7] & 0xFFu) == u) break;
-#endif
-            u = eu[7] & 0xFFu;
-          }
-          K.twn[pos] = tw;
-        }
-        pos++;
-      }
-      WV_STAT_WAVE_MAX(kStatWalkChainWave, chain_steps);
-    }
   }
-  return pos;
+  // lane = front: the sets into the round buffer; where the front's entries start within the chunk's
+  *reinterpret_cast<wv::u32x4*>(K.tog + lane * 4u) = wv::u32x4{(uint32_t)open[0], (uint32_t)(open[0] >> 32), (uint32_t)open[1], (uint32_t)(open[1] >> 32)};
+  const uint32_t n = (uint32_t)__builtin_popcountll(open[0]) + (uint32_t)__builtin_popcountll(open[1]);
+  uint32_t incl = n;
+  incl += wv::row_shr0<1>(incl); incl += wv::row_shr0<2>(incl); incl += wv::row_shr0<4>(incl); incl += wv::row_shr0<8>(incl);
+  {
+    const uint32_t t0 = wv::readlane(incl, 15u), t1 = t0 + wv::readlane(incl, 31u), t2 = t1 + wv::readlane(incl, 47u);
+    incl += lane >= 48u ? t2 : lane >= 32u ? t1 : lane >= 16u ? t0 : 0u;
+  }
+  const uint32_t start = incl - n, total = wv::readlane(incl, 63u);
+  const uint32_t base = wv::readlane(f.pos0, 0u);                   // (the chunk has a front: lane 0's)
+#if defined(TBC_EMU)
+  if (f.active && f.pos0 != base + start) wv::stat(kStatWalkNotContiguous, 1);      // off[] is the running sum of the fronts' counts
+  if (lane == 0u) wv::stat(kStatWalkEntries, total);
+#endif
+  // lane = entry, 64 at a time
+  uint32_t carry_front = 0u, carry_start = 0u;                      // (uniform) the front the pass before ended in, and where its entries start
+  WV_NOUNROLL
+  for (uint32_t e0 = 0u; e0 < total; e0 += 64u) {
+    if (lane == 0u) wv::stat(kStatWalkEmitTrips, 1);
+    if (lane < 16u) mark[lane] = wv::opaque(0u);
+    wv::barrier();
+#if defined(TBC_WALK_FRONT_LE)
+    if (n != 0u && !(start <= e0) && start - e0 < 64u)
+#else
+    if (n != 0u && !(start < e0) && start - e0 < 64u)
+#endif
+      wv::lds_add32(&mark[(start - e0) >> 2], (0x40u | lane) << (8u * ((start - e0) & 3u)));      // (one front starts at an entry: adding is setting)
+    wv::barrier();
+    const uint32_t mb = (mark[lane >> 2] >> (8u * (lane & 3u))) & 0xFFu;
+    const uint32_t mv = max_scan(mb ? (0x1000u | ((mb & 63u) << 6) | lane) : 0u, lane);
+    const uint32_t fr = mv ? (mv >> 6) & 63u : carry_front;
+#if defined(TBC_WALK_RANK_OFF_BY_ONE)
+    const uint32_t k = (mv ? lane - (mv & 63u) : e0 + lane - carry_start) + 1u;
+#else
+    const uint32_t k = mv ? lane - (mv & 63u) : e0 + lane - carry_start;
+#endif
+    {
+      const uint32_t last = wv::readlane(mv, 63u);
+      if (last != 0u) { carry_front = (last >> 6) & 63u; carry_start = e0 + (last & 63u); }
+    }
+    uint32_t chain_steps = 0u;                                      // (counted for the emulated build's statistics only)
+    if (e0 + lane < total) {
+      const uint32_t F = K.F_lo + fr;
+      const wv::u32x4 sets = *reinterpret_cast<const wv::u32x4*>(K.tog + fr * 4u);
+      const uint32_t p = kth_set_bit(sets, k);
+      uint32_t ci = by_ret ? (uint32_t)K.perm[p] : p;
+#if defined(TBC_EMU)
+      if (p >= 64u) wv::stat(kStatWalkSecondSet, 1);
+      if (ci >= NC || k >= (uint32_t)__builtin_popcount(sets.x) + (uint32_t)__builtin_popcount(sets.y) + (uint32_t)__builtin_popcount(sets.z) + (uint32_t)__builtin_popcount(sets.w)) {
+        wv::stat(kStatWalkBadPlace, 1);                             // (no such entry: a planted mutation; the read below stays inside the table)
+        ci = 0u;
+      }
+#endif
+      const uint32_t* e = cand + ci * kCandWords;
+      const uint64_t at = (uint64_t)base + e0 + lane;
+      OpRec o; o.op = e[2]; o.f_slot = e[3] | (e[1] == F ? kAtFront : 0u); o.a = (int32_t)e[4]; o.b = (int32_t)e[5];
+      K.lst[at] = o;
+      if (K.twn) {
+        uint64_t tw = 0ull;
+        for (uint32_t u = e[7] & 0xFFu; u != 0xFFu;) {
+          const uint32_t* eu = cand + u * kCandWords;
+          wv::stat(kStatWalkTwinSteps, 1);
+          chain_steps++;
+          if (eu[1] < F) break;
+          if (eu[0] <= F) tw |= 1ull << ((eu[3] >> 8) & 63u);
+#if defined(TBC_WALK_TWIN_LE)
+          if ((eu[7] & 0xFFu) == u) break;
+#endif
+          u = eu[7] & 0xFFu;
+        }
+        K.twn[at] = tw;
+      }
+    }
+    WV_STAT_WAVE_MAX(kStatWalkChainWave, chain_steps);
+    WV_STAT_WAVE_LINES(kStatWalkLstLines, e0 + lane < total, (K.B->lst_off + base + e0 + lane) * sizeof(OpRec));
+    wv::barrier();                                                  // (the marks are read: the next pass zeroes them)
+  }
+  return f.pos0 + n;
 }
 
 // ---- C, THE DENSE LOOP: iteration t broadcasts the candidate at place t of the list order to the 64 lanes, and each lane decides for ITS
@@ -835,7 +930,7 @@ WV_DEV bool walk_chunk(const PackOpenArgs& A_, uint32_t h, uint32_t c, uint32_t*
     dense = false;
     sparse_read_rows(K, NC, lane, f, c_fl);
     sparse_producers(K, NC, lane, f, c_fl);
-    pos = sparse_lists(K, NC, lane, f, c_fl, by_ret, pos);
+    pos = sparse_lists(K, NC, lane, f, c_fl, by_ret);
   }
   if (dense) pos = dense_loop<VCAP>(K, NC, lane, f, c_key, c_ret, by_ret, pos);
   // D: words 6 and 7 of a compact record
