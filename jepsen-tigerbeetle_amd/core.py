@@ -183,10 +183,13 @@ class Batch:
     @staticmethod
     def wire_words(f, a, b, process):
         """TBC_WIRE_WORD over columns: f | a << 4 | b << 12 | process << 20 (nil = 0xFF); values must be 0..254, processes 0..4095."""
-        a8 = np.where(a == N.NIL, N.WIRE_NIL, a).astype(np.uint32)
-        b8 = np.where(b == N.NIL, N.WIRE_NIL, np.where(f == N.F_CAS, b, 0)).astype(np.uint32)
-        if len(a8) and (int(a8.max()) > 255 or int(b8.max()) > 255 or int(process.max()) > 4095 or int(process.min()) < 0):
+        # (checked BEFORE nil becomes 0xFF: a value of 255 would travel as a nil read, which every state allows)
+        cas = f == N.F_CAS
+        if len(a) and (bool((((a < 0) | (a >= N.WIRE_NIL)) & (a != N.NIL)).any()) or bool((cas & ((b < 0) | (b >= N.WIRE_NIL)) & (b != N.NIL)).any())
+                       or int(process.max()) > 4095 or int(process.min()) < 0):
             raise ValueError("the wire format holds values 0..254 (or nil) and processes 0..4095")
+        a8 = np.where(a == N.NIL, N.WIRE_NIL, a).astype(np.uint32)
+        b8 = np.where(b == N.NIL, N.WIRE_NIL, np.where(cas, b, 0)).astype(np.uint32)
         return f.astype(np.uint32) | (a8 << np.uint32(4)) | (b8 << np.uint32(12)) | (process.astype(np.uint32) << np.uint32(20))
 
     def fill_input(self, slot, histories: Sequence[OpColumns]):

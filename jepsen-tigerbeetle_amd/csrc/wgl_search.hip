@@ -316,6 +316,18 @@ __device__ void search_one(const SearchArgs& A, const uint32_t hidx, uint32_t* r
       }
       n_cfg += (uint32_t)__popcll(hb);
     }
+    // the root (the initial state, nothing linearized) is pushed without a lookup, so the set never holds it: where the FIRST completion is
+    // the one that fails, it is stuck there like every config found above -- and the only one when no open call can be linearized at all
+    if (maxf == 0u) {
+      if (lane == 0 && n_cfg < kCfgCap) {
+        uint64_t* o = cfg + (uint64_t)n_cfg * (2 + MW);
+        o[0] = 1ull | ((uint64_t)(uint32_t)A.init_state << 32);
+#pragma unroll
+        for (int j = 0; j < MW; j++) o[1 + j] = 0ull;
+        o[1 + MW] = (uint64_t)TBC_NO_OP;
+      }
+      n_cfg++;
+    }
   }
   // ---- results
   if (A.dbg && lane == 0) { A.dbg[4] = 0x200u + hidx; A.dbg[16] = (uint32_t)verdict; A.dbg[17] = (uint32_t)steps; }

@@ -576,7 +576,9 @@ int sweep_ref_check(uint32_t n, const uint8_t* f, const int32_t* a, const int32_
     if (F1 == R) { for (uint32_t q = 0; q < 32; q++) if (next_live[0] >> q & 1) { final_state = regfam ? dom[q < nd ? q : 0] : model->init; break; } }
     memcpy(live, next_live, sizeof live);
   }
-  if (verdict == 1 && !regfam) final_state = cur.n ? (int32_t)(uint32_t)(cur.key[0] >> 32) : model->init;
+  /* (a register without a value domain -- a value past 30, a negative one: nd = 1, the one uncut segment's origin the init -- has no index to
+     name its last state by either: the state itself, as the library reports it there, batch_run.hip sweep_verdicts) */
+  if (verdict == 1 && (!regfam || nd < 2)) final_state = cur.n ? (int32_t)(uint32_t)(cur.key[0] >> 32) : model->init;
 
   if (g_rel && verdict == 1) verdict = -1;
   out->valid = verdict < -1 ? -1 : verdict;

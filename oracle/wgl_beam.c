@@ -448,7 +448,10 @@ int wgl_beam_check_rp(uint32_t n, const uint8_t* f, const int32_t* a, const int3
   }
   spair[sp] = 0xFFFFu;
   stack[sp++] = arena_add(&ar, key, 0, 0xFFFFFFFFu);
-  st->visited = 1; st->max_stack = 1;
+  /* a root that passed every completion is never searched: no config is counted, as for a history without a completion (R == 0 above) --
+     the narrow kernel's count (wgl_narrow_impl.h, init_group: "nothing to search"); tests/test_state_domain_oracle.py pins verdict and
+     final state of such histories by brute force */
+  st->visited = root_wins ? 0 : 1; st->max_stack = root_wins ? 0 : 1;
 
   uint8_t* unchecked = NULL; size_t unchecked_cap = 0;          /* lazy_look: configs pushed without their lookahead run, by arena id */
   g_look_runs = 0;

@@ -243,9 +243,16 @@ int wgl_window_check(uint32_t n, const uint8_t* f, const int32_t* a, const int32
     free(g_cfg); g_cfg = NULL; g_cfg_n = 0; g_cfg_kw = KW;
     size_t cnt = 0;
     for (size_t j = 0; j < vs.cap; j++) if ((uint32_t)vs.tab[j * KW] == maxf + 1) cnt++;
-    g_cfg = (uint64_t*)malloc((cnt ? cnt : 1) * KW * 8);
+    g_cfg = (uint64_t*)malloc((cnt + 1) * KW * 8);
     for (size_t j = 0; j < vs.cap; j++)
       if ((uint32_t)vs.tab[j * KW] == maxf + 1) { memcpy(g_cfg + (size_t)g_cfg_n * KW, vs.tab + j * KW, KW * 8); g_cfg_n++; }
+    /* the root (the initial state, nothing linearized) is searched without ever entering the set: where the FIRST completion fails it is stuck
+       there too -- the only config at all when no open call can be linearized (knossos reports it; tests/test_state_domain_oracle.py) */
+    if (maxf == 0) {
+      memset(g_cfg + (size_t)g_cfg_n * KW, 0, KW * 8);
+      g_cfg[(size_t)g_cfg_n * KW] = 1ull | ((uint64_t)(uint32_t)(oracle_is_cfg_model(model) ? 0 : model->init) << 32);
+      g_cfg_n++;
+    }
     g_sort_kw = KW;
     qsort(g_cfg, g_cfg_n, KW * 8, cmp_cfg);
   }

@@ -181,9 +181,10 @@ def build_sweep(force=False):
     return _SO_SWEEP
 
 
-def sweep_wg(ops, model_kind, init, seg_target, n_dom, max_segs, waves=8, cap=1024, rules=None, seed=1, rel_bytes=688, again=None, first=None, compact=False, relaxed=False):
+def sweep_wg(ops, model_kind, init, seg_target, n_dom, max_segs, waves=8, cap=1024, rules=None, seed=1, rel_bytes=688, again=None, first=None, compact=False, relaxed=False, vpad=None):
     """ONE history through K6w: max_segs * 4 tbc_sweep_rel records as a uint8 array (as oracle.wgl.sweep_relations returns them).
-    again = [(segment, slice), ...] with first = the first pass's records: the second pass over those segments only."""
+    again = [(segment, slice), ...] with first = the first pass's records: the second pass over those segments only.
+    vpad: the tables' row length where the history is one of a batch whose largest value is another's (default: the history's own)."""
     global _LIB_SWEEP
     if _LIB_SWEEP is None:
         _LIB_SWEEP = C.CDLL(build_sweep())
@@ -191,7 +192,9 @@ def sweep_wg(ops, model_kind, init, seg_target, n_dom, max_segs, waves=8, cap=10
     d = ops if isinstance(ops, dict) else ops.as_dict()
     f, a, b = (np.ascontiguousarray(d[k], t) for k, t in (("f", np.uint8), ("a", np.int32), ("b", np.int32)))
     pr, inv, ret = (np.ascontiguousarray(d[k], t) for k, t in (("process", np.int32), ("inv_pos", np.uint32), ("ret_pos", np.uint32)))
-    r, vpad = rules_for([d], model_kind, init)
+    r, own = rules_for([d], model_kind, init)
+    assert vpad is None or (own and vpad >= own), (vpad, own)
+    vpad = own if vpad is None else vpad
     if rules is not None:
         r &= rules
     buf = np.zeros(max_segs * 4 * rel_bytes, np.uint8) if again is None else np.array(first, np.uint8, copy=True)

@@ -20,7 +20,9 @@ def _records(buf):
     return np.frombuffer(buf, dtype=np.uint8).reshape(-1, C.sizeof(N.SweepRel))
 
 
-def _compare(ops, seg_target, n_dom, waves, cap=1024, rules=None, seed=1, expect_overflow=False, second_pass=False, compact=False, relaxed=False):
+def _compare(ops, seg_target, n_dom, waves, cap=1024, rules=None, seed=1, expect_overflow=False, second_pass=False, compact=False, relaxed=False, model=CAS, vpad=None):
+    """model: the oracle's model dict (kind and init), the emulated kernel's with it; the module's cas-register from nil unless named.
+    vpad: the batch's row length where the history alone would have a shorter one."""
     d = ops.as_dict()
     R = int((np.asarray(d["ret_pos"]) != 0xFFFFFFFF).sum())
     max_segs = max(1, min(512, (R + seg_target - 1) // seg_target)) if seg_target else 1
@@ -29,17 +31,17 @@ def _compare(ops, seg_target, n_dom, waves, cap=1024, rules=None, seed=1, expect
     buf = np.zeros(max_segs * 4 * C.sizeof(N.SweepRel), np.uint8)
     L.sweep_set_export(buf.ctypes.data_as(C.c_void_p), C.c_uint32(max_segs), C.c_uint32(0), C.c_uint32(1))
     try:
-        wgl.check_sweep(d, CAS, eager_reads=eager, twin_rule=twin, seg_target=seg_target, n_dom=n_dom, relaxed=relaxed)
+        wgl.check_sweep(d, model, eager_reads=eager, twin_rule=twin, seg_target=seg_target, n_dom=n_dom, relaxed=relaxed)
     finally:
         L.sweep_set_export(None, C.c_uint32(0), C.c_uint32(0), C.c_uint32(1))
-    got = emu.sweep_wg(d, 1, N.NIL, seg_target, n_dom, max_segs, waves=waves, cap=cap, rules=None if rules is None else (3 if rules else 0), seed=seed, compact=compact, relaxed=relaxed)
+    got = emu.sweep_wg(d, model["kind"], model["init"], seg_target, n_dom, max_segs, waves=waves, cap=cap, rules=None if rules is None else (3 if rules else 0), seed=seed, compact=compact, relaxed=relaxed, vpad=vpad)
     want = [N.SweepRel.from_buffer_copy(r.tobytes()) for r in _records(buf)]
     have = [N.SweepRel.from_buffer_copy(r.tobytes()) for r in _records(got)]
     if second_pass:      # the segments that overflowed, once more with sets of 2,048 configs and eight wavefronts (what launch_sweep does)
         again = [(i // 4, i % 4) for i, g in enumerate(have) if g.status == 2]
         assert (len(again) > 0) == expect_overflow
         expect_overflow = False
-        got = emu.sweep_wg(d, 1, N.NIL, seg_target, n_dom, max_segs, waves=8, cap=2048, rules=None if rules is None else (3 if rules else 0), seed=seed + 5, again=again, first=got)
+        got = emu.sweep_wg(d, model["kind"], model["init"], seg_target, n_dom, max_segs, waves=8, cap=2048, rules=None if rules is None else (3 if rules else 0), seed=seed + 5, again=again, first=got, vpad=vpad)
         have = [N.SweepRel.from_buffer_copy(r.tobytes()) for r in _records(got)]
     n_swept = overflowed = 0
     for i, (w, g) in enumerate(zip(want, have)):
@@ -56,7 +58,7 @@ def _compare(ops, seg_target, n_dom, waves, cap=1024, rules=None, seed=1, expect
         assert list(g.last_level) == list(w.last_level), (i, "last levels")
     assert (overflowed > 0) == expect_overflow
     if not overflowed:      # the library's own composition (host code, no device) of K6w's records = the oracle's verdict
-        ref = wgl.check_sweep(d, CAS, eager_reads=eager, twin_rule=twin, seg_target=seg_target, n_dom=n_dom, relaxed=relaxed)
+        ref = wgl.check_sweep(d, model, eager_reads=eager, twin_rule=twin, seg_target=seg_target, n_dom=n_dom, relaxed=relaxed)
         v = N.SweepVerdict()
         recs = (N.SweepRel * len(have))(*have)
         assert N.lib().tbc_sweep_compose(recs, C.c_uint32(max_segs), C.c_uint32(R), C.byref(v)) == 0
