@@ -8,6 +8,7 @@
 //              of this call's arena, its image the first copy --, then pairing by process (lgrt::pair) for inv(R) and ret(R) of every
 //              :ok read, as index + 1 (0: the read has no invocation), and the regions of this checker after the snapshot plan's.
 //              The core's two bit matrices are NOT in the arena: their size is known only when the device has counted the core.
+//   steps      the call from the plan to the filled output, over a call frame: the library's and the emulator's run this one list
 #pragma once
 #include "ledger_rt_plan.h"
 #include "ledger_snap_plan.h"
@@ -146,6 +147,63 @@ inline CyArgs with_matrix(CyArgs A, uint32_t n_core, char* matrices) {
   A.n_core = n_core; A.n_words = matrix_words(n_core);
   A.mat[0] = (uint32_t*)matrices; A.mat[1] = (uint32_t*)(matrices + matrix_bytes(n_core));
   return A;
+}
+
+// The call from a finished plan to the filled `out`, over an open frame (oneshot_plan.h, "the frame interface"): the snapshot plan's
+// image and this checker's head as two copies, the zeroed regions, the kernels that separate clean reads from the core --
+// run.prepare(A) --, the accumulators back -- the core's size decides whether the call goes on (`max_core` at most), and how large the
+// two bit matrices are, which are allocated only now --, the descriptors and the matrix -- run.describe(A) --, one squaring per round
+// -- run.round(A, round) -- with the changed flag read back after each, the rest of the kernels -- run.finish(A, final_side, rounds)
+// --, the summary back, and then one copy per array the caller asked for.  Every run of kernels is a timed section; ns_device is their
+// sum.
+template <class Frame, class Run>
+tbc_status steps(const char* fn, Frame& C, Run&& run, const tbc_ledger_rt_in* in, const Plan& P, tbc_ledger_cycles_out* out, uint32_t max_core = TBC_LEDGER_CYCLES_MAX_CORE) {
+  const lgsn::SnArena& S = P.sn.arena;
+  const CyArena& L = P.arena;
+  const std::vector<unsigned char> img = lgsn::image(&in->ledger, P.sn), head = head_image(P);
+  lgsn::SnAcc sn_acc{};
+  CyAcc acc{};
+  uint32_t changed = 0;
+  C.image(img);
+  C.image(head, L.head_at());
+  C.fill(S.val, 0, S.zero_bytes());
+  CyArgs A = args(in, P, C.base());
+  C.timed([&] { run.prepare(A); });
+  C.get(&sn_acc, S.acc, sizeof sn_acc);
+  C.get(&acc, L.acc, sizeof acc);
+  if (C.sync() != TBC_OK) return C.status;
+  tbc_ledger_cycles_summary& s = out->summary;
+  s = tbc_ledger_cycles_summary{};
+  s.read_count = P.sn.n_reads; s.n_partial = sn_acc.n_partial; s.n_core = acc.n_core; s.bad_values = sn_acc.bad_values; s.n_checked = sn_acc.n_checked;
+  s.first = s.largest = kCyNone;
+  oneshot::account(C, s);
+  if (s.bad_values) return C.fail(TBC_ERR_UNSUPPORTED, "%s: %u reads hold counters whose magnitudes add up to 2^63 or more", fn, s.bad_values);
+  if (s.n_core > max_core) return C.fail(TBC_ERR_UNSUPPORTED, "%s: %u reads are partial, skewed or contradicted by real time; the search takes %u at most", fn, s.n_core, max_core);
+  uint32_t rounds = 0, final_side = 0;
+  if (acc.n_core) {
+    char* matrices = C.more(2 * matrix_bytes(acc.n_core));
+    if (C.status != TBC_OK) return C.status;
+    A = with_matrix(A, acc.n_core, matrices);
+    for (;;) {
+      C.timed([&] {
+        if (!rounds) run.describe(A);
+        run.round(A, rounds);
+      });
+      C.get(&changed, Region{L.acc.at + offsetof(CyAcc, changed) + 4u * rounds, 4u});
+      if (C.sync() != TBC_OK) return C.status;
+      final_side = (rounds & 1u) ^ 1u;
+      rounds++;
+      if (!changed) break;
+      if (rounds == kCyMaxRounds) return C.fail(TBC_ERR_HIP, "%s: the closure did not settle in %u rounds", fn, rounds);
+    }
+  }
+  C.timed([&] { run.finish(A, final_side, rounds); });
+  C.get(&out->summary, L.summary, sizeof(tbc_ledger_cycles_summary));
+  if (C.sync() != TBC_OK) return C.status;
+  oneshot::account(C, out->summary);
+  const size_t R = P.sn.n_reads;
+  C.get(out->scc, L.scc, R * 4); C.get(out->cyc_flags, L.cyc_flags, R);
+  return C.sync();
 }
 
 }  // namespace lgcy

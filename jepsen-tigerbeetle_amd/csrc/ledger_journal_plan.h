@@ -11,6 +11,7 @@
 //              reads' micro-ops -- id, a, b, flags: 25 B.  Per transfer micro-op its owner's inv, ret and status; per lookup inv and
 //              ret; per read inv and ret; the SLICES the entries kernel's workgroups take (a lookup's entries in runs of slice_entries);
 //              the sorted accounts with their positions, `init` per counter; the arena as named regions.
+//   steps      the call from the plan to the filled output, over a call frame: the library's and the emulator's run this one list
 #pragma once
 #include "ledger_rt_plan.h"
 
@@ -230,6 +231,28 @@ inline JnArgs args(const tbc_ledger_rt_in* rin, const Plan& P, char* base) {
   A.xfer_present = u32(L.xfer_present); A.xfer_early = u32(L.xfer_early); A.xfer_lost = u32(L.xfer_lost); A.xfer_vanished = u32(L.xfer_vanished);
   A.xfer_flags = (uint8_t*)at(L.xfer_flags);
   return A;
+}
+
+// The call from a finished plan to the filled `out`, over an open frame (oneshot_plan.h, "the frame interface"): the head and the three
+// groups of micro-op columns as one image in one copy, the zeroed regions, the kernels -- run.sequence(A) --, the summary back -- an
+// amount out of range, which only the device has looked at, ends the call there -- and then one copy per array the caller asked for.
+template <class Frame, class Run>
+tbc_status steps(const char* fn, Frame& C, Run&& run, const tbc_ledger_rt_in* in, const Plan& P, tbc_ledger_journal_out* out) {
+  const JnArena& L = P.arena;
+  const std::vector<unsigned char> img = image(in, P);
+  C.image(img);
+  C.fill(L.slots, 0, L.zero_bytes());
+  C.timed([&] { run.sequence(args(in, P, C.base())); });
+  C.get(&out->summary, L.summary, sizeof(tbc_ledger_journal_summary));
+  if (C.sync() != TBC_OK) return C.status;
+  oneshot::account(C, out->summary);
+  if (out->summary.bad_amounts) return C.fail(TBC_ERR_UNSUPPORTED, "%s: %u amounts of journalled transfers are outside [0, 2^31)", fn, out->summary.bad_amounts);
+  const size_t M = (size_t)P.xf.n_mops, R = P.n_reads;
+  C.get(out->entry_bits, L.entry_bits); C.get(out->lk_counts, L.lk_counts); C.get(out->lk_present, L.lk_present); C.get(out->lk_vector, L.lk_vector);
+  C.get(out->rd_bits, L.rd_bits, R); C.get(out->rd_first, L.rd_first, R * 8);
+  C.get(out->xfer_present, L.xfer_present, M * 4); C.get(out->xfer_early, L.xfer_early, M * 4); C.get(out->xfer_lost, L.xfer_lost, M * 4);
+  C.get(out->xfer_vanished, L.xfer_vanished, M * 4); C.get(out->xfer_flags, L.xfer_flags, M);
+  return C.sync();
 }
 
 }  // namespace lgjn

@@ -8,6 +8,7 @@
 //              that) --, the RUNS the SI kernel's workgroups take (consecutive reads of at most kLgRunMops micro-ops and kLgRunReads
 //              reads together; a longer read is a run of its own), the distinct invoked transfer ids, the sorted accounts, and the
 //              arena as named regions with 256 B starts.  The lookups' micro-ops -- the big part -- are never looked at here.
+//   steps      the call from the plan to the filled output, over a call frame: the library's and the emulator's run this one list
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -225,6 +226,27 @@ inline LgArgs args(const tbc_ledger_in* in, const Plan& P, char* base) {
   A.fr_lo = (const unsigned long long*)at(L.fr_lo); A.fr_cum = (const unsigned long long*)at(L.fr_cum); A.n_final_reads = P.n_final_reads;
   A.fr_unlike = (uint32_t*)at(L.fr_unlike); A.fl_unlike = (uint32_t*)at(L.fl_unlike);
   return A;
+}
+
+// The call from a finished plan to the filled `out`, over an open frame (oneshot_plan.h, "the frame interface"): the head as one image
+// and the caller's micro-op columns straight to their regions, the zeroed regions, the kernels -- run.sequence(A, fr_mops, fl_mops) --,
+// and the results back in one copy per array the caller asked for.
+template <class Frame, class Run>
+tbc_status steps(Frame& C, Run&& run, const tbc_ledger_in* in, const Plan& P, tbc_ledger_out* out) {
+  const LgArena& L = P.arena;
+  const std::vector<unsigned char> img = head_image(P);
+  C.image(img);
+  C.put(L.mop_id, in->mop_id); C.put(L.mop_a, in->mop_a); C.put(L.mop_b, in->mop_b); C.put(L.mop_c, in->mop_c); C.put(L.mop_flags, in->mop_flags);
+  C.fill(L.slots, 0, L.zero_bytes());
+  C.timed([&] { run.sequence(args(in, P, C.base()), P.fr_cum.back(), P.fl_cum.back()); });
+  const size_t R = P.n_reads, FR = P.n_final_reads, FL = P.n_final_lookups;
+  C.get(out->read_error, L.read_error, R); C.get(out->read_total, L.read_total, R * 8); C.get(out->read_badness, L.read_badness, R * 8);
+  C.get(out->lookup_missing, L.missing, FL * 4);
+  C.get(out->final_read_unlike, L.fr_unlike, FR); C.get(out->final_lookup_unlike, L.fl_unlike, FL);
+  C.get(&out->summary, L.summary, sizeof(tbc_ledger_summary));
+  if (C.sync() != TBC_OK) return C.status;
+  oneshot::account(C, out->summary);
+  return TBC_OK;
 }
 
 }  // namespace lg

@@ -11,6 +11,7 @@
 //                reads      the :ok reads, position = the read's own index (ret); beside it the invocation's index (inv)
 //              A micro-op gives two ENTRIES, credits then debits; a stream of M micro-ops is cut into chunks of whole wavefronts'
 //              worth of entries.  Then the sorted accounts with `init` permuted to match, and the arena as named regions.
+//   steps      the call from the plan to the filled output, over a call frame: the library's and the emulator's run this one list
 #pragma once
 #include <unordered_map>
 #include "ledger_plan.h"
@@ -250,6 +251,27 @@ inline RtArgs args(const tbc_ledger_rt_in* in, const Plan& P, char* base) {
   A.rt_bits = (uint32_t*)at(L.rt_bits); A.rt_miss = (unsigned long long*)at(L.rt_miss);
   A.mop_lo = (long long*)at(L.mop_lo); A.mop_hi = (long long*)at(L.mop_hi); A.mop_floor = (long long*)at(L.mop_floor);
   return A;
+}
+
+// The call from a finished plan to the filled `out`, over an open frame (oneshot_plan.h, "the frame interface"): the head and the
+// micro-op columns of the ops the kernels look at as one image in one copy, the zeroed regions, the kernels -- run.sequence(A) --, the
+// summary back -- an amount out of range, which only the device has looked at, ends the call there -- and then one copy per array the
+// caller asked for.
+template <class Frame, class Run>
+tbc_status steps(const char* fn, Frame& C, Run&& run, const tbc_ledger_rt_in* in, const Plan& P, tbc_ledger_rt_out* out) {
+  const RtArena& L = P.arena;
+  const std::vector<unsigned char> img = image(in, P);
+  C.image(img);
+  C.fill(L.carry_cnt[0], 0, L.zero_bytes());
+  C.timed([&] { run.sequence(args(in, P, C.base())); });
+  C.get(&out->summary, L.summary, sizeof(tbc_ledger_rt_summary));
+  if (C.sync() != TBC_OK) return C.status;
+  oneshot::account(C, out->summary);
+  if (out->summary.bad_amounts) return C.fail(TBC_ERR_UNSUPPORTED, "%s: %u transfer amounts are outside [0, 2^31)", fn, out->summary.bad_amounts);
+  const size_t R = P.n_reads, Mr = (size_t)P.rows[kReads].mops();
+  C.get(out->rt_bits, L.rt_bits, R); C.get(out->rt_miss, L.rt_miss, R * 24);
+  C.get(out->mop_lo, L.mop_lo, Mr * 16); C.get(out->mop_hi, L.mop_hi, Mr * 16); C.get(out->mop_floor, L.mop_floor, Mr * 16);
+  return C.sync();
 }
 
 }  // namespace lgrt

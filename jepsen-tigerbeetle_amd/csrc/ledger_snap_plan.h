@@ -9,6 +9,7 @@
 //              read's only id, a, b and the flags --, the sorted accounts with each one's position in the caller's `accounts` (a counter
 //              is 2 x that position + field), the chunks of the sort and of the scan, and the arena as named regions.
 //              R reads x C = 2 x n_accounts counters are laid out densely: R x C < 2^31, or the call is refused.
+//   steps      the call from the plan to the filled output, over a call frame: the library's and the emulator's run this one list
 #pragma once
 #include "ledger_plan.h"
 
@@ -170,6 +171,34 @@ inline SnArgs args(const tbc_ledger_in* in, const Plan& P, char* base) {
   A.skew_count = (uint32_t*)at(L.skew_count); A.skew_first = (uint32_t*)at(L.skew_first); A.skew_key = (uint32_t*)at(L.skew_key);
   A.snap_flags = (uint8_t*)at(L.snap_flags);
   return A;
+}
+
+// The call from a finished plan to the filled `out`, over an open frame (oneshot_plan.h, "the frame interface"): the head and the reads'
+// micro-op columns as one image in one copy, the zeroed and the all-ones regions, the filter's kernels -- run.filter(A) --, the
+// accumulators back -- the number of candidates decides whether a pair kernel is launched at all --, the rest of the kernels --
+// run.rest(A, n_candidates) --, the summary back -- a read out of range, which only the device has looked at, ends the call there --
+// and then one copy per array the caller asked for.  The two runs of kernels are timed sections of their own; ns_device is their sum.
+template <class Frame, class Run>
+tbc_status steps(const char* fn, Frame& C, Run&& run, const tbc_ledger_in* in, const Plan& P, tbc_ledger_snap_out* out) {
+  const SnArena& L = P.arena;
+  const std::vector<unsigned char> img = image(in, P);
+  SnAcc acc{};
+  C.image(img);
+  C.fill(L.val, 0, L.zero_bytes());
+  C.fill(L.skew_first, 0xFF, L.ones_bytes());
+  const SnArgs A = args(in, P, C.base());
+  C.timed([&] { run.filter(A); });
+  C.get(&acc, L.acc, sizeof acc);
+  if (C.sync() != TBC_OK) return C.status;
+  C.timed([&] { run.rest(A, acc.bad_values ? 0u : acc.n_candidates); });    // (bad values: only the summary is wanted)
+  C.get(&out->summary, L.summary, sizeof(tbc_ledger_snap_summary));
+  if (C.sync() != TBC_OK) return C.status;
+  oneshot::account(C, out->summary);
+  if (out->summary.bad_values) return C.fail(TBC_ERR_UNSUPPORTED, "%s: %u reads hold counters whose magnitudes add up to 2^63 or more", fn, out->summary.bad_values);
+  const size_t R = P.n_reads;
+  C.get(out->skew_count, L.skew_count, R * 4); C.get(out->skew_first, L.skew_first, R * 4);
+  C.get(out->skew_key, L.skew_key, R * 8); C.get(out->snap_flags, L.snap_flags, R);
+  return C.sync();
 }
 
 }  // namespace lgsn

@@ -1,7 +1,10 @@
 // oneshot_call.h -- the host call frame of the one-shot entry points that take op columns (tbc_ledger_check, tbc_ledger_realtime,
-// tbc_ledger_snapshots, tbc_ledger_cycles, tbc_perf_series): the HIP error macro, the extern "C" wrapper, and OneShotCall -- what one call makes on the
-// device (ONE arena laid out by the plan, a stream and two events of its own) and the steps every such call takes, released on every
-// path out.  One-shot and re-entrant: nothing outlives the call.
+// tbc_ledger_snapshots, tbc_ledger_journal, tbc_ledger_cycles, tbc_perf_series): the HIP error macro, the extern "C" wrapper, and
+// OneShotCall -- what one call makes on the device (ONE arena laid out by the plan, a stream and two events of its own; for the cycle
+// search a second allocation) and the steps every such call takes, released on every path out.  One-shot and re-entrant: nothing
+// outlives the call.  Each checker's LIST of steps is the `steps` template of its plan header, written against THE FRAME INTERFACE
+// (oneshot_plan.h) that this struct and the emulator's arena of tests/emu/oneshot_emu.h both meet; a host unit validates, plans, opens
+// the frame and calls it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -24,15 +27,15 @@
 namespace tbc {
 
 // One call's frame.  The FIRST step that fails sets `status` (and the error text, through TBC_ONESHOT_TRY); every step after it does
-// nothing and returns that status, so a host unit reads as the list of its steps and looks at the status where it must: after `open`,
-// before it reads what a `sync` brought back.  The copies read pageable memory of the caller's and of the plan's: what they read from
-// lives until the next `sync`, and is declared before the call, whose destructor synchronises.
+// nothing and returns that status, so a step list reads as a list and looks at the status where it must: before it reads what a `sync`
+// brought back.  The copies read and write pageable memory of the caller's, of the plan's and of the step list's: it lives until the
+// next `sync`, which waits for the stream on a failed call too -- a step list returns only after one.
 struct OneShotCall {
   using Region = oneshot::Region;
   tbc_status status = TBC_OK;
   uint64_t bytes_in = 0;                                    // what `put` and `image` have copied in
   int device_before = -1;                                   // the calling thread's current device, put back on the way out
-  void* arena = nullptr;
+  void *arena = nullptr, *extra = nullptr;                  // (`extra`: what `more` made)
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool section_open = false;                                // ev0 .. ev1 are recorded and not yet added to ms
@@ -41,6 +44,7 @@ struct OneShotCall {
   // released in this order whichever way the call ends
   ~OneShotCall() {
     if (stream) (void)hipStreamSynchronize(stream);       // (a call that failed half way may have left a copy or a kernel in flight)
+    if (extra) (void)hipFree(extra);
     if (arena) (void)hipFree(arena);
     for (hipEvent_t e : {ev0, ev1}) if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
@@ -65,12 +69,22 @@ struct OneShotCall {
       return TBC_OK;
     });
   }
+  // a second allocation that lives as long as the frame (one a call; null once the call has failed)
+  char* more(size_t bytes) {
+    step([&]() -> tbc_status { TBC_ONESHOT_TRY(hipMalloc(&extra, bytes)); return TBC_OK; });
+    return static_cast<char*>(extra);
+  }
+  // the call ends here, with `st` and this message
+  template <class... A>
+  tbc_status fail(tbc_status st, const char* fmt, const A&... a) {
+    return step([&]() -> tbc_status { set_error(fmt, a...); return st; });
+  }
   char* base() const { return static_cast<char*>(arena); }
   char* at(const Region& r) const { return base() + r.at; }
 
-  // `src` to region `r`; the head's image to the arena's start
+  // `src` to region `r`; an image of the plan's to the arena's start, or `at` bytes past it
   tbc_status put(const Region& r, const void* src) { return copy_in(at(r), src, r.bytes); }
-  tbc_status image(const std::vector<unsigned char>& img) { return copy_in(base(), img.data(), img.size()); }
+  tbc_status image(const std::vector<unsigned char>& img, size_t at = 0) { return copy_in(base() + at, img.data(), img.size()); }
   // `bytes` from the start of region `first` on (several regions in a row) set to 0x00 or 0xFF
   tbc_status fill(const Region& first, int byte, size_t bytes) {
     return step([&]() -> tbc_status {
@@ -98,8 +112,9 @@ struct OneShotCall {
     });
   }
   tbc_status get(void* dst, const Region& r) { return get(dst, r, r.bytes); }
-  // everything so far is done: the copies have arrived, a timed section is measured
+  // everything so far is done: the copies have arrived, a timed section is measured (a failed call: whatever is still in flight has landed)
   tbc_status sync() {
+    if (status != TBC_OK && stream) (void)hipStreamSynchronize(stream);
     return step([&]() -> tbc_status {
       TBC_ONESHOT_TRY(hipStreamSynchronize(stream));
       if (section_open) {

@@ -7,6 +7,7 @@
 //              t_max over all ops, nb_all and n_plot, the cell numbering -- quantile cell (f, bucket) = f * nb_all + bucket, class
 //              (f, outcome) = f * 3 + outcome - 1, class cell = class * nb_all + bucket --, the chunks of the open scan, and the
 //              arena as named regions with 256 B starts.
+//   steps      the call from the plan to the filled output, over a call frame: the library's and the emulator's run this one list
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -171,6 +172,25 @@ inline PfArgs args(const Plan& P, char* base) {
   A.rate_count = (uint32_t*)at(L.rate_count); A.carry = (uint32_t*)at(L.carry); A.open_word = (unsigned long long*)at(L.open_word);
   A.open_last = (int32_t*)at(L.open_last); A.open_fill = (int32_t*)at(L.open_fill);
   return A;
+}
+
+// The call from a finished plan to the filled `out`, over an open frame (oneshot_plan.h, "the frame interface"): the zeroed head, the
+// plan's partner column and the caller's columns straight to their regions, the kernels -- run.sequence(A) --, and the results back in
+// one copy per array the caller asked for.
+template <class Frame, class Run>
+tbc_status steps(Frame& C, Run&& run, const tbc_perf_in* in, const Plan& P, tbc_perf_out* out) {
+  const PfArena& L = P.arena;
+  C.fill(L.acc, 0, L.zero_bytes());
+  C.put(L.partner, P.partner.data());
+  C.put(L.time, in->time); C.put(L.process, in->process); C.put(L.type, in->type); C.put(L.f, in->f);
+  C.timed([&] { run.sequence(args(P, C.base())); });
+  C.get(out->op_latency, L.op_latency); C.get(out->op_outcome, L.op_outcome); C.get(out->op_open_after, L.op_open_after);
+  C.get(out->q_count, L.q_count); C.get(out->q_value, L.q_value); C.get(out->rate_count, L.rate_count);
+  C.get(out->open_last, L.open_last); C.get(out->open_fill, L.open_fill);
+  C.get(&out->summary, L.summary);
+  if (C.sync() != TBC_OK) return C.status;
+  oneshot::account(C, out->summary);
+  return TBC_OK;
 }
 
 }  // namespace pf

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  emu_ledger_journal.cpp: tbc_ledger_journal on the CPU -- the validation and the host plan of
-// csrc/ledger_journal_plan.h, the arena laid out and filled in the steps of csrc/ledger_journal_host.hip (the one image of the head and
-// the gathered columns, the zeroed regions), and the kernels of csrc/ledger_journal_kernels.h (the very file hipcc compiles into
+// csrc/ledger_journal_plan.h, the steps of the call as lgjn::steps of that header states them -- the list csrc/ledger_journal_host.hip
+// runs -- over the emulator's call frame, and the kernels of csrc/ledger_journal_kernels.h (the very file hipcc compiles into
 // libtbcheck.so) under the wavefront / workgroup emulator, launched by lgjn::sequence of that file -- the library's own statement -- over
 // the emulator's launcher (oneshot_emu.h).  Every grid that strides is capped at `grid_cap` workgroups, so that the strides run;
 // `slice_entries` and `chunk` are the plan's: a few entries a slice cut a lookup over several workgroups, whose rows of the bitmap are
@@ -24,23 +24,11 @@ extern "C" int emu_journal_check(const tbc_ledger_rt_in* in, tbc_ledger_journal_
   if (!lgjn::validate("emu_journal_check", in, g_err)) return TBC_ERR_INVALID_ARG;
   lgjn::Plan P;
   if (!lgjn::plan("emu_journal_check", in, P, g_err, slice_entries ? slice_entries : lgjn::kJnSliceEntries, chunk ? chunk : lgjn::kJnChunk, chunk ? kEmuTile : lgjn::kJnTile)) return TBC_ERR_INVALID_ARG;
-  const lgjn::JnArena& L = P.arena;
-  emu::Arena C(L.bytes);
-  const std::vector<unsigned char> img = lgjn::image(in, P);
-  C.image(img);
-  C.fill(L.slots, 0, L.zero_bytes());
-  const lgjn::JnArgs A = lgjn::args(in, P, C.base());
-  emu::Launcher go(grid_cap, seed);
-  lgjn::sequence<kEmuWindowWords>(go, A);
-  C.get(&out->summary, L.summary, sizeof(tbc_ledger_journal_summary));
-  out->summary.ns_device = 0; out->summary.bytes_in = img.size();
-  if (out->summary.bad_amounts) { g_err = "emu_journal_check: amounts of journalled transfers are outside [0, 2^31)"; return TBC_ERR_UNSUPPORTED; }
-  const size_t M = (size_t)P.xf.n_mops, R = P.n_reads;
-  C.get(out->entry_bits, L.entry_bits); C.get(out->lk_counts, L.lk_counts); C.get(out->lk_present, L.lk_present); C.get(out->lk_vector, L.lk_vector);
-  C.get(out->rd_bits, L.rd_bits, R); C.get(out->rd_first, L.rd_first, R * 8);
-  C.get(out->xfer_present, L.xfer_present, M * 4); C.get(out->xfer_early, L.xfer_early, M * 4); C.get(out->xfer_lost, L.xfer_lost, M * 4);
-  C.get(out->xfer_vanished, L.xfer_vanished, M * 4); C.get(out->xfer_flags, L.xfer_flags, M);
-  return 0;
+  struct Run { emu::Launcher go; void sequence(const lgjn::JnArgs& A) { lgjn::sequence<kEmuWindowWords>(go, A); } };
+  emu::Arena C(g_err);
+  C.open(in->ledger.device, P.arena.bytes);
+  lgjn::steps("emu_journal_check", C, Run{emu::Launcher(grid_cap, seed)}, in, P, out);
+  return C.close();
 }
 
 extern "C" const char* emu_journal_error() { return g_err.c_str(); }

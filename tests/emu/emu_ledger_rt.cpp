@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  emu_ledger_rt.cpp: tbc_ledger_realtime on the CPU -- the validation and the host plan of
-// csrc/ledger_rt_plan.h, the arena laid out and filled in the steps of csrc/ledger_rt_host.hip (the one image of the head and the
-// gathered columns, the zeroed regions), and the kernels of csrc/ledger_rt_kernels.h (the very file hipcc compiles into libtbcheck.so)
+// csrc/ledger_rt_plan.h, the steps of the call as lgrt::steps of that header states them -- the list csrc/ledger_rt_host.hip runs --
+// over the emulator's call frame, and the kernels of csrc/ledger_rt_kernels.h (the very file hipcc compiles into libtbcheck.so)
 // under the wavefront / workgroup emulator, launched by lgrt::sequence of that file -- the library's own statement -- over the
 // emulator's launcher (oneshot_emu.h).  Every grid that strides is capped at `grid_cap` workgroups, so that the strides run; at the
 // sizes of the tests a chunk is one wavefront's 64 entries unless `chunks_cap` says otherwise.  Built as a shared object by
@@ -20,14 +20,13 @@ extern "C" int emu_rt_check(const tbc_ledger_rt_in* in, tbc_ledger_rt_out* out, 
   if (!lgrt::validate("emu_rt_check", in, g_err)) return TBC_ERR_INVALID_ARG;
   lgrt::Plan P;
   if (!lgrt::plan("emu_rt_check", in, P, g_err, chunks_cap ? chunks_cap : lgrt::kRtChunksMax)) return TBC_ERR_INVALID_ARG;
-  const lgrt::RtArena& L = P.arena;
-  emu::Arena C(L.bytes);
-  C.image(lgrt::image(in, P));
-  C.fill(L.carry_cnt[0], 0, L.zero_bytes());
-  const lgrt::RtArgs A = lgrt::args(in, P, C.base());
-  emu::Launcher go(grid_cap, seed);
-  lgrt::sequence(go, A);
+  struct Run { emu::Launcher go; void sequence(const lgrt::RtArgs& A) { lgrt::sequence(go, A); } };
+  emu::Arena C(g_err);
+  C.open(in->ledger.device, P.arena.bytes);
+  lgrt::steps("emu_rt_check", C, Run{emu::Launcher(grid_cap, seed)}, in, P, out);
+  if (C.close() != TBC_OK && C.status != TBC_ERR_UNSUPPORTED) return C.status;
   // every list is full: each stream's lists hold as many entries as the numbering gave a class, in ascending position order
+  const lgrt::RtArgs A = lgrt::args(in, P, C.base());
   for (int k = 0; k < lgrt::kStreams; k++) {
     const lgrt::RtStream& S = A.s[k];
     uint64_t with_class = 0;
@@ -37,13 +36,7 @@ extern "C" int emu_rt_check(const tbc_ledger_rt_in* in, tbc_ledger_rt_out* out, 
       for (uint32_t i = S.off[c] + 1u; i < S.off[c + 1u]; i++)
         if (S.list_pos[i] < S.list_pos[i - 1u]) { g_err = "a list is not in position order"; return -1; }
   }
-  C.get(&out->summary, L.summary, sizeof(tbc_ledger_rt_summary));
-  out->summary.ns_device = 0; out->summary.bytes_in = 0;
-  if (out->summary.bad_amounts) { g_err = "emu_rt_check: transfer amounts outside [0, 2^31)"; return TBC_ERR_UNSUPPORTED; }
-  const size_t R = P.n_reads, Mr = (size_t)P.rows[lgrt::kReads].mops();
-  C.get(out->rt_bits, L.rt_bits, R); C.get(out->rt_miss, L.rt_miss, R * 24);
-  C.get(out->mop_lo, L.mop_lo, Mr * 16); C.get(out->mop_hi, L.mop_hi, Mr * 16); C.get(out->mop_floor, L.mop_floor, Mr * 16);
-  return 0;
+  return C.status;
 }
 
 extern "C" const char* emu_rt_error() { return g_err.c_str(); }

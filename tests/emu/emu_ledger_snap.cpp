@@ -1,9 +1,9 @@
 // TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  emu_ledger_snap.cpp: tbc_ledger_snapshots on the CPU -- the validation and the host plan of
-// csrc/ledger_snap_plan.h, the arena laid out and filled in the steps of csrc/ledger_snap_host.hip (the one image of the head and the
-// gathered columns, the zeroed and the all-ones regions), and the kernels of csrc/ledger_snap_kernels.h (the very file hipcc compiles
-// into libtbcheck.so) under the wavefront / workgroup emulator, launched by lgsn::filter_sequence and lgsn::rest_sequence of that file
-// -- the library's own statement -- over the emulator's launcher (oneshot_emu.h), the candidates' number read in between as the host
-// does.  Every grid that strides is capped at `grid_cap` workgroups, so that the strides run (the pair kernel: as many slices of tiles
+// csrc/ledger_snap_plan.h, the steps of the call as lgsn::steps of that header states them -- the list csrc/ledger_snap_host.hip runs,
+// the candidates' number read between the two runs of kernels -- over the emulator's call frame, and the kernels of
+// csrc/ledger_snap_kernels.h (the very file hipcc compiles into libtbcheck.so) under the wavefront / workgroup emulator, launched by
+// lgsn::filter_sequence and lgsn::rest_sequence of that file -- the library's own statement -- over the emulator's launcher
+// (oneshot_emu.h).  Every grid that strides is capped at `grid_cap` workgroups, so that the strides run (the pair kernel: as many slices of tiles
 // at most); `sort_chunks_cap` and `scan_rows` are the plan's: a few chunks make a sort chunk several wavefronts' worth, a few rows a
 // chunk give the scan's carry several steps.  Built as a shared object by tests/test_ledger_snapshots_emu.py, which compares what comes
 // back with snapshots_numpy of jepsen/ledger.py.
@@ -24,16 +24,18 @@ extern "C" int emu_snap_check(const tbc_ledger_in* in, tbc_ledger_snap_out* out,
   if (!lgsn::validate("emu_snap_check", in, g_err)) return TBC_ERR_INVALID_ARG;
   lgsn::Plan P;
   if (!lgsn::plan("emu_snap_check", in, P, g_err, sort_chunks_cap ? sort_chunks_cap : lgsn::kSnSortChunksMax, scan_rows ? scan_rows : lgsn::kSnScanRows)) return TBC_ERR_INVALID_ARG;
-  const lgsn::SnArena& L = P.arena;
-  emu::Arena C(L.bytes);
-  const std::vector<unsigned char> img = lgsn::image(in, P);
-  C.image(img);
-  C.fill(L.val, 0, L.zero_bytes());
-  C.fill(L.skew_first, 0xFF, L.ones_bytes());
-  const lgsn::SnArgs A = lgsn::args(in, P, C.base());
-  emu::Launcher go(grid_cap, seed);
-  lgsn::filter_sequence(go, A);
+  struct Run {
+    emu::Launcher go;
+    void filter(const lgsn::SnArgs& A) { lgsn::filter_sequence(go, A); }
+    void rest(const lgsn::SnArgs& A, uint32_t n_candidates) { lgsn::rest_sequence(go, A, n_candidates); }
+  } run{emu::Launcher(grid_cap, seed)};
+  emu::Arena C(g_err);
+  C.open(in->device, P.arena.bytes);
+  lgsn::steps("emu_snap_check", C, run, in, P, out);
+  if (C.close() != TBC_OK && C.status != TBC_ERR_UNSUPPORTED) return C.status;
+  for (const emu::Recorder::Launch& l : run.go.ran.launches) g_pair_launches += l.kernel == emu::Recorder::of(sn_pair_kernel);
   // the order is sorted by (key, read number), and it is a permutation (nothing after the sort writes the order)
+  const lgsn::SnArgs A = lgsn::args(in, P, C.base());
   if (A.n_reads && A.n_class) {
     std::vector<uint8_t> seen(A.n_reads, 0);
     for (uint32_t p = 0; p < A.n_reads; p++) {
@@ -43,14 +45,7 @@ extern "C" int emu_snap_check(const tbc_ledger_in* in, tbc_ledger_snap_out* out,
       if (p && (A.sort_key[0][p - 1] > A.sort_key[0][p] || (A.sort_key[0][p - 1] == A.sort_key[0][p] && A.sort_perm[0][p - 1] > r))) { g_err = "the reads are not in the order of (sum, read number)"; return -1; }
     }
   }
-  lgsn::rest_sequence(go, A, A.acc->bad_values ? 0u : A.acc->n_candidates);
-  for (const emu::Recorder::Launch& l : go.ran.launches) g_pair_launches += l.kernel == emu::Recorder::of(sn_pair_kernel);
-  C.get(&out->summary, L.summary, sizeof(tbc_ledger_snap_summary));
-  out->summary.ns_device = 0; out->summary.bytes_in = img.size();
-  if (out->summary.bad_values) { g_err = "emu_snap_check: reads hold counters whose magnitudes add up to 2^63 or more"; return TBC_ERR_UNSUPPORTED; }
-  const size_t R = P.n_reads;
-  C.get(out->skew_count, L.skew_count, R * 4); C.get(out->skew_first, L.skew_first, R * 4); C.get(out->skew_key, L.skew_key, R * 8); C.get(out->snap_flags, L.snap_flags, R);
-  return 0;
+  return C.status;
 }
 
 extern "C" const char* emu_snap_error() { return g_err.c_str(); }

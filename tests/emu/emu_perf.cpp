@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  emu_perf.cpp: tbc_perf_series on the CPU -- the validation and the host plan of
-// csrc/perf_plan.h, the arena laid out and filled in the steps of csrc/perf_host.hip (the zeroed head, the partner column, the caller's
-// columns), and the kernels of csrc/perf_kernels.h (the very file hipcc compiles into libtbcheck.so) under the wavefront / workgroup
-// emulator, launched by pf::sequence of that file -- the library's own statement -- over the emulator's launcher (oneshot_emu.h).  The
+// csrc/perf_plan.h, the steps of the call as pf::steps of that header states them -- the list csrc/perf_host.hip runs -- over the
+// emulator's call frame, and the kernels of csrc/perf_kernels.h (the very file hipcc compiles into libtbcheck.so) under the wavefront /
+// workgroup emulator, launched by pf::sequence of that file -- the library's own statement -- over the emulator's launcher (oneshot_emu.h).  The
 // select's LDS tile is PF_SELECT_TILE = 32 latencies here (the library's is TBC_PERF_SELECT_TILE), so that a cell of a few dozen takes
 // the radix select; every grid that strides is capped at `grid_cap` workgroups, so that the strides run.
 // Built as a shared object by tests/test_perf_emu.py, which compares what comes back with the host statement of jepsen/perf.py.
@@ -37,20 +37,15 @@ extern "C" int emu_pf_series(const tbc_perf_in* in, tbc_perf_out* out, uint32_t 
   pf::Plan P;
   st = pf::plan("emu_pf_series", in, P, g_err);
   if (st != TBC_OK) return st;
-  const pf::PfArena& L = P.arena;
-  emu::Arena C(L.bytes);
-  C.fill(L.acc, 0, L.zero_bytes());
-  C.put(L.partner, P.partner.data()); C.put(L.time, in->time); C.put(L.process, in->process); C.put(L.type, in->type); C.put(L.f, in->f);
-  const pf::PfArgs A = pf::args(P, C.base());
-  emu::Launcher go(grid_cap, seed);
-  pf::sequence(go, A);
+  struct Run { emu::Launcher go; void sequence(const pf::PfArgs& A) { pf::sequence(go, A); } };
+  emu::Arena C(g_err);
+  C.open(in->device, P.arena.bytes);
+  pf::steps(C, Run{emu::Launcher(grid_cap, seed)}, in, P, out);
+  if (C.close() != TBC_OK) return C.status;
   // every cell's cursor has come to the end of the cell
+  const pf::PfArgs A = pf::args(P, C.base());
   for (uint32_t c = 0; c < A.n_cells; c++)
     if (A.q_cur[c] != A.q_off[c] + A.q_count[c]) { g_err = "a cell's cursor is not at the cell's end"; return -1; }
-  C.get(out->op_latency, L.op_latency); C.get(out->op_outcome, L.op_outcome); C.get(out->op_open_after, L.op_open_after);
-  C.get(out->q_count, L.q_count); C.get(out->q_value, L.q_value); C.get(out->rate_count, L.rate_count);
-  C.get(out->open_last, L.open_last); C.get(out->open_fill, L.open_fill); C.get(&out->summary, L.summary);
-  out->summary.ns_device = 0; out->summary.bytes_in = 0;
   return 0;
 }
 

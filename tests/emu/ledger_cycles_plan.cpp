@@ -210,7 +210,8 @@ int main() {
     std::string err;
     lgcy::Plan P;
     CHECK(lgcy::validate("t", &in, err) && lgcy::plan("t", &in, P, err));
-    emu::Arena C(P.arena.bytes);
+    emu::Arena C(err);
+    C.open(0, P.arena.bytes);
     const lgcy::CyArgs A = lgcy::args(&in, P, C.base());
     emu::Recorder rec, snap;
     lgsn::filter_sequence(snap, A.sn);

@@ -6,7 +6,9 @@
 // walk of the ops, the runs, the transfer ids, the arena's regions; then it breaks each rule of tbc_ledger_in in turn and looks at
 // the message.  The columns are exactly as long as the struct says, so a read past an end is the sanitizer's to see.  And because it
 // includes the emulator program of the kernels (emu_ledger.cpp), it holds lg::sequence -- the launches the library makes -- to the list
-// of (kernel, grid, threads) written out below by hand, under the device's caps, on the edge shapes.
+// of (kernel, grid, threads) written out below by hand, under the device's caps, on the edge shapes; and it runs lg::steps -- the
+// steps the library takes -- over the emulator's call frame into output arrays of exactly the size the header states, and sees that
+// the frame's own checks fire: a get longer than its region, a fill past the arena, a byte written behind it.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -130,6 +132,30 @@ void launches() {
       {{si, 16384, 256}, {build, 274, 256}, {lookup, 4096, 256}, {rows, 8192, 256}, {rows, 8192, 256}, {finish, 79, 256}, {summary, 1, 64}}));
 }
 
+// ---- the call frame: lg::steps into exact arrays, then each of the frame's checks broken in turn
+void frame(const Ledger& L) {
+  const tbc_ledger_in in = L.in();
+  uint64_t n[6];
+  CHECK(emu_lg_shape(&in, n) == 0);
+  std::vector<uint8_t> read_error(n[0]), fr_unlike(n[2]), fl_unlike(n[3]);
+  std::vector<int64_t> read_total(n[0]), read_badness(n[0]);
+  std::vector<uint32_t> missing(n[3]);
+  tbc_ledger_out out{};
+  out.read_error = read_error.data(); out.read_total = read_total.data(); out.read_badness = read_badness.data();
+  out.lookup_missing = missing.data(); out.final_read_unlike = fr_unlike.data(); out.final_lookup_unlike = fl_unlike.data();
+  CHECK(emu_lg_check(&in, &out, 2, 1) == 0);
+  CHECK(out.summary.ns_device == 0 && out.summary.bytes_in >= 33 * in.mop_off[in.n_ops]);
+  std::string err;
+  const oneshot::Region r{256, 64};
+  unsigned char buf[128];
+  { emu::Arena C(err); C.open(0, 1024); CHECK(C.get(buf, r, 64) == TBC_OK && C.get(nullptr, r, 64) == TBC_OK && C.close() == TBC_OK && err.empty()); }
+  { emu::Arena C(err); C.open(0, 1024); CHECK(C.get(buf, r, 65) == TBC_ERR_HIP && err.find("a get of 65 bytes") != std::string::npos && C.put(r, buf) == TBC_ERR_HIP && C.close() == TBC_ERR_HIP); }
+  { emu::Arena C(err); C.open(0, 1024); CHECK(C.fill(r, 0, 768) == TBC_OK && C.fill(r, 0, 769) == TBC_ERR_HIP && err.find("a fill of 769 bytes") != std::string::npos && (unsigned char)C.base()[1024] == 0xA5); }
+  { emu::Arena C(err); C.open(0, 1024); CHECK(C.put(oneshot::Region{1024, 1}, buf) == TBC_ERR_HIP && err.find("a put of 1 bytes at 1024") != std::string::npos && C.bytes_in == 0); }
+  { emu::Arena C(err); C.open(0, 1024); C.base()[1024 + 7] = 0; CHECK(C.status == TBC_OK && C.close() == TBC_ERR_HIP && err.find("byte 7 behind the arena") != std::string::npos); }
+  { emu::Arena C(err); C.open(0, 1024); C.more(40)[40] = 0; CHECK(C.close() == TBC_ERR_HIP && err.find("byte 0 behind the second allocation") != std::string::npos); }
+}
+
 void refuse(tbc_ledger_in in, const char* needle) {
   std::string err;
   CHECK(!lg::validate("tbc_ledger_check", &in, err));
@@ -150,6 +176,8 @@ int main() {
   L.op(TBC_LEDGER_T_OK, TBC_LEDGER_K_READ, TBC_LEDGER_F_FINAL, {15, 10, 5});
   L.op(TBC_LEDGER_T_OK, TBC_LEDGER_K_LOOKUP, TBC_LEDGER_F_FINAL, {100, 101, 101});
   look(L);
+  frame(L);
+  rng_state = 9; frame(make(300, 8, 257));
   { tbc_ledger_in s = L.in(); s.mop_off = nullptr; refuse(s, "null argument"); }
   { tbc_ledger_in s = L.in(); s.kind = nullptr; refuse(s, "null argument"); }
   { tbc_ledger_in s = L.in(); s.mop_b = nullptr; refuse(s, "null argument"); }
