@@ -263,6 +263,75 @@
                   :n-ops (.getValue n-ops) :n-process (.getValue n-proc)
                   :pool-mem (when pool (int-pool pool)) :pool-len (count pool)))))
 
+;; tbc_pair_events_batch (additive, ABI version 2): tbc_pair_events for many histories in one call, on the device.  Its two structs
+;; have a table of their own, held against the ctypes binding by tests/test_pair_events_no_device.py as `abi` is by tests/test_clj_shim.py.
+(def pair-abi
+  {:event_batch {:size 56  :n_hist 0 :device 4 :ev_off 8 :type 16 :process 24 :f 32 :a 40 :b 48}
+   :pair_out    {:size 136 :ops_cap 0 :op_off 8 :n_events 16 :n_process 24 :f 32 :a 40 :b 48 :process 56 :inv_pos 64
+                 :ret_pos 72 :word 80 :status 88 :bad_row 96 :n_bad 104 :reserved0 108 :n_ops 112 :ns_device 120
+                 :bytes_in 128}})
+
+(defn- po
+  "Byte offset of field k of struct s of pair-abi (or its :size)."
+  ^long [s k]
+  (long (get-in pair-abi [s k])))
+
+(defn- cat-memory
+  "The Memory `k` (`width` bytes a row, (:n c) rows) of every element of `cs`, one after the other."
+  ^Memory [cs k width total]
+  (let [m (Memory. (* width (max 1 total)))]
+    (reduce (fn [at c]
+              (let [bytes (* width (long (:n c)))]
+                (when (pos? bytes) (.write m (long at) (.getByteArray ^Memory (k c) 0 bytes) 0 (int bytes)))
+                (+ at bytes)))
+            0 cs)
+    m))
+
+(defn pair-events-batch
+  "tbc_pair_events_batch: the `columns` of many histories -> per history what `paired` gives (views into the call's op
+   columns), or {:status s :bad-row r} for a history that is malformed (TBC_ERR_BAD_HISTORY, the row tbc_pair_events names) or has
+   more than 4,096 processes (TBC_ERR_UNSUPPORTED).  Returns nil when the call itself fails.  14 B an event go up, 21 B an op come back."
+  [colss {:keys [device] :or {device 0}}]
+  (let [nh     (count colss)
+        offs   (reductions + 0 (map :n colss))
+        total  (long (last offs))
+        cap    (max 1 total)
+        ev-off (Memory. (* 8 (inc nh)))
+        _      (dorun (map-indexed (fn [i v] (.setLong ev-off (* 8 i) (long v))) offs))
+        typ    (cat-memory colss :type 1 total) prc (cat-memory colss :process 4 total) fc (cat-memory colss :f 1 total)
+        a      (cat-memory colss :a 4 total)    b   (cat-memory colss :b 4 total)
+        op-off (Memory. (* 8 (inc nh))) n-ev (Memory. (* 4 (max 1 nh))) n-pr (Memory. (* 4 (max 1 nh)))
+        status (Memory. (* 4 (max 1 nh))) bad (Memory. (* 4 (max 1 nh)))
+        of     (Memory. cap) oa (Memory. (* 4 cap)) ob (Memory. (* 4 cap)) op* (Memory. (* 4 cap))
+        inv    (Memory. (* 4 cap)) ret (Memory. (* 4 cap))
+        in     (doto (Memory. (po :event_batch :size)) (.clear)
+                 (.setInt (po :event_batch :n_hist) nh) (.setInt (po :event_batch :device) device)
+                 (.setPointer (po :event_batch :ev_off) ev-off) (.setPointer (po :event_batch :type) typ)
+                 (.setPointer (po :event_batch :process) prc) (.setPointer (po :event_batch :f) fc)
+                 (.setPointer (po :event_batch :a) a) (.setPointer (po :event_batch :b) b))
+        out    (doto (Memory. (po :pair_out :size)) (.clear)
+                 (.setLong (po :pair_out :ops_cap) total) (.setPointer (po :pair_out :op_off) op-off)
+                 (.setPointer (po :pair_out :n_events) n-ev) (.setPointer (po :pair_out :n_process) n-pr)
+                 (.setPointer (po :pair_out :f) of) (.setPointer (po :pair_out :a) oa) (.setPointer (po :pair_out :b) ob)
+                 (.setPointer (po :pair_out :process) op*) (.setPointer (po :pair_out :inv_pos) inv)
+                 (.setPointer (po :pair_out :ret_pos) ret) (.setPointer (po :pair_out :word) Pointer/NULL)
+                 (.setPointer (po :pair_out :status) status) (.setPointer (po :pair_out :bad_row) bad))
+        st     (keeping [colss ev-off typ prc fc a b op-off n-ev n-pr status bad of oa ob op* inv ret in out]
+                 (.invokeInt (f "tbc_pair_events_batch") (to-array [in out])))]
+    (when (zero? st)
+      (vec (map-indexed
+             (fn [h cols]
+               (let [s (.getInt status (* 4 h))]
+                 (if-not (zero? s)
+                   {:status s :bad-row (Integer/toUnsignedLong (.getInt bad (* 4 h)))}
+                   (let [lo  (.getLong op-off (* 8 h))
+                         k   (- (.getLong op-off (* 8 (inc h))) lo)
+                         cut (fn [^Memory m width] (.share m (* width lo) (max 1 (* width k))))]
+                     (assoc cols :of (cut of 1) :oa (cut oa 4) :ob (cut ob 4) :oproc (cut op* 4) :inv (cut inv 4) :ret (cut ret 4)
+                                 :n-ops (int k) :n-process (.getInt n-pr (* 4 h))
+                                 :pool-mem (when (:pool cols) (int-pool (:pool cols))) :pool-len (count (:pool cols)))))))
+             colss)))))
+
 (defn- ops-struct ^Memory [{:keys [n n-ops n-process of oa ob oproc inv ret pool-mem pool-len]}]
   (doto (struct :ops)
     (.setInt (o :ops :n) n-ops) (.setInt (o :ops :n_events) n)

@@ -45,7 +45,8 @@ extern "C" {
  * tbc_comm_* (the sharded sweep's exchange behind the C-ABI); tbc_setfull_create_rows takes its exception lists in any order again.
  * Still 2, additive: tbc_ledger_snapshots and its structs.
  * Still 2, additive: tbc_ledger_journal and its structs.
- * Still 2, additive: tbc_ledger_cycles and its structs. */
+ * Still 2, additive: tbc_ledger_cycles and its structs.
+ * Still 2, additive: tbc_pair_events_batch and its structs. */
 #define TBC_ABI_VERSION 2u
 
 /* ------------------------------------------------------------------ status */
@@ -127,7 +128,8 @@ typedef struct tbc_ops {
  *   - process ids are re-numbered densely in order of first appearance.
  * Output arrays are caller-allocated with capacity ev->n; *n_ops, *n_process
  * receive the counts.  ev_index[i] = row of op i's invocation (its :index).
- * Pure host code, no device needed.
+ * Pure host code, no device needed: one history a call, one thread.  tbc_pair_events_batch (below, "pairing on the device") does
+ * the same for many histories in one call on the device; this function is its specification.
  */
 tbc_status tbc_pair_events(const tbc_events* ev,
                            uint8_t* f, int32_t* a, int32_t* b, int32_t* process,
@@ -1167,6 +1169,59 @@ typedef struct tbc_perf_out {             /* arrays caller-allocated, each optio
 } tbc_perf_out;
 tbc_status tbc_perf_plan_sizes(const tbc_perf_in* in, tbc_perf_sizes* sizes);
 tbc_status tbc_perf_series(const tbc_perf_in* in, tbc_perf_out* out);
+
+/* ------------------------------------------------------------------- pairing on the device, many histories a call
+ * tbc_pair_events_batch: tbc_pair_events for n_hist event histories at once, decided on the device (csrc/pair_*.h).  History h owns
+ * the rows [ev_off[h], ev_off[h + 1]) of the five event columns, which are those of tbc_events concatenated; ev_off[0] = 0, ascending,
+ * a history has fewer than 2^31 rows and a call 2^32 - 1 at most.  The columns are caller-owned (pageable or pinned) and go to the
+ * device as they are, 14 B a row.
+ * Of a WELL-FORMED history the six op columns, op_off[h + 1] - op_off[h] and n_process[h] are bit for bit what tbc_pair_events
+ * writes for that history alone (inv_pos / ret_pos are rows within the history); n_events[h] = its rows.  op_off, n_events and
+ * n_process are the three descriptor arrays of tbc_batch_desc and tbc_batch_input; `word` is TBC_WIRE_WORD(f, a8, b8, process) as
+ * tbc_batch_reload encodes it, so the pointers of a mapped input slot can be passed here and tbc_batch_submit_input called after.
+ * A MALFORMED history (an invocation while the process's op is open; an invocation after the process's :info; a completion without an
+ * invocation; an unknown :type code) has status[h] = TBC_ERR_BAD_HISTORY and bad_row[h] = the row tbc_pair_events names, contributes
+ * no op and n_process[h] = 0; the other histories are unaffected, the call returns TBC_OK and n_bad counts the histories whose status
+ * is not TBC_OK.  status[h] = TBC_ERR_UNSUPPORTED (no op, n_process[h] = 0, bad_row 0xFFFFFFFF): more than TBC_PAIR_MAX_PROCESS
+ * distinct :process values among the history's rows (counted in steps of 64 rows up to and including the step of the first malformed
+ * row: there it takes precedence, past it the history is malformed), or -- only when `word` is asked for
+ * -- a surviving op the wire format does not hold (f > 15; a value outside 0..254 that is not nil, b looked at for :cas only).
+ * More surviving ops in the call than ops_cap: TBC_ERR_INVALID_ARG, the count in tbc_last_error(), no op array written.  A null
+ * argument, ev_off that does not start at 0 or descends, too many rows: TBC_ERR_INVALID_ARG, decided before the device is looked
+ * for; valid input without a gfx950 device: TBC_ERR_NO_DEVICE (no CPU fallback).  One-shot and re-entrant as tbc_ledger_check is. */
+#define TBC_PAIR_MAX_PROCESS 4096u
+#define TBC_PAIR_NO_ROW 0xFFFFFFFFu
+
+typedef struct tbc_event_batch {
+  uint32_t n_hist, device;
+  const uint64_t* ev_off;        /* [n_hist + 1] */
+  const uint8_t* type;           /* the columns of tbc_events, [ev_off[n_hist]] each */
+  const int32_t* process;
+  const uint8_t* f;
+  const int32_t* a;
+  const int32_t* b;
+} tbc_event_batch;
+
+typedef struct tbc_pair_out {    /* every array caller-allocated */
+  uint64_t ops_cap;              /* ops the op arrays hold */
+  uint64_t* op_off;              /* [n_hist + 1] */
+  uint32_t* n_events;            /* [n_hist] */
+  uint32_t* n_process;           /* [n_hist] */
+  uint8_t* f;                    /* [ops_cap]; f, a, b, process: NULL = not wanted */
+  int32_t* a;
+  int32_t* b;
+  int32_t* process;
+  uint32_t* inv_pos;             /* [ops_cap] */
+  uint32_t* ret_pos;             /* [ops_cap] */
+  uint32_t* word;                /* [ops_cap], NULL = not wanted */
+  int32_t* status;               /* [n_hist] a tbc_status */
+  uint32_t* bad_row;             /* [n_hist] TBC_PAIR_NO_ROW: none */
+  uint32_t n_bad, reserved0;
+  uint64_t n_ops;                /* = op_off[n_hist] */
+  uint64_t ns_device;            /* the kernels, between HIP events */
+  uint64_t bytes_in;             /* copied to the device */
+} tbc_pair_out;
+tbc_status tbc_pair_events_batch(const tbc_event_batch* in, tbc_pair_out* out);
 
 /* ------------------------------------------------------------------- misc */
 uint32_t tbc_version(void);             /* TBC_ABI_VERSION                       */

@@ -340,6 +340,24 @@ class PerfOut(C.Structure):
                 ("open_last", C.POINTER(C.c_int32)), ("open_fill", C.POINTER(C.c_int32)), ("summary", PerfSummary)]
 
 
+# tbc_pair_events_batch: tbc_pair_events for many histories a call, on the device (include/tbcheck.h)
+PAIR_MAX_PROCESS = 4096
+PAIR_NO_ROW = 0xFFFFFFFF
+
+
+class EventBatch(C.Structure):
+    _fields_ = [("n_hist", C.c_uint32), ("device", C.c_uint32), ("ev_off", C.POINTER(C.c_uint64)), ("type", C.POINTER(C.c_uint8)),
+                ("process", C.POINTER(C.c_int32)), ("f", C.POINTER(C.c_uint8)), ("a", C.POINTER(C.c_int32)), ("b", C.POINTER(C.c_int32))]
+
+
+class PairOut(C.Structure):
+    _fields_ = [("ops_cap", C.c_uint64), ("op_off", C.POINTER(C.c_uint64)), ("n_events", C.POINTER(C.c_uint32)),
+                ("n_process", C.POINTER(C.c_uint32)), ("f", C.POINTER(C.c_uint8)), ("a", C.POINTER(C.c_int32)), ("b", C.POINTER(C.c_int32)),
+                ("process", C.POINTER(C.c_int32)), ("inv_pos", C.POINTER(C.c_uint32)), ("ret_pos", C.POINTER(C.c_uint32)),
+                ("word", C.POINTER(C.c_uint32)), ("status", C.POINTER(C.c_int32)), ("bad_row", C.POINTER(C.c_uint32)),
+                ("n_bad", C.c_uint32), ("reserved0", C.c_uint32), ("n_ops", C.c_uint64), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64)]
+
+
 class BatchInput(C.Structure):
     """tbc_batch_input: pointers into one pinned slot of a batch (tbc_batch_map_input)."""
     _fields_ = [("n_hist_cap", C.c_uint32), ("reserved0", C.c_uint32), ("ops_cap", C.c_uint64),
@@ -379,6 +397,7 @@ SYMBOLS = {
     "tbc_pair_events": (C.c_int, [C.POINTER(Events), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tbc_pair_events_batch": (C.c_int, [C.POINTER(EventBatch), C.POINTER(PairOut)]),
     "tbc_check": (C.c_int, [C.POINTER(Ops), C.POINTER(Model), C.POINTER(Opts), C.POINTER(Result)]),
     "tbc_result_free": (None, [C.POINTER(Result)]),
     "tbc_batch_create": (C.c_int, [C.POINTER(BatchDesc), C.POINTER(Model), C.POINTER(Opts), C.POINTER(C.c_void_p)]),

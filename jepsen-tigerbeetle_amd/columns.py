@@ -98,3 +98,70 @@ def pair_events(ev: EventColumns) -> OpColumns:
     k = n_ops.value
     return OpColumns(f[:k].copy(), a[:k].copy(), b[:k].copy(), proc[:k].copy(), inv[:k].copy(), ret[:k].copy(),
                      n_events=n, n_process=n_proc.value)
+
+
+def concat_events(evs):
+    """Event histories side by side as tbc_event_batch takes them: (ev_off u64[n + 1], EventColumns of the concatenation)."""
+    nh = len(evs)
+    ev_off = np.zeros(nh + 1, np.uint64)
+    if nh:
+        np.cumsum(np.fromiter((len(e) for e in evs), np.uint64, nh), out=ev_off[1:])
+    cat = lambda name, dt: (np.ascontiguousarray(np.concatenate([getattr(e, name) for e in evs]).astype(dt, copy=False))
+                            if nh else np.zeros(0, dt))
+    return ev_off, EventColumns(cat("type", np.uint8), cat("process", np.int32), cat("f", np.uint8), cat("a", np.int32), cat("b", np.int32))
+
+
+def pair_events_batch_raw(ev_off, ev: EventColumns, ops_cap=None, columns=True, word=False, device=0, into=None, call=None, alloc=np.zeros):
+    """tbc_pair_events_batch on concatenated event columns (concat_events).  -> (status of the call, dict of the output arrays
+    and of n_bad, n_ops, ns_device, bytes_in).  ops_cap: the capacity of the op arrays (default: one op per event); columns: ask for
+    f, a, b, process; word: ask for the wire word; into: a mapped input slot (core.Batch.map_input) whose op_off, n_events,
+    n_process, word, inv_pos and ret_pos are written in place; call: another implementation of the entry point (the tests' emulator);
+    alloc(n, dtype): where the op arrays come from (pinned memory, for a caller that has some)."""
+    nh = len(ev_off) - 1
+    n = int(ev_off[-1])
+    cap = n if ops_cap is None else int(ops_cap)
+    m = max(cap, 1)
+    r = {"status": np.zeros(max(nh, 1), np.int32), "bad_row": np.zeros(max(nh, 1), np.uint32)}
+    if into is None:
+        r.update(op_off=np.zeros(nh + 1, np.uint64), n_events=np.zeros(max(nh, 1), np.uint32), n_process=np.zeros(max(nh, 1), np.uint32),
+                 inv_pos=alloc(m, np.uint32), ret_pos=alloc(m, np.uint32))
+        if word:
+            r["word"] = alloc(m, np.uint32)
+    else:
+        if nh > into["n_hist_cap"]:
+            raise ValueError(f"{nh} histories, the batch's slots hold {into['n_hist_cap']}")
+        cap = int(into["ops_cap"]) if ops_cap is None else min(cap, int(into["ops_cap"]))
+        r.update({k: into[k] for k in ("op_off", "n_events", "n_process", "inv_pos", "ret_pos", "word")})
+    if columns:
+        r.update(f=alloc(m, np.uint8), a=alloc(m, np.int32), b=alloc(m, np.int32), process=alloc(m, np.int32))
+    i = N.EventBatch()
+    i.n_hist, i.device, i.ev_off = nh, device, _p(ev_off, C.c_uint64)
+    i.type, i.process, i.f, i.a, i.b = _p(ev.type, C.c_uint8), _p(ev.process, C.c_int32), _p(ev.f, C.c_uint8), _p(ev.a, C.c_int32), _p(ev.b, C.c_int32)
+    o = N.PairOut()
+    o.ops_cap = cap
+    for name, ct in (("op_off", C.c_uint64), ("n_events", C.c_uint32), ("n_process", C.c_uint32), ("f", C.c_uint8), ("a", C.c_int32),
+                     ("b", C.c_int32), ("process", C.c_int32), ("inv_pos", C.c_uint32), ("ret_pos", C.c_uint32), ("word", C.c_uint32),
+                     ("status", C.c_int32), ("bad_row", C.c_uint32)):
+        if name in r:
+            setattr(o, name, _p(r[name], ct))
+    st = (call or N.lib().tbc_pair_events_batch)(C.byref(i), C.byref(o))
+    r.update(n_bad=int(o.n_bad), n_ops=int(o.n_ops), ns_device=int(o.ns_device), bytes_in=int(o.bytes_in))
+    r["status"], r["bad_row"] = r["status"][:nh], r["bad_row"][:nh]
+    return st, r
+
+
+def pair_events_batch(evs, device=0):
+    """tbc_pair_events_batch: pair_events for many histories in one call, on the device.
+    -> (list of OpColumns, None where the history is refused; status int32[n]; bad_row uint32[n], PAIR_NO_ROW where there is none)."""
+    ev_off, ev = concat_events(evs)
+    st, r = pair_events_batch_raw(ev_off, ev, device=device)
+    N.check_status(st)
+    ops = []
+    for h in range(len(evs)):
+        if r["status"][h] != N.OK_STATUS:
+            ops.append(None)
+            continue
+        lo, hi = int(r["op_off"][h]), int(r["op_off"][h + 1])
+        ops.append(OpColumns(*[r[k][lo:hi].copy() for k in ("f", "a", "b", "process", "inv_pos", "ret_pos")],
+                             n_events=int(r["n_events"][h]), n_process=int(r["n_process"][h])))
+    return ops, r["status"], r["bad_row"]

@@ -172,7 +172,9 @@ class Batch:
     def map_input(self, slot):
         """Slot `slot` of the batch's pinned host memory as numpy views the caller fills IN PLACE:
         {"op_off" u64[n_hist_cap + 1], "n_events", "n_process" u32[n_hist_cap], "word", "inv_pos", "ret_pos" u32[ops_cap]}.
-        Waits until the slot's previous input has left for the device."""
+        Waits until the slot's previous input has left for the device.
+        Slots 0 and 1 are the ones reload() fills in turn, slots 2 and 3 the ones reload_events() fills in turn: a caller who fills
+        slots of their own beside those calls takes 4 .. 15."""
         i = N.BatchInput()
         N.check_status(N.lib().tbc_batch_map_input(self._h, slot, C.byref(i)))
         nh, no = int(i.n_hist_cap), int(i.ops_cap)
@@ -193,7 +195,8 @@ class Batch:
         return f.astype(np.uint32) | (a8 << np.uint32(4)) | (b8 << np.uint32(12)) | (process.astype(np.uint32) << np.uint32(20))
 
     def fill_input(self, slot, histories: Sequence[OpColumns]):
-        """Write `histories` into slot `slot` in wire format (what a caller's own encoder would do in place).  -> n_hist"""
+        """Write `histories` into slot `slot` in wire format (what a caller's own encoder would do in place).  -> n_hist
+        (Which slots reload() and reload_events() use themselves: map_input.)"""
         m = self.map_input(slot)
         nh = len(histories)
         if nh > m["n_hist_cap"]:
@@ -245,6 +248,31 @@ class Batch:
         if not hasattr(self, "_pending_n"):
             self._pending_n = []
         self._pending_n.append(nh)
+        return self
+
+    def reload_events(self, events):
+        """Event histories (columns.EventColumns) straight into the batch: a slot is mapped, tbc_pair_events_batch pairs them on the
+        device INTO the slot's pointers (descriptors, wire words, positions), and the slot is submitted.  A malformed history, or one
+        the wire format does not hold, raises before anything is submitted.  Slots 2 and 3 in turn (map_input).
+        pair_call_s, pair_ns_device and pair_bytes_in are left on the object for whoever measures, as reload() leaves reload_call_s:
+        the C call's wall time, its kernels' time and what it copied in."""
+        from .columns import concat_events, pair_events_batch_raw
+        slot = 2 + (getattr(self, "_events_slot", 0) & 1)          # (tbc_batch_reload takes slots 0 and 1 in turn)
+        m = self.map_input(slot)
+        ev_off, ev = concat_events(events)
+        import time as _time
+        t0 = _time.perf_counter()
+        st, r = pair_events_batch_raw(ev_off, ev, columns=False, word=True, device=self._o.device, into=m)
+        self.pair_call_s = _time.perf_counter() - t0               # (the C call alone)
+        self.pair_ns_device, self.pair_bytes_in = r["ns_device"], r["bytes_in"]
+        N.check_status(st)
+        if r["n_bad"]:
+            h = int(np.flatnonzero(r["status"])[0])
+            raise N.TbcError(int(r["status"][h]), f"reload_events: history {h} of {r['n_bad']} refused" +
+                           (f": malformed at row {int(r['bad_row'][h])}" if r["status"][h] == N.ERR_BAD_HISTORY else
+                            ": more than 4096 processes, or ops the wire format does not hold"))
+        self.submit_input(slot, len(events))
+        self._events_slot = getattr(self, "_events_slot", 0) + 1
         return self
 
     def input_info(self):
