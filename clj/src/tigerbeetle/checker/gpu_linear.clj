@@ -332,6 +332,66 @@
                                  :pool-mem (when (:pool cols) (int-pool (:pool cols))) :pool-len (count (:pool cols)))))))
              colss)))))
 
+;; Events straight into a batch (additive, ABI version 2): tbc_pack_events, tbc_batch_map_events, tbc_batch_submit_events.  Packed events
+;; (8 B a row: TBC_EVENT_WORD + :process) are written into a pinned event slot of the batch, paired on the device, and their wire columns
+;; emitted into the batch's device stage; only the descriptors come back.  The structs have a table of their own, as pair-abi has, held
+;; against the ctypes binding by tests/test_submit_events_shim.py.  Not for a count-form batch (include/tbcheck.h): there, pair-events-batch
+;; into a mapped op slot.
+(def events-abi
+  {:batch_events  {:size 40 :n_hist_cap 0 :reserved0 4 :events_cap 8 :ev_off 16 :ev_word 24 :process 32}
+   :events_report {:size 48 :status 0 :bad_row 8 :n_bad 16 :reserved0 20 :n_ops 24 :ns_device 32 :bytes_in 40}})
+
+(defn- eo
+  "Byte offset of field k of struct s of events-abi (or its :size)."
+  ^long [s k]
+  (long (get-in events-abi [s k])))
+
+(defn pack-events
+  "tbc_pack_events: the `columns` of one history -> its packed event words, written at `words` (a Pointer with room for (:n cols) ints:
+   a view into a mapped event slot, or a Memory).  The :process column travels beside them as it is.  Returns the status."
+  [cols ^Pointer words]
+  (let [es (events-struct cols)]
+    (keeping [cols es words]
+      (.invokeInt (f "tbc_pack_events") (to-array [es words])))))
+
+(defn map-events
+  "tbc_batch_map_events: event slot `slot` of the batch `handle` -> {:n-hist-cap :events-cap :ev-off :ev-word :process} (Pointers into
+   pinned memory the caller fills in place), or nil.  events-cap 0 = three times the batch's op capacity; the first mapping fixes it."
+  [handle slot events-cap]
+  (let [m (doto (Memory. (eo :batch_events :size)) (.clear))]
+    (when (zero? (keeping [m] (.invokeInt (f "tbc_batch_map_events") (to-array [handle (int slot) (long events-cap) m]))))
+      {:n-hist-cap (.getInt m (eo :batch_events :n_hist_cap)) :events-cap (.getLong m (eo :batch_events :events_cap))
+       :ev-off (.getPointer m (eo :batch_events :ev_off)) :ev-word (.getPointer m (eo :batch_events :ev_word))
+       :process (.getPointer m (eo :batch_events :process))})))
+
+(defn submit-events
+  "The `columns` of many histories into event slot `slot` of the batch `handle` and on to the device: each history packed in place
+   (pack-events), its :process column copied beside, then tbc_batch_submit_events.  Returns {:status s :n-ops :n-bad :statuses :bad-rows}
+   -- s zero: the input is pending and the next tbc_batch_run answers it; otherwise nothing is pending and the batch is as it was (the
+   per-history statuses say which history was refused, and at which row) -- or nil when the histories do not fit the slot."
+  [handle slot colss]
+  (let [nh    (count colss)
+        total (long (reduce + (map :n colss)))]
+    (when-let [{:keys [n-hist-cap events-cap ^Pointer ev-off ^Pointer ev-word ^Pointer process]} (map-events handle slot 0)]
+      (when (and (pos? nh) (<= nh n-hist-cap) (<= total events-cap))
+        (.setLong ev-off 0 0)
+        (reduce (fn [at [h c]]
+                  (let [n (long (:n c))]
+                    (when (pos? n)
+                      (pack-events c (.share ev-word (* 4 at)))
+                      (.write process (* 4 at) (.getByteArray ^Memory (:process c) 0 (int (* 4 n))) 0 (int (* 4 n))))
+                    (.setLong ev-off (* 8 (inc h)) (+ at n))
+                    (+ at n)))
+                0 (map-indexed vector colss))
+        (let [status (Memory. (* 4 nh)) bad (Memory. (* 4 nh))
+              rep    (doto (Memory. (eo :events_report :size)) (.clear)
+                       (.setPointer (eo :events_report :status) status) (.setPointer (eo :events_report :bad_row) bad))
+              st     (keeping [colss status bad rep]
+                       (.invokeInt (f "tbc_batch_submit_events") (to-array [handle (int slot) (int nh) rep])))]
+          {:status st :n-ops (.getLong rep (eo :events_report :n_ops)) :n-bad (.getInt rep (eo :events_report :n_bad))
+           :statuses (mapv #(.getInt status (* 4 %)) (range nh))
+           :bad-rows (mapv #(Integer/toUnsignedLong (.getInt bad (* 4 %))) (range nh))})))))
+
 (defn- ops-struct ^Memory [{:keys [n n-ops n-process of oa ob oproc inv ret pool-mem pool-len]}]
   (doto (struct :ops)
     (.setInt (o :ops :n) n-ops) (.setInt (o :ops :n_events) n)

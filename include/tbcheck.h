@@ -46,7 +46,8 @@ extern "C" {
  * Still 2, additive: tbc_ledger_snapshots and its structs.
  * Still 2, additive: tbc_ledger_journal and its structs.
  * Still 2, additive: tbc_ledger_cycles and its structs.
- * Still 2, additive: tbc_pair_events_batch and its structs. */
+ * Still 2, additive: tbc_pair_events_batch and its structs.
+ * Still 2, additive: tbc_pack_events, tbc_pair_packed_batch, tbc_batch_map_events / _submit_events and their structs. */
 #define TBC_ABI_VERSION 2u
 
 /* ------------------------------------------------------------------ status */
@@ -1222,6 +1223,91 @@ typedef struct tbc_pair_out {    /* every array caller-allocated */
   uint64_t bytes_in;             /* copied to the device */
 } tbc_pair_out;
 tbc_status tbc_pair_events_batch(const tbc_event_batch* in, tbc_pair_out* out);
+
+/* ------------------------------------------------------------------- packed events, and events straight into a batch
+ * THE PACKED EVENT WORD.  A batch takes what the wire format holds (f <= 15, values 0..254 or nil), so an event bound for one loses
+ * nothing as TWO columns, 8 B a row instead of 14: a uint32_t ev_word and the int32_t process column as it is (process ids are
+ * arbitrary and stay whole).  ev_word = TBC_EVENT_WORD(type, f, a, b) over ENCODED fields:
+ *   bits 0-2    type   TBC_INVOKE .. TBC_INFO; TBC_EVW_TYPE_UNKNOWN (7) = a :type code that is none of them
+ *   bits 3-7    f      0..15; TBC_EVW_F_ABOVE (16) = an :f above 15
+ *   bits 8-16   a      0..254; TBC_EVW_NIL (255) = nil; TBC_EVW_UNFIT (256) = a value the wire format does not hold
+ *   bits 17-25  b      as a
+ * The three codes beside the values keep every rule of tbc_pair_events_batch with `word` asked for decidable from the packed form,
+ * with the same answer: the malformed row (an unknown :type), and TBC_ERR_UNSUPPORTED for a SURVIVING op whose f, a -- or b of a
+ * :cas -- does not fit (a failed op with such a value is still fine).  Read back, an encoded field is its value, the codes 7, 16
+ * and 256 themselves, and TBC_EVW_NIL is TBC_NIL.
+ * tbc_pack_events: one history's five columns -> its words, ev_word[ev->n]; host code, no device (the process column is not touched:
+ * the caller passes it on beside the words).
+ * tbc_pair_packed_batch: tbc_pair_events_batch over the packed form -- the same plan, kernels, steps and output contract, the events
+ * those the words decode to; it differs in what is copied in: bytes_in = 8 B a row + 8 B * (n_hist + 1). */
+#define TBC_EVW_TYPE_UNKNOWN 7u
+#define TBC_EVW_F_ABOVE 16u
+#define TBC_EVW_NIL 255u
+#define TBC_EVW_UNFIT 256u
+#define TBC_EVENT_WORD(type, f, a, b) ((uint32_t)(type) | ((uint32_t)(f) << 3) | ((uint32_t)(a) << 8) | ((uint32_t)(b) << 17))
+#define TBC_EVW_TYPE(w) ((uint32_t)(w) & 7u)
+#define TBC_EVW_F(w) (((uint32_t)(w) >> 3) & 31u)
+#define TBC_EVW_A(w) (((uint32_t)(w) >> 8) & 511u)
+#define TBC_EVW_B(w) (((uint32_t)(w) >> 17) & 511u)
+#define TBC_EVW_VALUE(v9) ((v9) == TBC_EVW_NIL ? TBC_NIL : (int32_t)(v9))      /* an encoded a / b read back */
+
+tbc_status tbc_pack_events(const tbc_events* ev, uint32_t* ev_word);
+
+typedef struct tbc_packed_event_batch {
+  uint32_t n_hist, device;
+  const uint64_t* ev_off;        /* [n_hist + 1] as tbc_event_batch.ev_off */
+  const uint32_t* ev_word;       /* [ev_off[n_hist]] */
+  const int32_t* process;        /* [ev_off[n_hist]] */
+} tbc_packed_event_batch;
+tbc_status tbc_pair_packed_batch(const tbc_packed_event_batch* in, tbc_pair_out* out);
+
+/* EVENTS INTO A BATCH.  tbc_batch_map_events / tbc_batch_submit_events are to event histories what tbc_batch_map_input /
+ * tbc_batch_submit_input are to op columns: the caller writes packed events into library-owned PINNED memory, the library pairs them
+ * on the device (the kernels of tbc_pair_events_batch, on the batch's COPY stream, so under whatever the batch is searching) and the
+ * wire columns are emitted straight into the batch's device stage; only the per-history descriptors come back.
+ *   tbc_batch_map_events     the event slots (slot < 16) are a second set of pinned slots, apart from the op slots.  events_cap = 0
+ *                            means 3 * the batch's ops_cap (tbc_input_info); the FIRST mapping fixes events_cap for the batch and a
+ *                            later, larger request is TBC_ERR_INVALID_ARG.  Waits until the slot's previous events have left for the
+ *                            device.  The first mapping also allocates the batch's device event arena, once, kept until
+ *                            tbc_batch_destroy (24 B an event and 36 B a history; tbc_batch_device_bytes counts it).
+ *   tbc_batch_submit_events  the slot holds n_hist histories: ev_off[0..n_hist] (the rules of tbc_event_batch.ev_off), the words, the
+ *                            process column.  Validated on the host in O(histories) (INVALID_ARG: ev_off; n_hist = 0 or beyond the
+ *                            batch's n_hist_cap; more events than events_cap; two inputs pending already; the slot unmapped or still
+ *                            being copied).  Then the three arrays go up, the histories are paired, and the descriptors -- op_off,
+ *                            n_events, n_process, status, bad_row, the totals: TBC_EVENTS_DESC_BYTES(n_hist) -- come back; the call
+ *                            BLOCKS its thread until the pairing is done (it never waits for the compute stream) and fills `rep`
+ *                            (null: no report).  ALL OR NOTHING: a history that is not TBC_OK -> TBC_ERR_BAD_HISTORY if one is
+ *                            malformed, else TBC_ERR_UNSUPPORTED; more surviving ops than the batch's ops_cap -> TBC_ERR_INVALID_ARG,
+ *                            the count in tbc_last_error().  Then nothing is pending, no stage has been written and the batch still
+ *                            answers its resident input.  Otherwise the input is laid out as tbc_batch_submit_input lays one out
+ *                            (the same refusals), its wire columns are emitted into the stage and it is pending: the next
+ *                            tbc_batch_run consumes it.
+ * tbc_input_info.bytes_copied of such an input is what crossed PCIe for it: 8 B an event + 8 B * (n_hist + 1) up and
+ * TBC_EVENTS_DESC_BYTES(n_hist) down (an op input: 12 B an op).
+ * A COUNT-FORM batch plans its crashed calls on the host from the wire words, which this route never brings to the host:
+ * tbc_batch_submit_events on one is TBC_ERR_UNSUPPORTED; its route is tbc_pair_events_batch into a mapped OP slot and
+ * tbc_batch_submit_input.  Batches that take no fresh inputs refuse as tbc_batch_map_input refuses. */
+#define TBC_EVENTS_DESC_BYTES(n_hist) (16ull + 8ull * ((uint64_t)(n_hist) + 1ull) + 16ull * (uint64_t)(n_hist))
+
+typedef struct tbc_batch_events {  /* pointers into one pinned slot; valid until the batch is destroyed */
+  uint32_t n_hist_cap, reserved0;
+  uint64_t events_cap;
+  uint64_t* ev_off;                /* [n_hist_cap + 1] */
+  uint32_t* ev_word;               /* [events_cap] */
+  int32_t* process;                /* [events_cap] */
+} tbc_batch_events;
+
+typedef struct tbc_events_report { /* arrays caller-allocated, [n_hist]; each optional */
+  int32_t* status;                 /* a tbc_status per history */
+  uint32_t* bad_row;               /* TBC_PAIR_NO_ROW: none */
+  uint32_t n_bad, reserved0;
+  uint64_t n_ops;                  /* surviving ops of the input */
+  uint64_t ns_device;              /* the pairing kernels, between HIP events */
+  uint64_t bytes_in;               /* copied to the device */
+} tbc_events_report;
+
+tbc_status tbc_batch_map_events(tbc_batch* b, uint32_t slot, uint64_t events_cap, tbc_batch_events* out);
+tbc_status tbc_batch_submit_events(tbc_batch* b, uint32_t slot, uint32_t n_hist, tbc_events_report* rep);
 
 /* ------------------------------------------------------------------- misc */
 uint32_t tbc_version(void);             /* TBC_ABI_VERSION                       */

@@ -358,6 +358,31 @@ class PairOut(C.Structure):
                 ("n_bad", C.c_uint32), ("reserved0", C.c_uint32), ("n_ops", C.c_uint64), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64)]
 
 
+# the packed event word (include/tbcheck.h TBC_EVENT_WORD): type bits 0-2, f bits 3-7, a bits 8-16, b bits 17-25
+EVW_TYPE_UNKNOWN, EVW_F_ABOVE, EVW_NIL, EVW_UNFIT = 7, 16, 255, 256
+
+
+class PackedEventBatch(C.Structure):
+    _fields_ = [("n_hist", C.c_uint32), ("device", C.c_uint32), ("ev_off", C.POINTER(C.c_uint64)), ("ev_word", C.POINTER(C.c_uint32)),
+                ("process", C.POINTER(C.c_int32))]
+
+
+class BatchEvents(C.Structure):
+    """tbc_batch_events: pointers into one pinned event slot of a batch (tbc_batch_map_events)."""
+    _fields_ = [("n_hist_cap", C.c_uint32), ("reserved0", C.c_uint32), ("events_cap", C.c_uint64), ("ev_off", C.POINTER(C.c_uint64)),
+                ("ev_word", C.POINTER(C.c_uint32)), ("process", C.POINTER(C.c_int32))]
+
+
+class EventsReport(C.Structure):
+    _fields_ = [("status", C.POINTER(C.c_int32)), ("bad_row", C.POINTER(C.c_uint32)), ("n_bad", C.c_uint32), ("reserved0", C.c_uint32),
+                ("n_ops", C.c_uint64), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64)]
+
+
+def events_desc_bytes(n_hist):
+    """TBC_EVENTS_DESC_BYTES: what tbc_batch_submit_events brings back from the device"""
+    return 16 + 8 * (n_hist + 1) + 16 * n_hist
+
+
 class BatchInput(C.Structure):
     """tbc_batch_input: pointers into one pinned slot of a batch (tbc_batch_map_input)."""
     _fields_ = [("n_hist_cap", C.c_uint32), ("reserved0", C.c_uint32), ("ops_cap", C.c_uint64),
@@ -398,6 +423,10 @@ SYMBOLS = {
                                   C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "tbc_pair_events_batch": (C.c_int, [C.POINTER(EventBatch), C.POINTER(PairOut)]),
+    "tbc_pack_events": (C.c_int, [C.POINTER(Events), C.POINTER(C.c_uint32)]),
+    "tbc_pair_packed_batch": (C.c_int, [C.POINTER(PackedEventBatch), C.POINTER(PairOut)]),
+    "tbc_batch_map_events": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(BatchEvents)]),
+    "tbc_batch_submit_events": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(EventsReport)]),
     "tbc_check": (C.c_int, [C.POINTER(Ops), C.POINTER(Model), C.POINTER(Opts), C.POINTER(Result)]),
     "tbc_result_free": (None, [C.POINTER(Result)]),
     "tbc_batch_create": (C.c_int, [C.POINTER(BatchDesc), C.POINTER(Model), C.POINTER(Opts), C.POINTER(C.c_void_p)]),

@@ -111,8 +111,22 @@ def concat_events(evs):
     return ev_off, EventColumns(cat("type", np.uint8), cat("process", np.int32), cat("f", np.uint8), cat("a", np.int32), cat("b", np.int32))
 
 
-def pair_events_batch_raw(ev_off, ev: EventColumns, ops_cap=None, columns=True, word=False, device=0, into=None, call=None, alloc=np.zeros):
-    """tbc_pair_events_batch on concatenated event columns (concat_events).  -> (status of the call, dict of the output arrays
+def pack_events(ev: EventColumns, out=None) -> np.ndarray:
+    """tbc_pack_events: one history's columns -> its packed event words (TBC_EVENT_WORD, uint32[len(ev)]); the process column
+    travels beside them as it is.  out: where to write them (a view of a mapped event slot, core.Batch.map_events)."""
+    n = len(ev)
+    if out is None:
+        out = np.zeros(n, np.uint32)
+    elif len(out) != n or out.dtype != np.uint32 or not out.flags.c_contiguous:
+        raise ValueError("pack_events: out must be a contiguous uint32 array of the history's length")
+    es = ev.struct()
+    N.check_status(N.lib().tbc_pack_events(C.byref(es), _p(out, C.c_uint32)))
+    return out
+
+
+def pair_events_batch_raw(ev_off, ev, ops_cap=None, columns=True, word=False, device=0, into=None, call=None, alloc=np.zeros):
+    """tbc_pair_events_batch on concatenated event columns (concat_events) -- or tbc_pair_packed_batch, if `ev` is a pair
+    (ev_word uint32[events], process int32[events]) of packed events.  -> (status of the call, dict of the output arrays
     and of n_bad, n_ops, ns_device, bytes_in).  ops_cap: the capacity of the op arrays (default: one op per event); columns: ask for
     f, a, b, process; word: ask for the wire word; into: a mapped input slot (core.Batch.map_input) whose op_off, n_events,
     n_process, word, inv_pos and ret_pos are written in place; call: another implementation of the entry point (the tests' emulator);
@@ -134,9 +148,13 @@ def pair_events_batch_raw(ev_off, ev: EventColumns, ops_cap=None, columns=True, 
         r.update({k: into[k] for k in ("op_off", "n_events", "n_process", "inv_pos", "ret_pos", "word")})
     if columns:
         r.update(f=alloc(m, np.uint8), a=alloc(m, np.int32), b=alloc(m, np.int32), process=alloc(m, np.int32))
-    i = N.EventBatch()
+    packed = isinstance(ev, tuple)
+    i = N.PackedEventBatch() if packed else N.EventBatch()
     i.n_hist, i.device, i.ev_off = nh, device, _p(ev_off, C.c_uint64)
-    i.type, i.process, i.f, i.a, i.b = _p(ev.type, C.c_uint8), _p(ev.process, C.c_int32), _p(ev.f, C.c_uint8), _p(ev.a, C.c_int32), _p(ev.b, C.c_int32)
+    if packed:
+        i.ev_word, i.process = _p(ev[0], C.c_uint32), _p(ev[1], C.c_int32)
+    else:
+        i.type, i.process, i.f, i.a, i.b = _p(ev.type, C.c_uint8), _p(ev.process, C.c_int32), _p(ev.f, C.c_uint8), _p(ev.a, C.c_int32), _p(ev.b, C.c_int32)
     o = N.PairOut()
     o.ops_cap = cap
     for name, ct in (("op_off", C.c_uint64), ("n_events", C.c_uint32), ("n_process", C.c_uint32), ("f", C.c_uint8), ("a", C.c_int32),
@@ -144,7 +162,7 @@ def pair_events_batch_raw(ev_off, ev: EventColumns, ops_cap=None, columns=True, 
                      ("status", C.c_int32), ("bad_row", C.c_uint32)):
         if name in r:
             setattr(o, name, _p(r[name], ct))
-    st = (call or N.lib().tbc_pair_events_batch)(C.byref(i), C.byref(o))
+    st = (call or (N.lib().tbc_pair_packed_batch if packed else N.lib().tbc_pair_events_batch))(C.byref(i), C.byref(o))
     r.update(n_bad=int(o.n_bad), n_ops=int(o.n_ops), ns_device=int(o.ns_device), bytes_in=int(o.bytes_in))
     r["status"], r["bad_row"] = r["status"][:nh], r["bad_row"][:nh]
     return st, r

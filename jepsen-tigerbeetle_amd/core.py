@@ -275,6 +275,71 @@ class Batch:
         self._events_slot = getattr(self, "_events_slot", 0) + 1
         return self
 
+    # ---- events straight into the batch's device stage (include/tbcheck.h "events into a batch")
+    def map_events(self, slot, events_cap=0):
+        """Event slot `slot` of the batch's pinned host memory as numpy views the caller fills IN PLACE:
+        {"n_hist_cap", "events_cap", "ev_off" u64[n_hist_cap + 1], "ev_word" u32[events_cap], "process" i32[events_cap]}.
+        events_cap = 0: 3 * the batch's ops_cap; the first mapping fixes it.  Waits until the slot's previous events have left for
+        the device.  Slots 0 and 1 are the ones stream_events() fills in turn."""
+        i = N.BatchEvents()
+        N.check_status(N.lib().tbc_batch_map_events(self._h, slot, events_cap, C.byref(i)))
+        nh, ne = int(i.n_hist_cap), int(i.events_cap)
+        view = lambda p, n: np.ctypeslib.as_array(p, shape=(n,))
+        return {"n_hist_cap": nh, "events_cap": ne, "ev_off": view(i.ev_off, nh + 1), "ev_word": view(i.ev_word, ne), "process": view(i.process, ne)}
+
+    def submit_events(self, slot, n_hist):
+        """tbc_batch_submit_events: the slot's packed events go up, are paired on the device, and their wire columns are emitted into
+        the batch's device stage; the next run() consumes them.  -> the report {"status", "bad_row", "n_bad", "n_ops", "ns_device",
+        "bytes_in"}.  All or nothing: a refused history or too many ops raises TbcError (its .report is the report) and leaves the
+        batch as it was."""
+        status, bad_row = np.zeros(max(n_hist, 1), np.int32), np.zeros(max(n_hist, 1), np.uint32)
+        rep = N.EventsReport()
+        rep.status, rep.bad_row = _p(status, C.c_int32), _p(bad_row, C.c_uint32)
+        st = N.lib().tbc_batch_submit_events(self._h, slot, n_hist, C.byref(rep))
+        report = {"status": status[:n_hist], "bad_row": bad_row[:n_hist], "n_bad": int(rep.n_bad), "n_ops": int(rep.n_ops),
+                  "ns_device": int(rep.ns_device), "bytes_in": int(rep.bytes_in)}
+        try:
+            N.check_status(st)
+        except N.TbcError as e:
+            e.report = report
+            raise
+        if not hasattr(self, "_pending_n"):
+            self._pending_n = []
+        self._pending_n.append(int(n_hist))
+        return report
+
+    def stream_events(self, events):
+        """Event histories (columns.EventColumns) into the batch by the packed route: each history is packed by tbc_pack_events
+        straight into the views of an event slot (no intermediate columns), then submit_events.  Event slots 0 and 1 in turn.
+        Raises as reload_events does on a refused history.  pack_s, submit_s and events_report are left on the object for whoever
+        measures."""
+        from .columns import pack_events
+        import time as _time
+        slot = getattr(self, "_stream_slot", 0) & 1
+        m = self.map_events(slot)
+        nh = len(events)
+        if nh > m["n_hist_cap"]:
+            raise ValueError(f"{nh} histories, the batch's slots hold {m['n_hist_cap']}")
+        t0 = _time.perf_counter()
+        ev_off, at = m["ev_off"], 0
+        ev_off[0] = 0
+        for h, e in enumerate(events):
+            n = len(e)
+            if at + n > m["events_cap"]:
+                raise ValueError(f"more than {m['events_cap']} events, which is what the batch's event slots hold")
+            pack_events(e, out=m["ev_word"][at:at + n])
+            m["process"][at:at + n] = e.process
+            at += n
+            ev_off[h + 1] = at
+        self.pack_s = _time.perf_counter() - t0
+        t0 = _time.perf_counter()
+        try:
+            self.events_report = self.submit_events(slot, nh)
+        finally:
+            self.submit_s = _time.perf_counter() - t0
+        self._stream_slot = getattr(self, "_stream_slot", 0) + 1
+        return self
+
     def input_info(self):
         i = N.InputInfo()
         N.check_status(N.lib().tbc_batch_input_info(self._h, C.byref(i)))

@@ -460,6 +460,7 @@ void tbc_batch::count_device_bytes() {
                                B->d_crashed.bytes() + B->d_slot8.bytes() + B->d_rk8.bytes() + B->d_twn.bytes() + B->d_rdm.bytes() + B->d_look.bytes() + B->d_looktmp.bytes() + B->d_dstack.bytes() + B->d_stack.bytes() + B->d_btab.bytes() + B->d_pool.bytes() + B->d_cmem.bytes();
   if (B->d_stage[0].p) B->device_bytes += B->d_stage[0].bytes();
   if (B->d_stage[1].p) B->device_bytes += B->d_stage[1].bytes();
+  if (B->d_events.p) B->device_bytes += B->d_events.bytes();
 }
 
 tbc_batch::~tbc_batch() {

@@ -1,5 +1,5 @@
 // batch_stream.hip -- FRESH INPUTS into a batch's arenas (include/tbcheck.h, "streaming": tbc_batch_map_input, tbc_batch_submit_input,
-// tbc_batch_reload, tbc_batch_input_info).
+// tbc_batch_reload, tbc_batch_input_info; tbc_batch_map_events, tbc_batch_submit_events).
 //
 // The reference calls a checker once per history (/root/reference/src/tigerbeetle/core.clj:139-146: checker/compose over the test's ONE
 // history; workloads/set_full.clj:155-158: independent/checker, once per key): a caller that checks many histories never checks one
@@ -26,6 +26,12 @@
 //     submitted (plan_count_input: batch_create.hip's build_count_form over the wire columns, on up to 16 threads; the words with
 //     the slot numbers go to a pinned copy, which is what travels), the class records go up beside the wire columns, and since such a batch has no sequential
 //     fallback for lists that outgrow their arena, the lists' lengths are counted on the host as well and the arena grown before the run.
+//   * EVENTS (tbc_batch_map_events / tbc_batch_submit_events): event histories, which is what the reference produces, go in packed
+//     (8 B an event: TBC_EVENT_WORD + process) through a second set of pinned slots, are paired on the copy stream by the kernels of
+//     tbc_pair_events_batch in the batch's own event arena (pair_plan.h plan_batch, allocated once), and the wire columns are emitted
+//     straight into the device stage: nothing but the descriptors, 24 B a history, comes back.  From the descriptors on such an input
+//     is laid out by the function tbc_batch_submit_input lays its own out with (layout_input).  Not for a count-form batch, whose
+//     planning reads the wire words on the host.
 // What it does not take (TBC_ERR_UNSUPPORTED: destroy and create): batches of the level sweep (a count-form batch of <= 8 histories has
 // the relaxed sweep beside it), set / bank / multi-register / table models, batches of tbc_check's persistent contexts.
 #include "tbc_batch.h"
@@ -254,6 +260,11 @@ void stream_release(tbc_batch* B) {
     if (sl.planned) (void)hipHostFree(sl.planned);
   }
   B->in_slots.clear();
+  for (auto& sl : B->ev_slots) {
+    if (sl.copied) { (void)hipEventSynchronize(sl.copied); (void)hipEventDestroy(sl.copied); }
+    if (sl.mem) (void)hipHostFree(sl.mem);
+  }
+  B->ev_slots.clear();
   if (B->stream_copy) { (void)hipStreamSynchronize(B->stream_copy); (void)hipStreamDestroy(B->stream_copy); B->stream_copy = nullptr; }
   for (int i = 0; i < 2; i++) {
     if (B->ev_stage[i]) (void)hipEventDestroy(B->ev_stage[i]);
@@ -262,6 +273,8 @@ void stream_release(tbc_batch* B) {
     if (B->ev_copy[i][1]) (void)hipEventDestroy(B->ev_copy[i][1]);
     B->d_stage[i].release();
   }
+  for (hipEvent_t& e : B->ev_pair) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+  B->d_events.release();
   B->d_in_flags.release(); B->d_list_over.release();
   if (B->in_flags_host) { (void)hipHostFree(B->in_flags_host); B->in_flags_host = nullptr; }
 }
@@ -316,7 +329,7 @@ tbc_status stream_consume(tbc_batch* B, bool* consumed) {
   HIP_TRY(hipStreamSynchronize(s));          // (the pack must not run over an input the batch cannot take: its crashed-call arena may not exist)
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, B->ev_copy[P.stage][0], B->ev_copy[P.stage][1]) == hipSuccess) B->in_copy_ns = (uint64_t)(ms * 1e6);
-  B->in_bytes_copied = T * 12ull;
+  B->in_bytes_copied = P.bytes_copied ? P.bytes_copied : T * 12ull;
   const uint32_t flags = B->in_flags_host[0];
   if (flags) {
     set_error("the submitted input does not fit this batch's layout decisions (%s%s%s): destroy and create the batch from it",
@@ -392,6 +405,175 @@ tbc_status tbc_batch_map_input(tbc_batch* b, uint32_t slot, tbc_batch_input* out
   catch (...) { set_error("unexpected exception"); return TBC_ERR_HIP; }
 }
 
+namespace tbc {
+namespace {
+
+// What an input's descriptors decide, whichever way its wire columns reach the stage: the process slots against the batch's mask words,
+// the layout of its histories (P.hist, P.bh, P.tot), the limits of several histories per wavefront.  n_slots: n_process, or a
+// count-form batch's re-used slots.
+tbc_status layout_input(tbc_batch* b, uint32_t n_hist, const uint64_t* op_off, const uint32_t* n_events, const uint32_t* n_slots, tbc_pending_input& P) {
+  uint32_t max_slots = 1;
+  uint64_t longest = 0;
+  for (uint32_t h = 0; h < n_hist; h++) {
+    max_slots = std::max(max_slots, n_slots[h]);
+    longest = std::max<uint64_t>(longest, op_off[h + 1] - op_off[h]);
+  }
+  if (max_slots > 64u * b->mask_words || max_slots > 4096u) {
+    set_error("the input has a history of %u process slots, the batch's kernels were chosen for at most %u: destroy and create", max_slots, 64u * b->mask_words);
+    return TBC_ERR_UNSUPPORTED;
+  }
+  const tbc_status st = layout_histories(b, n_hist, op_off, n_events, n_slots, nullptr, nullptr, true, P.hist, P.bh, P.tot, b->count_form ? &P.count_hist : nullptr);
+  if (st != TBC_OK) return st;
+  P.max_ops = P.tot.max_ops;
+  if (b->lanes && (longest >= kNarrowMaxOps || P.tot.boff_n >= (1ull << 32) || look_words(P.total_ops, b->in_hist_cap, b->mask_words) >= (1ull << 32))) {
+    set_error("the input exceeds what several histories per wavefront address (2^24 - 16 ops a history, 2^32 fronts a batch): destroy and create");
+    return TBC_ERR_UNSUPPORTED;
+  }
+  return TBC_OK;
+}
+
+// an event slot: [ev_off][the descriptors that come back: acc, op_off, n_events, n_process, status, bad_row][ev_word][process]
+struct EventSlotView {
+  tbc_batch_events in;
+  pr::PrAcc* acc; uint64_t* op_off; uint32_t *n_events, *n_process; int32_t* status; uint32_t* bad_row;
+};
+size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
+size_t event_slot_bytes(const tbc_batch* B) {
+  return al256((size_t)(B->in_hist_cap + 1) * 8) * 2 + 256 + 4 * al256((size_t)B->in_hist_cap * 4) + 2 * al256((size_t)B->events_cap * 4);
+}
+EventSlotView event_slot_view(const tbc_batch* B, char* mem) {
+  const size_t a = al256((size_t)(B->in_hist_cap + 1) * 8), b = al256((size_t)B->in_hist_cap * 4);
+  EventSlotView v{};
+  v.in.n_hist_cap = B->in_hist_cap; v.in.reserved0 = 0; v.in.events_cap = B->events_cap;
+  v.in.ev_off = (uint64_t*)mem;
+  v.acc = (pr::PrAcc*)(mem + a);
+  v.op_off = (uint64_t*)(mem + a + 256);
+  char* d = mem + 2 * a + 256;
+  v.n_events = (uint32_t*)d; v.n_process = (uint32_t*)(d + b); v.status = (int32_t*)(d + 2 * b); v.bad_row = (uint32_t*)(d + 3 * b);
+  v.in.ev_word = (uint32_t*)(d + 4 * b);
+  v.in.process = (int32_t*)(d + 4 * b + al256((size_t)B->events_cap * 4));
+  return v;
+}
+
+const char* kCountFormEvents = "a count-form batch plans its crashed calls on the host from the wire words, which events paired into the device stage never "
+                               "bring there: pair with tbc_pair_events_batch into a mapped op slot (tbc_batch_map_input) and call tbc_batch_submit_input";
+
+}  // namespace
+}  // namespace tbc
+
+tbc_status tbc_batch_map_events(tbc_batch* b, uint32_t slot, uint64_t events_cap, tbc_batch_events* out) {
+  if (!b || !out) { set_error("tbc_batch_map_events: null argument"); return TBC_ERR_INVALID_ARG; }
+  if (slot >= kMaxInputSlots) { set_error("tbc_batch_map_events: slot %u (at most %u slots)", slot, kMaxInputSlots); return TBC_ERR_INVALID_ARG; }
+  try {
+    tbc_status s = ensure_stream(b);
+    if (s != TBC_OK) return s;
+    if (b->count_form) { set_error("tbc_batch_map_events: %s", kCountFormEvents); return TBC_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->d_events.p) {          // the first mapping: events_cap for the batch, the device event arena, the events of the pairing
+      const uint64_t cap = events_cap ? events_cap : 3ull * b->in_ops_cap;
+      if (cap > 0xFFFFFFFFull) { set_error("tbc_batch_map_events: %llu events, a call pairs 2^32 - 1 at most", (unsigned long long)cap); return TBC_ERR_INVALID_ARG; }
+      pr::plan_batch(b->in_hist_cap, cap, b->in_ops_cap, b->ev_plan);
+      if ((s = b->d_events.alloc(b->ev_plan.arena.bytes)) != TBC_OK) return s;
+      b->events_cap = cap;
+      HIP_TRY(hipEventCreate(&b->ev_pair[0])); HIP_TRY(hipEventCreate(&b->ev_pair[1]));
+      HIP_TRY(hipEventCreateWithFlags(&b->ev_pair[2], hipEventDisableTiming));
+      b->count_device_bytes();
+    } else if (events_cap > b->events_cap) {
+      set_error("tbc_batch_map_events: %llu events asked for, the batch's first mapping fixed %llu", (unsigned long long)events_cap, (unsigned long long)b->events_cap);
+      return TBC_ERR_INVALID_ARG;
+    }
+    if (b->ev_slots.size() <= slot) b->ev_slots.resize(slot + 1);
+    tbc_batch::EventSlot& sl = b->ev_slots[slot];
+    if (!sl.mem) {
+      const size_t bytes = event_slot_bytes(b);
+      HIP_TRY(hipHostMalloc((void**)&sl.mem, bytes, hipHostMallocDefault));
+      sl.bytes = bytes;
+      HIP_TRY(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
+    }
+    if (sl.busy) { HIP_TRY(hipEventSynchronize(sl.copied)); sl.busy = false; }      // its last events are on the device: the caller may write again
+    *out = event_slot_view(b, sl.mem).in;
+    return TBC_OK;
+  } catch (const std::bad_alloc&) { set_error("host allocation failed"); return TBC_ERR_OOM; }
+  catch (...) { set_error("unexpected exception"); return TBC_ERR_HIP; }
+}
+
+tbc_status tbc_batch_submit_events(tbc_batch* b, uint32_t slot, uint32_t n_hist, tbc_events_report* rep) {
+  const char* fn = "tbc_batch_submit_events";
+  if (!b) { set_error("%s: null batch", fn); return TBC_ERR_INVALID_ARG; }
+  if (b->count_form) { set_error("%s: %s", fn, kCountFormEvents); return TBC_ERR_UNSUPPORTED; }
+  if (!b->stream_copy || slot >= b->ev_slots.size() || !b->ev_slots[slot].mem) { set_error("%s: slot %u was never mapped (tbc_batch_map_events)", fn, slot); return TBC_ERR_INVALID_ARG; }
+  if (n_hist == 0 || n_hist > b->in_hist_cap) { set_error("%s: %u histories, the batch holds 1..%u", fn, n_hist, b->in_hist_cap); return TBC_ERR_INVALID_ARG; }
+  if (b->pending.size() >= 2) { set_error("%s: two inputs are waiting already -- tbc_batch_run consumes one", fn); return TBC_ERR_INVALID_ARG; }
+  try {
+    HIP_TRY(hipSetDevice(b->device));
+    tbc_batch::EventSlot& sl = b->ev_slots[slot];
+    if (sl.busy) { set_error("%s: slot %u is still being copied (map it again before it is re-filled)", fn, slot); return TBC_ERR_INVALID_ARG; }
+    const EventSlotView v = event_slot_view(b, sl.mem);
+    std::string err;
+    tbc_status st = pr::validate_offsets(fn, n_hist, v.in.ev_off, nullptr, err);
+    if (st != TBC_OK) { set_error("%s", err.c_str()); return st; }
+    const uint64_t n = v.in.ev_off[n_hist];
+    if (n > b->events_cap) { set_error("%s: %llu events, a slot holds %llu", fn, (unsigned long long)n, (unsigned long long)b->events_cap); return TBC_ERR_INVALID_ARG; }
+    tbc_pending_input P;
+    P.slot = slot; P.stage = (uint32_t)(b->in_seq & 1u); P.n_hist = n_hist;
+    DevBuf<uint32_t>& stage = b->d_stage[P.stage];
+    if (!stage.p && (st = stage.alloc(3 * b->in_ops_cap)) != TBC_OK) return st;
+    // ---- up, paired, the descriptors back: all on the copy stream
+    const pr::PrArena& L = b->ev_plan.arena;
+    char* base = (char*)b->d_events.p;
+    const pr::PrArgs A = pr::args_stage(b->ev_plan, n_hist, base, stage.p);
+    hipStream_t sc = b->stream_copy;
+    const size_t nh = n_hist;
+    HIP_TRY(hipEventRecord(b->ev_copy[P.stage][0], sc));
+    HIP_TRY(hipMemcpyAsync(base + L.ev_off.at, v.in.ev_off, (nh + 1) * 8, hipMemcpyHostToDevice, sc));
+    if (n) {
+      HIP_TRY(hipMemcpyAsync(base + L.ev_word.at, v.in.ev_word, (size_t)n * 4, hipMemcpyHostToDevice, sc));
+      HIP_TRY(hipMemcpyAsync(base + L.process.at, v.in.process, (size_t)n * 4, hipMemcpyHostToDevice, sc));
+    }
+    HIP_TRY(hipEventRecord(b->ev_copy[P.stage][1], sc));
+    HIP_TRY(hipMemsetAsync(base + L.acc.at, 0, L.acc.bytes, sc));
+    if (n) HIP_TRY(hipMemsetAsync(base + L.comp_of.at, 0xFF, (size_t)n * 4, sc));
+    HIP_TRY(hipEventRecord(b->ev_pair[0], sc));
+    pr::launch_pair(sc, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->ev_pair[1], sc));
+    HIP_TRY(hipMemcpyAsync(v.acc, base + L.acc.at, sizeof(pr::PrAcc), hipMemcpyDeviceToHost, sc));
+    HIP_TRY(hipMemcpyAsync(v.op_off, base + L.op_off.at, (nh + 1) * 8, hipMemcpyDeviceToHost, sc));
+    HIP_TRY(hipMemcpyAsync(v.n_events, base + L.n_events.at, nh * 4, hipMemcpyDeviceToHost, sc));
+    HIP_TRY(hipMemcpyAsync(v.n_process, base + L.n_process.at, nh * 4, hipMemcpyDeviceToHost, sc));
+    HIP_TRY(hipMemcpyAsync(v.status, base + L.status.at, nh * 4, hipMemcpyDeviceToHost, sc));
+    HIP_TRY(hipMemcpyAsync(v.bad_row, base + L.bad_row.at, nh * 4, hipMemcpyDeviceToHost, sc));
+    HIP_TRY(hipEventRecord(b->ev_pair[2], sc));
+    HIP_TRY(hipEventSynchronize(b->ev_pair[2]));          // (that event only: whatever the compute stream is doing goes on)
+    const uint64_t up = (uint64_t)n * 8 + (nh + 1) * 8;
+    if (rep) {
+      float ms = 0.f;
+      if (rep->status) std::memcpy(rep->status, v.status, nh * 4);
+      if (rep->bad_row) std::memcpy(rep->bad_row, v.bad_row, nh * 4);
+      rep->n_bad = v.acc->n_bad; rep->reserved0 = 0; rep->n_ops = v.acc->total_ops;
+      rep->ns_device = hipEventElapsedTime(&ms, b->ev_pair[0], b->ev_pair[1]) == hipSuccess ? (uint64_t)(ms * 1e6) : 0;
+      rep->bytes_in = up;
+    }
+    // ---- all or nothing: so far nothing is pending, in_seq stands, no stage has been written
+    if ((st = pr::batch_refusal(fn, n_hist, *v.acc, v.status, v.bad_row, b->in_ops_cap, err)) != TBC_OK) { set_error("%s", err.c_str()); return st; }
+    P.total_ops = v.acc->total_ops;
+    P.bytes_copied = up + TBC_EVENTS_DESC_BYTES(n_hist);
+    if ((st = layout_input(b, n_hist, v.op_off, v.n_events, v.n_process, P)) != TBC_OK) return st;
+    // ---- the wire columns into the stage, once its previous occupant has been unpacked
+    if (b->stage_used[P.stage]) HIP_TRY(hipStreamWaitEvent(sc, b->ev_unpacked[P.stage], 0));
+    b->stage_used[P.stage] = true;
+    pr::launch_emit(sc, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->ev_stage[P.stage], sc));
+    HIP_TRY(hipEventRecord(sl.copied, sc));
+    sl.busy = true;
+    b->in_seq++;
+    b->pending.push_back(std::move(P));
+    return TBC_OK;
+  } catch (const std::bad_alloc&) { set_error("host allocation failed"); return TBC_ERR_OOM; }
+  catch (...) { set_error("unexpected exception"); return TBC_ERR_HIP; }
+}
+
 tbc_status tbc_batch_submit_input(tbc_batch* b, uint32_t slot, uint32_t n_hist) {
   if (!b) { set_error("tbc_batch_submit_input: null batch"); return TBC_ERR_INVALID_ARG; }
   if (!b->stream_copy || slot >= b->in_slots.size() || !b->in_slots[slot].mem) { set_error("tbc_batch_submit_input: slot %u was never mapped (tbc_batch_map_input)", slot); return TBC_ERR_INVALID_ARG; }
@@ -404,13 +586,8 @@ tbc_status tbc_batch_submit_input(tbc_batch* b, uint32_t slot, uint32_t n_hist) 
     tbc_batch_input in;
     slot_pointers(b, sl.mem, &in);
     if (in.op_off[0] != 0) { set_error("op_off[0] must be 0"); return TBC_ERR_INVALID_ARG; }
-    uint32_t max_slots = 1;
-    uint64_t longest = 0;
-    for (uint32_t h = 0; h < n_hist; h++) {
+    for (uint32_t h = 0; h < n_hist; h++)
       if (in.op_off[h + 1] < in.op_off[h] || in.op_off[h + 1] - in.op_off[h] > 0x7FFFFFFFull) { set_error("history %u: bad op_off", h); return TBC_ERR_INVALID_ARG; }
-      max_slots = std::max(max_slots, in.n_process[h]);
-      longest = std::max<uint64_t>(longest, in.op_off[h + 1] - in.op_off[h]);
-    }
     const uint64_t T = in.op_off[n_hist];
     if (T > b->in_ops_cap) { set_error("tbc_batch_submit_input: %llu ops, a slot holds %llu", (unsigned long long)T, (unsigned long long)b->in_ops_cap); return TBC_ERR_INVALID_ARG; }
     if (T > 0xFFFFFFFFull) { set_error("tbc_batch_submit_input: more than 2^32 - 1 ops"); return TBC_ERR_INVALID_ARG; }
@@ -421,21 +598,8 @@ tbc_status tbc_batch_submit_input(tbc_batch* b, uint32_t slot, uint32_t n_hist) 
     if (b->count_form) {          // the classes of crashed calls and the re-used process slots, planned here on the host
       if (!sl.planned) HIP_TRY(hipHostMalloc((void**)&sl.planned, (size_t)b->in_ops_cap * 4, hipHostMallocDefault));
       if ((st = plan_count_input(b, in, sl.planned, n_hist, P, count_slots)) != TBC_OK) return st;
-      max_slots = 1;
-      for (uint32_t h = 0; h < n_hist; h++) max_slots = std::max(max_slots, count_slots[h]);
     }
-    if (max_slots > 64u * b->mask_words || max_slots > 4096u) {
-      set_error("the input has a history of %u process slots, the batch's kernels were chosen for at most %u: destroy and create", max_slots, 64u * b->mask_words);
-      return TBC_ERR_UNSUPPORTED;
-    }
-    st = layout_histories(b, n_hist, in.op_off, in.n_events, b->count_form ? count_slots.data() : in.n_process, nullptr, nullptr, true, P.hist, P.bh, P.tot,
-                          b->count_form ? &P.count_hist : nullptr);
-    if (st != TBC_OK) return st;
-    P.max_ops = P.tot.max_ops;
-    if (b->lanes && (longest >= kNarrowMaxOps || P.tot.boff_n >= (1ull << 32) || look_words(T, b->in_hist_cap, b->mask_words) >= (1ull << 32))) {
-      set_error("the input exceeds what several histories per wavefront address (2^24 - 16 ops a history, 2^32 fronts a batch): destroy and create");
-      return TBC_ERR_UNSUPPORTED;
-    }
+    if ((st = layout_input(b, n_hist, in.op_off, in.n_events, b->count_form ? count_slots.data() : in.n_process, P)) != TBC_OK) return st;
     DevBuf<uint32_t>& stage = b->d_stage[P.stage];
     if (!stage.p && (st = stage.alloc(3 * b->in_ops_cap)) != TBC_OK) return st;
     hipStream_t sc = b->stream_copy;

@@ -1,4 +1,5 @@
-// pair_host.hip -- tbc_pair_events_batch, the entry point of the pairing on the device (include/tbcheck.h), over the call frame of
+// pair_host.hip -- tbc_pair_events_batch and tbc_pair_packed_batch (the same call over packed events: 8 B a row), the entry points
+// of the pairing on the device (include/tbcheck.h), over the call frame of
 // oneshot_call.h: every rule of the arguments on the host (before the device is looked for), the plan, the frame, and the steps of the
 // call as pr::steps states them (pair_plan.h), the kernels those of pair.hip on the frame's stream.
 #include <string>
@@ -9,7 +10,8 @@ using namespace tbc;
 
 namespace {
 
-tbc_status pr_batch(const char* fn, const tbc_event_batch* in, tbc_pair_out* out) {
+template <class In>
+tbc_status pr_batch(const char* fn, const In* in, tbc_pair_out* out) {
   std::string err;
   const tbc_status st = pr::validate(fn, in, out, err);
   if (st != TBC_OK) { set_error("%s", err.c_str()); return st; }
@@ -28,5 +30,9 @@ tbc_status pr_batch(const char* fn, const tbc_event_batch* in, tbc_pair_out* out
 }  // namespace
 
 extern "C" tbc_status tbc_pair_events_batch(const tbc_event_batch* in, tbc_pair_out* out) {
-  return oneshot_entry("tbc_pair_events_batch", in, out, pr_batch);
+  return oneshot_entry("tbc_pair_events_batch", in, out, pr_batch<tbc_event_batch>);
+}
+
+extern "C" tbc_status tbc_pair_packed_batch(const tbc_packed_event_batch* in, tbc_pair_out* out) {
+  return oneshot_entry("tbc_pair_packed_batch", in, out, pr_batch<tbc_packed_event_batch>);
 }

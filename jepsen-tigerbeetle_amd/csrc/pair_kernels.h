@@ -36,6 +36,14 @@
 // shuffle are plain HIP, which tests/emu/oneshot_emu.h and tests/emu/emu_pair.cpp state for the host emulator -- these very kernels
 // run there lane by lane against tbc_pair_events (tests/test_pair_events_emu.py).  PR_MUTATION (1: a slot's carried state is not
 // stored from lane 63; 2: dense numbers by first appearance among ALL invocations) exists for that test alone, which must see both.
+//
+// THE PACKED READER.  With PrArgs.ev_word set (a wavefront-uniform choice; tbc_pair_packed_batch, tbc_batch_submit_events) an event's
+// type, f, a and b are the fields of its TBC_EVENT_WORD (include/tbcheck.h), one 4 B load where the columns take up to four; the
+// process column is read as it is.  Pass A reads the word for the type; pass B reads the invocation's word once (its type, its f)
+// and the completion's word for the completion's type; the wire check and the emit kernel read the word of the row whose values
+// count.  The codes 7 / 16 / 256 decode to themselves -- an unknown type, an :f above 15, a value the wire format does not hold
+// -- so every rule below decides as it does over the columns.  Null: the column loads are what they were.  PR_MUTATION 3 (the
+// completion's type read from the INVOCATION's word) exists for tests/test_packed_events_emu.py alone.
 #pragma once
 #include "wave_env_wg.h"
 #include "pair_plan.h"
@@ -91,7 +99,7 @@ __global__ __launch_bounds__(64) void pr_pair_kernel(PrArgs A) {
       const uint32_t i = base + lane;
       const bool in = i < n;
       uint32_t ty = 0, k = 0;
-      if (in) { ty = A.type[e0 + i]; k = (uint32_t)A.process[e0 + i]; }
+      if (in) { ty = A.ev_word ? TBC_EVW_TYPE(A.ev_word[e0 + i]) : (uint32_t)A.type[e0 + i]; k = (uint32_t)A.process[e0 + i]; }
       const bool known = in && ty <= TBC_INFO;
       bool fresh = false;
       const uint32_t slot = known ? pr_slot(s_key, k, true, fresh) : 0u;
@@ -133,12 +141,18 @@ __global__ __launch_bounds__(64) void pr_pair_kernel(PrArgs A) {
       bool wire_bad = false;
       for (uint32_t base = 0; base < n; base += 64u) {
         const uint32_t i = base + lane;
-        const bool inv = i < n && A.type[e0 + i] == TBC_INVOKE;
+        uint32_t wi = 0;                                                    // (packed) this row's word
+        if (A.ev_word && i < n) wi = A.ev_word[e0 + i];
+        const bool inv = i < n && (A.ev_word ? TBC_EVW_TYPE(wi) : (uint32_t)A.type[e0 + i]) == TBC_INVOKE;
         uint32_t c = pr::kPrNone, cty = TBC_INVOKE, slot = 0;
         if (inv) {
           bool fresh;
           c = A.comp_of[e0 + i];
-          if (c != pr::kPrNone) cty = A.type[e0 + c];
+#if defined(PR_MUTATION) && PR_MUTATION == 3
+          if (c != pr::kPrNone) cty = A.ev_word ? TBC_EVW_TYPE(wi) : (uint32_t)A.type[e0 + c];
+#else
+          if (c != pr::kPrNone) cty = A.ev_word ? TBC_EVW_TYPE(A.ev_word[e0 + c]) : (uint32_t)A.type[e0 + c];
+#endif
           slot = pr_slot(s_key, (uint32_t)A.process[e0 + i], false, fresh);
           if (slot > pr::kPrTable) slot = pr::kPrTable;                     // (pass A entered every id: never)
         }
@@ -165,8 +179,14 @@ __global__ __launch_bounds__(64) void pr_pair_kernel(PrArgs A) {
           bool unfit = false;
           if (survives) {
             const unsigned long long v = e0 + (ret != TBC_POS_CRASHED ? ret : i);
-            const uint32_t f = A.f[e0 + i];
-            const int32_t a = A.a[v], b = A.b[v];
+            uint32_t f;
+            int32_t a, b;
+            if (A.ev_word) {
+              const uint32_t wv_ = ret != TBC_POS_CRASHED ? A.ev_word[v] : wi;
+              f = TBC_EVW_F(wi); a = TBC_EVW_VALUE(TBC_EVW_A(wv_)); b = TBC_EVW_VALUE(TBC_EVW_B(wv_));
+            } else {
+              f = A.f[e0 + i]; a = A.a[v]; b = A.b[v];
+            }
             const bool a_ok = a == TBC_NIL || (a >= 0 && a <= 254), b_ok = b == TBC_NIL || (b >= 0 && b <= 254);
             unfit = f > 15u || !a_ok || (f == TBC_F_CAS && !b_ok);
           }
@@ -218,8 +238,14 @@ __global__ __launch_bounds__(64) void pr_emit_kernel(PrArgs A) {
       if (o >= A.out_cap) continue;                                         // (the host has held the total against the capacity: never)
       const uint32_t inv = A.s_inv[e0 + k], ret = A.s_ret[e0 + k], proc = A.s_proc[e0 + k];
       const unsigned long long v = e0 + (ret != TBC_POS_CRASHED ? ret : inv);   // an :ok completion's values replace the invocation's
-      const uint32_t f = A.f[e0 + inv];
-      const int32_t a = A.a[v], b = A.b[v];
+      uint32_t f;
+      int32_t a, b;
+      if (A.ev_word) {                                                      // (uniform)
+        const uint32_t wv_ = A.ev_word[v];
+        f = TBC_EVW_F(ret != TBC_POS_CRASHED ? A.ev_word[e0 + inv] : wv_); a = TBC_EVW_VALUE(TBC_EVW_A(wv_)); b = TBC_EVW_VALUE(TBC_EVW_B(wv_));
+      } else {
+        f = A.f[e0 + inv]; a = A.a[v]; b = A.b[v];
+      }
       if (A.o_f) A.o_f[o] = (uint8_t)f;
       if (A.o_a) A.o_a[o] = a;
       if (A.o_b) A.o_b[o] = b;

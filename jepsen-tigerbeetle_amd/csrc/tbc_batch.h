@@ -22,6 +22,7 @@
 #include <vector>
 #include "tbc_internal.h"
 #include "pool_plan.h"
+#include "pair_plan.h"
 
 namespace tbc {
 
@@ -188,6 +189,7 @@ struct tbc_pending_input {
   std::vector<tbc::CountHist> count_hist;
   std::vector<uint64_t> cmem;         // ... their records and members, all histories back to back (what goes to BeamArgs.cmem)
   uint64_t lst_total = 0;             // ... and how many entries its per-front lists hold (a count-form batch has no fallback for lists that do not fit)
+  uint64_t bytes_copied = 0;          // what crossed PCIe for it, if that is not 12 B an op: an input of events (tbc_batch_submit_events)
 };
 
 struct tbc_batch {
@@ -348,6 +350,15 @@ struct tbc_batch {
   bool inputs_stale = false;                // the last submitted input was refused: nothing resident to run until the next one
   uint64_t inputs_consumed = 0;
   uint32_t lists_regrown = 0, reload_slot = 0;
+  // ---- events into the batch (tbc_batch_map_events / tbc_batch_submit_events): a second set of pinned slots -- [ev_off][ev_word]
+  // [process] and a corner for the descriptors that come back -- and ONE device event arena (pair_plan.h plan_batch), made by the
+  // first mapping and kept; the pairing kernels run on stream_copy and emit the wire columns into d_stage
+  struct EventSlot { char* mem = nullptr; size_t bytes = 0; hipEvent_t copied = nullptr; bool busy = false; };
+  std::vector<EventSlot> ev_slots;
+  uint64_t events_cap = 0;                  // events a slot (and the arena) holds: fixed by the first mapping
+  pr::Plan ev_plan;
+  tbc::DevBuf<unsigned char> d_events;
+  hipEvent_t ev_pair[3] = {};               // the pairing kernels begin / end (timing); the descriptors have arrived
 
   bool borrowed = false;            // stream and events belong to a persistent context (tbc_check)
   ~tbc_batch();

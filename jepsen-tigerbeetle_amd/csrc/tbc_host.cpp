@@ -121,6 +121,20 @@ tbc_status tbc_pair_events(const tbc_events* ev, uint8_t* f, int32_t* a, int32_t
   return TBC_OK;
 }
 
+// one history's event columns -> packed event words (include/tbcheck.h, "the packed event word"); the process column is not touched
+tbc_status tbc_pack_events(const tbc_events* ev, uint32_t* ev_word) {
+  if (!ev || (ev->n && (!ev_word || !ev->type || !ev->f || !ev->a || !ev->b))) {
+    tbc::set_error("tbc_pack_events: null argument");
+    return TBC_ERR_INVALID_ARG;
+  }
+  const auto value = [](int32_t v) { return v == TBC_NIL ? TBC_EVW_NIL : (v >= 0 && v <= 254 ? (uint32_t)v : TBC_EVW_UNFIT); };
+  for (uint32_t i = 0; i < ev->n; i++) {
+    const uint32_t ty = ev->type[i] <= TBC_INFO ? ev->type[i] : TBC_EVW_TYPE_UNKNOWN, f = ev->f[i] <= 15u ? ev->f[i] : TBC_EVW_F_ABOVE;
+    ev_word[i] = TBC_EVENT_WORD(ty, f, value(ev->a[i]), value(ev->b[i]));
+  }
+  return TBC_OK;
+}
+
 // Composition of the level sweep's relations (jit_sweep.hip): the live set is a set of origin ids (<= 128) of the
 // current segment; every slice that holds a live origin contributes the next segment's ids its live origins reach.
 tbc_status tbc_sweep_compose(const tbc_sweep_rel* rel, uint32_t max_segs, uint32_t n_completions, tbc_sweep_verdict* out) {
