@@ -392,6 +392,110 @@
            :statuses (mapv #(.getInt status (* 4 %)) (range nh))
            :bad-rows (mapv #(Integer/toUnsignedLong (.getInt bad (* 4 %))) (range nh))})))))
 
+;; One keyed history (additive, ABI version 2): tbc_pair_keyed_events.  A run under jepsen.independent leaves ONE history whose values
+;; are [k v] tuples; its columns (`columns` over the ops with the tuple stripped) and one int32 key per row go up as they are, the
+;; device splits the rows by key (keys in order of first appearance, a stable split) and pairs every key's rows in the same call.  Rows
+;; that belong to every key (nemesis ops, values that are no tuple) are left out by the caller.  The structs have a table of their own,
+;; held against the ctypes binding by tests/test_keyed_events_shim.py.
+(def keyed-abi
+  {:keyed_events {:size 64 :n 0 :device 4 :key 8 :ev_word 16 :process 24 :type 32 :f 40 :a 48 :b 56}
+   :split_out    {:size 32 :keys_cap 0 :n_keys 4 :keys 8 :ev_off 16 :row_of 24}
+   :batch_keyed_events {:size 40 :n_hist_cap 0 :reserved0 4 :events_cap 8 :key 16 :ev_word 24 :process 32}
+   :keyed_report {:size 72 :status 0 :bad_row 8 :n_bad 16 :reserved0 20 :n_ops 24 :ns_device 32 :bytes_in 40 :n_keys 48 :reserved1 52
+                  :keys 56 :row_of 64}})
+
+(defn- ko
+  "Byte offset of field k of struct s of keyed-abi (or its :size)."
+  ^long [s k]
+  (long (get-in keyed-abi [s k])))
+
+(defn pair-keyed-events
+  "tbc_pair_keyed_events: the `columns` of ONE history and `keys` (a Memory of (:n cols) ints, the key of every row) ->
+   {:keys [k ...] in order of first appearance, :row-of (a Memory: the original row of every split row, key after key), :ev-off [...],
+    :histories [per key what pair-events-batch gives per history: the op columns as views into the call's, or {:status s :bad-row r}
+    with r a row WITHIN the key's rows]}.  Returns nil when the call itself fails.  18 B a row go up."
+  [cols ^Memory keys {:keys [device] :or {device 0}}]
+  (let [n      (long (:n cols))
+        cap    (max 1 n)
+        ks     (Memory. (* 4 cap)) ev-off (Memory. (* 8 (inc cap))) row-of (Memory. (* 4 cap))
+        op-off (Memory. (* 8 (inc cap))) n-ev (Memory. (* 4 cap)) n-pr (Memory. (* 4 cap))
+        status (Memory. (* 4 cap)) bad (Memory. (* 4 cap))
+        of     (Memory. cap) oa (Memory. (* 4 cap)) ob (Memory. (* 4 cap)) op* (Memory. (* 4 cap))
+        inv    (Memory. (* 4 cap)) ret (Memory. (* 4 cap))
+        in     (doto (Memory. (ko :keyed_events :size)) (.clear)
+                 (.setInt (ko :keyed_events :n) n) (.setInt (ko :keyed_events :device) device)
+                 (.setPointer (ko :keyed_events :key) keys) (.setPointer (ko :keyed_events :ev_word) Pointer/NULL)
+                 (.setPointer (ko :keyed_events :process) (:process cols)) (.setPointer (ko :keyed_events :type) (:type cols))
+                 (.setPointer (ko :keyed_events :f) (:f cols)) (.setPointer (ko :keyed_events :a) (:a cols))
+                 (.setPointer (ko :keyed_events :b) (:b cols)))
+        split  (doto (Memory. (ko :split_out :size)) (.clear)
+                 (.setInt (ko :split_out :keys_cap) n) (.setPointer (ko :split_out :keys) ks)
+                 (.setPointer (ko :split_out :ev_off) ev-off) (.setPointer (ko :split_out :row_of) row-of))
+        out    (doto (Memory. (po :pair_out :size)) (.clear)
+                 (.setLong (po :pair_out :ops_cap) n) (.setPointer (po :pair_out :op_off) op-off)
+                 (.setPointer (po :pair_out :n_events) n-ev) (.setPointer (po :pair_out :n_process) n-pr)
+                 (.setPointer (po :pair_out :f) of) (.setPointer (po :pair_out :a) oa) (.setPointer (po :pair_out :b) ob)
+                 (.setPointer (po :pair_out :process) op*) (.setPointer (po :pair_out :inv_pos) inv)
+                 (.setPointer (po :pair_out :ret_pos) ret) (.setPointer (po :pair_out :word) Pointer/NULL)
+                 (.setPointer (po :pair_out :status) status) (.setPointer (po :pair_out :bad_row) bad))
+        st     (keeping [cols keys ks ev-off row-of op-off n-ev n-pr status bad of oa ob op* inv ret in split out]
+                 (.invokeInt (f "tbc_pair_keyed_events") (to-array [in split out])))]
+    (when (zero? st)
+      (let [nk (.getInt split (ko :split_out :n_keys))]
+        {:keys   (mapv #(.getInt ks (* 4 %)) (range nk))
+         :ev-off (mapv #(.getLong ev-off (* 8 %)) (range (inc nk)))
+         :row-of row-of
+         :histories
+         (mapv (fn [h]
+                 (let [s (.getInt status (* 4 h))]
+                   (if-not (zero? s)
+                     {:status s :bad-row (Integer/toUnsignedLong (.getInt bad (* 4 h)))}
+                     (let [lo  (.getLong op-off (* 8 h))
+                           k   (- (.getLong op-off (* 8 (inc h))) lo)
+                           cut (fn [^Memory m width] (.share m (* width lo) (max 1 (* width k))))]
+                       {:n (.getInt n-ev (* 4 h)) :of (cut of 1) :oa (cut oa 4) :ob (cut ob 4) :oproc (cut op* 4) :inv (cut inv 4)
+                        :ret (cut ret 4) :n-ops (int k) :n-process (.getInt n-pr (* 4 h)) :pool-mem nil :pool-len 0}))))
+               (range nk))}))))
+
+(defn map-keyed-events
+  "tbc_batch_map_keyed_events: event slot `slot` of the batch `handle` for ONE keyed history -> {:n-hist-cap :events-cap :key :ev-word
+   :process} (Pointers into pinned memory the caller fills in place), or nil.  The slots are map-events' own; the first keyed mapping
+   adds the split's regions to the batch's device memory."
+  [handle slot events-cap]
+  (let [m (doto (Memory. (ko :batch_keyed_events :size)) (.clear))]
+    (when (zero? (keeping [m] (.invokeInt (f "tbc_batch_map_keyed_events") (to-array [handle (int slot) (long events-cap) m]))))
+      {:n-hist-cap (.getInt m (ko :batch_keyed_events :n_hist_cap)) :events-cap (.getLong m (ko :batch_keyed_events :events_cap))
+       :key (.getPointer m (ko :batch_keyed_events :key)) :ev-word (.getPointer m (ko :batch_keyed_events :ev_word))
+       :process (.getPointer m (ko :batch_keyed_events :process))})))
+
+(defn submit-keyed-events
+  "The `columns` of ONE history and `keys` (a Memory of (:n cols) ints, the key of every row) into event slot `slot` of the batch
+   `handle` and on to the device: packed in place (pack-events), the :process column and the keys copied beside, then
+   tbc_batch_submit_keyed_events -- split by key and paired on the device, the wire columns emitted into the batch's stage.  Returns
+   {:status s :n-keys :keys [k ...] :n-ops :n-bad :statuses :bad-rows} -- s zero: the input is pending, history h of the next
+   tbc_batch_run is key (nth keys h); otherwise nothing is pending and the batch is as it was -- or nil when the rows do not fit the slot."
+  [handle slot cols ^Memory keys]
+  (let [n (long (:n cols))]
+    (when-let [{:keys [n-hist-cap events-cap ^Pointer key ^Pointer ev-word ^Pointer process]} (map-keyed-events handle slot 0)]
+      (when (and (pos? n) (<= n events-cap))
+        (pack-events cols ev-word)
+        (.write process 0 (.getByteArray ^Memory (:process cols) 0 (int (* 4 n))) 0 (int (* 4 n)))
+        (.write key 0 (.getByteArray keys 0 (int (* 4 n))) 0 (int (* 4 n)))
+        (let [nh     (long n-hist-cap)
+              status (Memory. (* 4 nh)) bad (Memory. (* 4 nh)) ks (Memory. (* 4 nh))
+              rep    (doto (Memory. (ko :keyed_report :size)) (.clear)
+                       (.setPointer (ko :keyed_report :status) status) (.setPointer (ko :keyed_report :bad_row) bad)
+                       (.setPointer (ko :keyed_report :keys) ks) (.setPointer (ko :keyed_report :row_of) Pointer/NULL))
+              st     (keeping [cols keys status bad ks rep]
+                       (.invokeInt (f "tbc_batch_submit_keyed_events") (to-array [handle (int slot) (long n) rep])))
+              nk     (min nh (Integer/toUnsignedLong (.getInt rep (ko :keyed_report :n_keys))))]
+          {:status st :n-keys (Integer/toUnsignedLong (.getInt rep (ko :keyed_report :n_keys)))
+           :keys (mapv #(.getInt ks (* 4 %)) (range nk))
+           :n-ops (.getLong rep (ko :keyed_report :n_ops)) :n-bad (.getInt rep (ko :keyed_report :n_bad))
+           :ns-device (.getLong rep (ko :keyed_report :ns_device)) :bytes-in (.getLong rep (ko :keyed_report :bytes_in))
+           :statuses (mapv #(.getInt status (* 4 %)) (range nk))
+           :bad-rows (mapv #(Integer/toUnsignedLong (.getInt bad (* 4 %))) (range nk))})))))
+
 (defn- ops-struct ^Memory [{:keys [n n-ops n-process of oa ob oproc inv ret pool-mem pool-len]}]
   (doto (struct :ops)
     (.setInt (o :ops :n) n-ops) (.setInt (o :ops :n_events) n)

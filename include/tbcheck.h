@@ -47,7 +47,8 @@ extern "C" {
  * Still 2, additive: tbc_ledger_journal and its structs.
  * Still 2, additive: tbc_ledger_cycles and its structs.
  * Still 2, additive: tbc_pair_events_batch and its structs.
- * Still 2, additive: tbc_pack_events, tbc_pair_packed_batch, tbc_batch_map_events / _submit_events and their structs. */
+ * Still 2, additive: tbc_pack_events, tbc_pair_packed_batch, tbc_batch_map_events / _submit_events and their structs.
+ * Still 2, additive: tbc_pair_keyed_events, tbc_batch_map_keyed_events / _submit_keyed_events and their structs. */
 #define TBC_ABI_VERSION 2u
 
 /* ------------------------------------------------------------------ status */
@@ -1308,6 +1309,77 @@ typedef struct tbc_events_report { /* arrays caller-allocated, [n_hist]; each op
 
 tbc_status tbc_batch_map_events(tbc_batch* b, uint32_t slot, uint64_t events_cap, tbc_batch_events* out);
 tbc_status tbc_batch_submit_events(tbc_batch* b, uint32_t slot, uint32_t n_hist, tbc_events_report* rep);
+
+/* ------------------------------------------------------------------- one keyed history, split by key on the device
+ * A run under jepsen.independent leaves ONE event history whose values are [k v] tuples; the histories per key exist only after
+ * independent/subhistory.  tbc_pair_keyed_events takes that one history as it is -- the event columns (packed: ev_word + process,
+ * 8 B a row; or the five columns, 14 B) beside a key column, 4 B a row -- splits it by key on the device (csrc/split_*.h) and pairs
+ * every key's rows (the kernels of tbc_pair_events_batch, unchanged) in the same call; nothing returns to the host in between but the
+ * number of keys.  Rows that belong to every key (nemesis ops, values that are no tuple) are no client op of any key's object: the
+ * caller leaves them out.
+ *   keys[0 .. n_keys)       the distinct keys in order of FIRST APPEARANCE (every int32_t is a key)
+ *   ev_off[k], ev_off[k+1]  key k's rows in the split order; within a key the rows keep the order they had (a stable split)
+ *   row_of[j]               the original row of split row j (NULL: not wanted)
+ *   out                     the contract of tbc_pair_events_batch over n_keys histories, history h = keys[h]; inv_pos / ret_pos are rows
+ *                           within the key's rows; a malformed or unsupported key costs its own status[h].  NULL: split only.
+ * More distinct keys than keys_cap: TBC_ERR_INVALID_ARG, the count in tbc_last_error(), nothing written (decided before the rows are
+ * sorted); more surviving ops than out->ops_cap: as tbc_pair_events_batch, and the split is not written either.  Null arguments
+ * and more than 2^32 - 2 rows: TBC_ERR_INVALID_ARG before the device is looked for; valid input without a gfx950 device:
+ * TBC_ERR_NO_DEVICE.  n = 0: TBC_OK, n_keys = 0, ev_off[0] = 0.  out->bytes_in counts 12 B a row packed, 18 B in columns. */
+typedef struct tbc_keyed_events {      /* ONE history; ev_word non-null: the packed form, else the five columns */
+  uint32_t n, device;
+  const int32_t* key;                  /* [n] */
+  const uint32_t* ev_word; const int32_t* process;
+  const uint8_t* type; const uint8_t* f; const int32_t* a; const int32_t* b;
+} tbc_keyed_events;
+typedef struct tbc_split_out {         /* caller-allocated */
+  uint32_t keys_cap, n_keys;
+  int32_t* keys;                       /* [keys_cap] */
+  uint64_t* ev_off;                    /* [keys_cap + 1] */
+  uint32_t* row_of;                    /* [n], NULL = not wanted */
+} tbc_split_out;
+tbc_status tbc_pair_keyed_events(const tbc_keyed_events* in, tbc_split_out* split, tbc_pair_out* out);
+
+/* ONE KEYED HISTORY INTO A BATCH.  tbc_batch_map_keyed_events / tbc_batch_submit_keyed_events are tbc_batch_map_events /
+ * tbc_batch_submit_events with the split in front: the caller writes ONE history -- a key, a packed word and a process per event,
+ * 12 B -- into a pinned event slot; on the batch's copy stream the events are split by key (the kernels of tbc_pair_keyed_events), the
+ * gather writes where tbc_batch_submit_events' copies land, and from there on the call IS tbc_batch_submit_events: the keys' histories
+ * are paired, the descriptors come back, and -- all or nothing, the same refusals -- the wire columns are emitted into the device
+ * stage.  History h of the input is key keys[h].
+ *   tbc_batch_map_keyed_events     the event slots of tbc_batch_map_events (the key array lies in the same pinned allocation); the
+ *                                  first mapping of either kind fixes events_cap.  The first KEYED mapping adds the split's regions
+ *                                  to the batch's device memory, once (tbc_batch_device_bytes counts them): the raw input, the key
+ *                                  table, ids and the sort's scratch, about 60 to 80 B an event.
+ *   tbc_batch_submit_keyed_events  n_events rows of the slot.  TBC_ERR_INVALID_ARG, nothing pending and no stage written: n_events = 0
+ *                                  or beyond events_cap; more distinct keys than the batch's n_hist_cap (the count in
+ *                                  tbc_last_error(), decided before a row moves: rep then holds n_keys, bytes_in, the kernels so far
+ *                                  in ns_device, and zeros); and what tbc_batch_submit_events refuses.  rep
+ *                                  (null: none): tbc_events_report's fields, n_keys, and -- each optional -- keys[n_hist_cap] and
+ *                                  row_of[n_events] (4 B an event back only when asked for).  ns_device: the split's and the
+ *                                  pairing's kernels; bytes_in: 12 B an event.
+ * A count-form batch refuses as it refuses tbc_batch_submit_events. */
+typedef struct tbc_batch_keyed_events { /* pointers into one pinned slot; valid until the batch is destroyed */
+  uint32_t n_hist_cap, reserved0;
+  uint64_t events_cap;
+  int32_t* key;                    /* [events_cap] */
+  uint32_t* ev_word;               /* [events_cap] */
+  int32_t* process;                /* [events_cap] */
+} tbc_batch_keyed_events;
+
+typedef struct tbc_keyed_report {  /* arrays caller-allocated; each optional */
+  int32_t* status;                 /* [n_hist_cap] a tbc_status per key */
+  uint32_t* bad_row;               /* [n_hist_cap] a row within the key's rows; TBC_PAIR_NO_ROW: none */
+  uint32_t n_bad, reserved0;
+  uint64_t n_ops;
+  uint64_t ns_device;
+  uint64_t bytes_in;
+  uint32_t n_keys, reserved1;
+  int32_t* keys;                   /* [n_hist_cap] in order of first appearance */
+  uint32_t* row_of;                /* [n_events] the original row of every split row */
+} tbc_keyed_report;
+
+tbc_status tbc_batch_map_keyed_events(tbc_batch* b, uint32_t slot, uint64_t events_cap, tbc_batch_keyed_events* out);
+tbc_status tbc_batch_submit_keyed_events(tbc_batch* b, uint32_t slot, uint64_t n_events, tbc_keyed_report* rep);
 
 /* ------------------------------------------------------------------- misc */
 uint32_t tbc_version(void);             /* TBC_ABI_VERSION                       */

@@ -378,6 +378,30 @@ class EventsReport(C.Structure):
                 ("n_ops", C.c_uint64), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64)]
 
 
+class KeyedEvents(C.Structure):
+    """tbc_keyed_events: ONE event history beside a key column (tbc_pair_keyed_events); ev_word set: the packed form"""
+    _fields_ = [("n", C.c_uint32), ("device", C.c_uint32), ("key", C.POINTER(C.c_int32)), ("ev_word", C.POINTER(C.c_uint32)),
+                ("process", C.POINTER(C.c_int32)), ("type", C.POINTER(C.c_uint8)), ("f", C.POINTER(C.c_uint8)), ("a", C.POINTER(C.c_int32)),
+                ("b", C.POINTER(C.c_int32))]
+
+
+class SplitOut(C.Structure):
+    _fields_ = [("keys_cap", C.c_uint32), ("n_keys", C.c_uint32), ("keys", C.POINTER(C.c_int32)), ("ev_off", C.POINTER(C.c_uint64)),
+                ("row_of", C.POINTER(C.c_uint32))]
+
+
+class BatchKeyedEvents(C.Structure):
+    """tbc_batch_keyed_events: pointers into one pinned event slot of a batch (tbc_batch_map_keyed_events)."""
+    _fields_ = [("n_hist_cap", C.c_uint32), ("reserved0", C.c_uint32), ("events_cap", C.c_uint64), ("key", C.POINTER(C.c_int32)),
+                ("ev_word", C.POINTER(C.c_uint32)), ("process", C.POINTER(C.c_int32))]
+
+
+class KeyedReport(C.Structure):
+    _fields_ = [("status", C.POINTER(C.c_int32)), ("bad_row", C.POINTER(C.c_uint32)), ("n_bad", C.c_uint32), ("reserved0", C.c_uint32),
+                ("n_ops", C.c_uint64), ("ns_device", C.c_uint64), ("bytes_in", C.c_uint64), ("n_keys", C.c_uint32), ("reserved1", C.c_uint32),
+                ("keys", C.POINTER(C.c_int32)), ("row_of", C.POINTER(C.c_uint32))]
+
+
 def events_desc_bytes(n_hist):
     """TBC_EVENTS_DESC_BYTES: what tbc_batch_submit_events brings back from the device"""
     return 16 + 8 * (n_hist + 1) + 16 * n_hist
@@ -425,6 +449,9 @@ SYMBOLS = {
     "tbc_pair_events_batch": (C.c_int, [C.POINTER(EventBatch), C.POINTER(PairOut)]),
     "tbc_pack_events": (C.c_int, [C.POINTER(Events), C.POINTER(C.c_uint32)]),
     "tbc_pair_packed_batch": (C.c_int, [C.POINTER(PackedEventBatch), C.POINTER(PairOut)]),
+    "tbc_pair_keyed_events": (C.c_int, [C.POINTER(KeyedEvents), C.POINTER(SplitOut), C.POINTER(PairOut)]),
+    "tbc_batch_map_keyed_events": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(BatchKeyedEvents)]),
+    "tbc_batch_submit_keyed_events": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(KeyedReport)]),
     "tbc_batch_map_events": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(BatchEvents)]),
     "tbc_batch_submit_events": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(EventsReport)]),
     "tbc_check": (C.c_int, [C.POINTER(Ops), C.POINTER(Model), C.POINTER(Opts), C.POINTER(Result)]),

@@ -183,3 +183,109 @@ def pair_events_batch(evs, device=0):
         ops.append(OpColumns(*[r[k][lo:hi].copy() for k in ("f", "a", "b", "process", "inv_pos", "ret_pos")],
                              n_events=int(r["n_events"][h]), n_process=int(r["n_process"][h])))
     return ops, r["status"], r["bad_row"]
+
+
+def split_events(ev, key):
+    """ONE event history whose rows belong to keys (jepsen.independent: values are [k v] tuples) split by key, in numpy -- THE
+    DEFINITION of what tbc_pair_keyed_events splits on the device, and jepsen/independent.split restricted to tuple rows.
+    `ev`: anything with a length (only len(ev) is looked at); key: int32[len(ev)], one key per row (rows that belong to every key --
+    nemesis ops, non-tuple values -- are no client op of any key's object: the caller leaves them out).
+    -> (keys int32[n_keys] in order of FIRST APPEARANCE, ev_off uint64[n_keys + 1], row_of uint32[n]): key k's rows are
+    row_of[ev_off[k]:ev_off[k + 1]], in the order they had (a stable split)."""
+    key = np.ascontiguousarray(key, np.int32)
+    n = len(key)
+    if len(ev) != n:
+        raise ValueError(f"split_events: {len(ev)} rows, {n} keys")
+    uniq, first, inverse, counts = np.unique(key, return_index=True, return_inverse=True, return_counts=True)
+    order = np.argsort(first, kind="stable")                     # the distinct keys by their first row
+    rank = np.empty(len(uniq), np.int64)
+    rank[order] = np.arange(len(uniq))
+    ev_off = np.zeros(len(uniq) + 1, np.uint64)
+    np.cumsum(counts[order], out=ev_off[1:])
+    row_of = np.argsort(rank[inverse.reshape(-1)], kind="stable").astype(np.uint32)
+    return uniq[order].astype(np.int32), ev_off, row_of
+
+
+def take_events(ev: EventColumns, rows) -> EventColumns:
+    """the rows `rows` of an event history, in that order"""
+    return EventColumns(*[np.ascontiguousarray(getattr(ev, k)[rows]) for k in ("type", "process", "f", "a", "b")])
+
+
+def pair_keyed_events_raw(ev, key, keys_cap=None, ops_cap=None, columns=True, word=False, row_of=True, pair=True, device=0, call=None):
+    """tbc_pair_keyed_events: ONE keyed event history -- `ev` an EventColumns, or a pair (ev_word uint32[n], process int32[n]) of packed
+    events (pack_events) -- split by key and paired per key on the device in one call.
+    -> (status of the call, dict): keys, ev_off, row_of (split_events' three, the first n_keys / n_keys + 1 entries), n_keys, and -- with
+    `pair` -- what pair_events_batch_raw returns over the keys' histories.  keys_cap: the keys the outputs hold (default: one per
+    row); ops_cap, columns, word: as pair_events_batch_raw; row_of=False: not asked for; pair=False: split only (out = NULL);
+    call: another implementation of the entry point (the tests' emulator)."""
+    key = np.ascontiguousarray(key, np.int32)
+    n = len(key)
+    packed = isinstance(ev, tuple)
+    if (len(ev[0]) if packed else len(ev)) != n:
+        raise ValueError("pair_keyed_events_raw: one key per row")
+    kc = n if keys_cap is None else int(keys_cap)
+    cap = n if ops_cap is None else int(ops_cap)
+    m = max(cap, 1)
+    r = {"keys": np.zeros(max(kc, 1), np.int32), "ev_off": np.zeros(kc + 1, np.uint64)}
+    if row_of:
+        r["row_of"] = np.zeros(max(n, 1), np.uint32)
+    i = N.KeyedEvents()
+    i.n, i.device, i.key = n, device, _p(key, C.c_int32)
+    if packed:
+        i.ev_word, i.process = _p(ev[0], C.c_uint32), _p(ev[1], C.c_int32)
+    else:
+        i.type, i.process, i.f, i.a, i.b = _p(ev.type, C.c_uint8), _p(ev.process, C.c_int32), _p(ev.f, C.c_uint8), _p(ev.a, C.c_int32), _p(ev.b, C.c_int32)
+    s = N.SplitOut()
+    s.keys_cap, s.keys, s.ev_off = kc, _p(r["keys"], C.c_int32), _p(r["ev_off"], C.c_uint64)
+    if row_of:
+        s.row_of = _p(r["row_of"], C.c_uint32)
+    o = None
+    if pair:
+        nh = max(kc, 1)
+        r.update(status=np.zeros(nh, np.int32), bad_row=np.zeros(nh, np.uint32), op_off=np.zeros(kc + 1, np.uint64), n_events=np.zeros(nh, np.uint32),
+                 n_process=np.zeros(nh, np.uint32), inv_pos=np.zeros(m, np.uint32), ret_pos=np.zeros(m, np.uint32))
+        if word:
+            r["word"] = np.zeros(m, np.uint32)
+        if columns:
+            r.update(f=np.zeros(m, np.uint8), a=np.zeros(m, np.int32), b=np.zeros(m, np.int32), process=np.zeros(m, np.int32))
+        o = N.PairOut()
+        o.ops_cap = cap
+        for name, ct in (("op_off", C.c_uint64), ("n_events", C.c_uint32), ("n_process", C.c_uint32), ("f", C.c_uint8), ("a", C.c_int32),
+                         ("b", C.c_int32), ("process", C.c_int32), ("inv_pos", C.c_uint32), ("ret_pos", C.c_uint32), ("word", C.c_uint32),
+                         ("status", C.c_int32), ("bad_row", C.c_uint32)):
+            if name in r:
+                setattr(o, name, _p(r[name], ct))
+    st = (call or N.lib().tbc_pair_keyed_events)(C.byref(i), C.byref(s), C.byref(o) if pair else None)
+    nk = int(s.n_keys) if st == N.OK_STATUS else 0
+    r["n_keys"] = nk
+    r["keys"], r["ev_off"] = r["keys"][:nk], r["ev_off"][:nk + 1]
+    if row_of:
+        r["row_of"] = r["row_of"][:n]
+    if pair:
+        r.update(n_bad=int(o.n_bad), n_ops=int(o.n_ops), ns_device=int(o.ns_device), bytes_in=int(o.bytes_in))
+        for k in ("status", "bad_row", "n_events", "n_process"):
+            r[k] = r[k][:nk]
+        r["op_off"] = r["op_off"][:nk + 1]
+    return st, r
+
+
+def pair_keyed_events(ev: EventColumns, key, device=0):
+    """tbc_pair_keyed_events: one keyed event history -> (keys int32[n_keys] by first appearance; a list of OpColumns, one per key,
+    None where the key's history is refused; status int32[n_keys]; bad_row uint32[n_keys], a row WITHIN the key's rows, PAIR_NO_ROW
+    where there is none; row_of uint32[n]: the original row of every split row, key after key -- split_events' row_of)."""
+    st, r = pair_keyed_events_raw(ev, key, device=device)
+    N.check_status(st)
+    return r["keys"], keyed_ops(r), r["status"], r["bad_row"], r["row_of"]
+
+
+def keyed_ops(r):
+    """the OpColumns of every key out of what pair_keyed_events_raw returned (all six op columns asked for); None for a refused key"""
+    ops = []
+    for h in range(r["n_keys"]):
+        if r["status"][h] != N.OK_STATUS:
+            ops.append(None)
+            continue
+        lo, hi = int(r["op_off"][h]), int(r["op_off"][h + 1])
+        ops.append(OpColumns(*[r[k][lo:hi].copy() for k in ("f", "a", "b", "process", "inv_pos", "ret_pos")],
+                             n_events=int(r["n_events"][h]), n_process=int(r["n_process"][h])))
+    return ops

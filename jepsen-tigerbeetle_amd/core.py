@@ -340,6 +340,75 @@ class Batch:
         self._stream_slot = getattr(self, "_stream_slot", 0) + 1
         return self
 
+    # ---- ONE keyed history straight into the batch's device stage (include/tbcheck.h "one keyed history into a batch")
+    def map_keyed_events(self, slot, events_cap=0):
+        """Event slot `slot` as numpy views for ONE keyed history, filled IN PLACE: {"n_hist_cap", "events_cap", "key" i32[events_cap],
+        "ev_word" u32[events_cap], "process" i32[events_cap]}.  The slots are map_events' own (the first mapping of either kind fixes
+        events_cap); the first keyed mapping adds the split's regions to the batch's device memory."""
+        i = N.BatchKeyedEvents()
+        N.check_status(N.lib().tbc_batch_map_keyed_events(self._h, slot, events_cap, C.byref(i)))
+        nh, ne = int(i.n_hist_cap), int(i.events_cap)
+        view = lambda p, n: np.ctypeslib.as_array(p, shape=(n,))
+        return {"n_hist_cap": nh, "events_cap": ne, "key": view(i.key, ne), "ev_word": view(i.ev_word, ne), "process": view(i.process, ne)}
+
+    def submit_keyed_events(self, slot, n_events, keys=True, row_of=False):
+        """tbc_batch_submit_keyed_events: the slot's n_events rows go up (12 B each), are split by key and paired per key on the device,
+        and the wire columns are emitted into the batch's device stage; the next run() consumes them, history h = key keys[h].
+        -> the report: submit_events' fields, "n_keys", and -- if asked for -- "keys" and "row_of".  All or nothing, as submit_events;
+        more keys than the batch holds histories, or no event, raises TbcError too and leaves the batch as it was."""
+        cap = int(self.input_info()["n_hist_cap"])
+        status, bad_row = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.uint32)
+        ks = np.zeros(max(cap, 1), np.int32) if keys else None
+        rows = np.zeros(max(int(n_events), 1), np.uint32) if row_of else None
+        rep = N.KeyedReport()
+        rep.status, rep.bad_row = _p(status, C.c_int32), _p(bad_row, C.c_uint32)
+        if keys:
+            rep.keys = _p(ks, C.c_int32)
+        if row_of:
+            rep.row_of = _p(rows, C.c_uint32)
+        st = N.lib().tbc_batch_submit_keyed_events(self._h, slot, int(n_events), C.byref(rep))
+        nk = int(rep.n_keys) if int(rep.n_keys) <= cap else 0
+        report = {"status": status[:nk], "bad_row": bad_row[:nk], "n_bad": int(rep.n_bad), "n_ops": int(rep.n_ops),
+                  "ns_device": int(rep.ns_device), "bytes_in": int(rep.bytes_in), "n_keys": int(rep.n_keys)}
+        if keys:
+            report["keys"] = ks[:nk]
+        if row_of:
+            report["row_of"] = rows[:int(n_events)]
+        try:
+            N.check_status(st)
+        except N.TbcError as e:
+            e.report = report
+            raise
+        if not hasattr(self, "_pending_n"):
+            self._pending_n = []
+        self._pending_n.append(nk)
+        return report
+
+    def stream_keyed_events(self, ev, key, row_of=False):
+        """ONE keyed history (columns.EventColumns and key int32[len(ev)], the key of every row) into the batch: packed by
+        tbc_pack_events straight into an event slot, the key column copied beside, then submit_keyed_events.  Event slots 0 and 1 in
+        turn, as stream_events.  No per-key work on the host: the split is the device's.  pack_s, submit_s and events_report (with
+        the keys in order of first appearance: history h of the next run() is key events_report["keys"][h]) are left on the object."""
+        from .columns import pack_events
+        import time as _time
+        slot = getattr(self, "_stream_slot", 0) & 1
+        m = self.map_keyed_events(slot)
+        n = len(ev)
+        if n > m["events_cap"]:
+            raise ValueError(f"more than {m['events_cap']} events, which is what the batch's event slots hold")
+        t0 = _time.perf_counter()
+        pack_events(ev, out=m["ev_word"][:n])
+        m["process"][:n] = ev.process
+        m["key"][:n] = key
+        self.pack_s = _time.perf_counter() - t0
+        t0 = _time.perf_counter()
+        try:
+            self.events_report = self.submit_keyed_events(slot, n, row_of=row_of)
+        finally:
+            self.submit_s = _time.perf_counter() - t0
+        self._stream_slot = getattr(self, "_stream_slot", 0) + 1
+        return self
+
     def input_info(self):
         i = N.InputInfo()
         N.check_status(N.lib().tbc_batch_input_info(self._h, C.byref(i)))

@@ -461,6 +461,7 @@ void tbc_batch::count_device_bytes() {
   if (B->d_stage[0].p) B->device_bytes += B->d_stage[0].bytes();
   if (B->d_stage[1].p) B->device_bytes += B->d_stage[1].bytes();
   if (B->d_events.p) B->device_bytes += B->d_events.bytes();
+  if (B->d_split.p) B->device_bytes += B->d_split.bytes();
 }
 
 tbc_batch::~tbc_batch() {

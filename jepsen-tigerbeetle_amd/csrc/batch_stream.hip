@@ -1,5 +1,6 @@
 // batch_stream.hip -- FRESH INPUTS into a batch's arenas (include/tbcheck.h, "streaming": tbc_batch_map_input, tbc_batch_submit_input,
-// tbc_batch_reload, tbc_batch_input_info; tbc_batch_map_events, tbc_batch_submit_events).
+// tbc_batch_reload, tbc_batch_input_info; tbc_batch_map_events, tbc_batch_submit_events; tbc_batch_map_keyed_events,
+// tbc_batch_submit_keyed_events).
 //
 // The reference calls a checker once per history (/root/reference/src/tigerbeetle/core.clj:139-146: checker/compose over the test's ONE
 // history; workloads/set_full.clj:155-158: independent/checker, once per key): a caller that checks many histories never checks one
@@ -32,6 +33,9 @@
 //     straight into the device stage: nothing but the descriptors, 24 B a history, comes back.  From the descriptors on such an input
 //     is laid out by the function tbc_batch_submit_input lays its own out with (layout_input).  Not for a count-form batch, whose
 //     planning reads the wire words on the host.
+//   * ONE KEYED HISTORY (tbc_batch_map_keyed_events / tbc_batch_submit_keyed_events): the same slots with a key array, 12 B an event;
+//     the split by key (split_plan.h, split.hip) runs on the copy stream in front and gathers into the event arena's input, and from
+//     there the call ends as tbc_batch_submit_events ends: pair_into_stage, one function for both.
 // What it does not take (TBC_ERR_UNSUPPORTED: destroy and create): batches of the level sweep (a count-form batch of <= 8 histories has
 // the relaxed sweep beside it), set / bank / multi-register / table models, batches of tbc_check's persistent contexts.
 #include "tbc_batch.h"
@@ -275,6 +279,7 @@ void stream_release(tbc_batch* B) {
   }
   for (hipEvent_t& e : B->ev_pair) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   B->d_events.release();
+  B->d_split.release();
   B->d_in_flags.release(); B->d_list_over.release();
   if (B->in_flags_host) { (void)hipHostFree(B->in_flags_host); B->in_flags_host = nullptr; }
 }
@@ -432,14 +437,16 @@ tbc_status layout_input(tbc_batch* b, uint32_t n_hist, const uint64_t* op_off, c
   return TBC_OK;
 }
 
-// an event slot: [ev_off][the descriptors that come back: acc, op_off, n_events, n_process, status, bad_row][ev_word][process]
+// an event slot: [ev_off][the descriptors that come back: acc (and, 64 B on, the split's), op_off, n_events, n_process, status,
+// bad_row][ev_word][process][key]
 struct EventSlotView {
   tbc_batch_events in;
+  int32_t* key; sp::SpAcc* sp_acc;
   pr::PrAcc* acc; uint64_t* op_off; uint32_t *n_events, *n_process; int32_t* status; uint32_t* bad_row;
 };
 size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
 size_t event_slot_bytes(const tbc_batch* B) {
-  return al256((size_t)(B->in_hist_cap + 1) * 8) * 2 + 256 + 4 * al256((size_t)B->in_hist_cap * 4) + 2 * al256((size_t)B->events_cap * 4);
+  return al256((size_t)(B->in_hist_cap + 1) * 8) * 2 + 256 + 4 * al256((size_t)B->in_hist_cap * 4) + 3 * al256((size_t)B->events_cap * 4);
 }
 EventSlotView event_slot_view(const tbc_batch* B, char* mem) {
   const size_t a = al256((size_t)(B->in_hist_cap + 1) * 8), b = al256((size_t)B->in_hist_cap * 4);
@@ -452,6 +459,8 @@ EventSlotView event_slot_view(const tbc_batch* B, char* mem) {
   v.n_events = (uint32_t*)d; v.n_process = (uint32_t*)(d + b); v.status = (int32_t*)(d + 2 * b); v.bad_row = (uint32_t*)(d + 3 * b);
   v.in.ev_word = (uint32_t*)(d + 4 * b);
   v.in.process = (int32_t*)(d + 4 * b + al256((size_t)B->events_cap * 4));
+  v.key = (int32_t*)(d + 4 * b + 2 * al256((size_t)B->events_cap * 4));
+  v.sp_acc = (sp::SpAcc*)(mem + a + 64);
   return v;
 }
 
@@ -461,17 +470,21 @@ const char* kCountFormEvents = "a count-form batch plans its crashed calls on th
 }  // namespace
 }  // namespace tbc
 
-tbc_status tbc_batch_map_events(tbc_batch* b, uint32_t slot, uint64_t events_cap, tbc_batch_events* out) {
-  if (!b || !out) { set_error("tbc_batch_map_events: null argument"); return TBC_ERR_INVALID_ARG; }
-  if (slot >= kMaxInputSlots) { set_error("tbc_batch_map_events: slot %u (at most %u slots)", slot, kMaxInputSlots); return TBC_ERR_INVALID_ARG; }
+namespace tbc {
+namespace {
+
+// tbc_batch_map_events and, `keyed`, tbc_batch_map_keyed_events: the first mapping of either kind fixes events_cap and makes the event
+// arena; the first keyed one adds the split's regions; the slot's pinned memory; `v`: its pointers
+tbc_status map_event_slot(tbc_batch* b, const char* fn, uint32_t slot, uint64_t events_cap, bool keyed, EventSlotView& v) {
+  if (slot >= kMaxInputSlots) { set_error("%s: slot %u (at most %u slots)", fn, slot, kMaxInputSlots); return TBC_ERR_INVALID_ARG; }
   try {
     tbc_status s = ensure_stream(b);
     if (s != TBC_OK) return s;
-    if (b->count_form) { set_error("tbc_batch_map_events: %s", kCountFormEvents); return TBC_ERR_UNSUPPORTED; }
+    if (b->count_form) { set_error("%s: %s", fn, kCountFormEvents); return TBC_ERR_UNSUPPORTED; }
     HIP_TRY(hipSetDevice(b->device));
     if (!b->d_events.p) {          // the first mapping: events_cap for the batch, the device event arena, the events of the pairing
       const uint64_t cap = events_cap ? events_cap : 3ull * b->in_ops_cap;
-      if (cap > 0xFFFFFFFFull) { set_error("tbc_batch_map_events: %llu events, a call pairs 2^32 - 1 at most", (unsigned long long)cap); return TBC_ERR_INVALID_ARG; }
+      if (cap > 0xFFFFFFFFull) { set_error("%s: %llu events, a call pairs 2^32 - 1 at most", fn, (unsigned long long)cap); return TBC_ERR_INVALID_ARG; }
       pr::plan_batch(b->in_hist_cap, cap, b->in_ops_cap, b->ev_plan);
       if ((s = b->d_events.alloc(b->ev_plan.arena.bytes)) != TBC_OK) return s;
       b->events_cap = cap;
@@ -479,8 +492,14 @@ tbc_status tbc_batch_map_events(tbc_batch* b, uint32_t slot, uint64_t events_cap
       HIP_TRY(hipEventCreateWithFlags(&b->ev_pair[2], hipEventDisableTiming));
       b->count_device_bytes();
     } else if (events_cap > b->events_cap) {
-      set_error("tbc_batch_map_events: %llu events asked for, the batch's first mapping fixed %llu", (unsigned long long)events_cap, (unsigned long long)b->events_cap);
+      set_error("%s: %llu events asked for, the batch's first mapping fixed %llu", fn, (unsigned long long)events_cap, (unsigned long long)b->events_cap);
       return TBC_ERR_INVALID_ARG;
+    }
+    if (keyed && !b->d_split.p) {  // the first keyed mapping: the split's regions, once
+      if (b->events_cap > sp::kMaxRows) { set_error("%s: %llu events, a keyed history has 2^32 - 2 rows at most", fn, (unsigned long long)b->events_cap); return TBC_ERR_INVALID_ARG; }
+      sp::plan_batch(b->events_cap, b->sp_plan);
+      if ((s = b->d_split.alloc(b->sp_plan.bytes)) != TBC_OK) return s;
+      b->count_device_bytes();
     }
     if (b->ev_slots.size() <= slot) b->ev_slots.resize(slot + 1);
     tbc_batch::EventSlot& sl = b->ev_slots[slot];
@@ -491,10 +510,94 @@ tbc_status tbc_batch_map_events(tbc_batch* b, uint32_t slot, uint64_t events_cap
       HIP_TRY(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
     }
     if (sl.busy) { HIP_TRY(hipEventSynchronize(sl.copied)); sl.busy = false; }      // its last events are on the device: the caller may write again
-    *out = event_slot_view(b, sl.mem).in;
+    v = event_slot_view(b, sl.mem);
     return TBC_OK;
   } catch (const std::bad_alloc&) { set_error("host allocation failed"); return TBC_ERR_OOM; }
   catch (...) { set_error("unexpected exception"); return TBC_ERR_HIP; }
+}
+
+// what the keyed call hands its second half: the split's arguments, and where the caller wants keys and row_of (null: not asked for)
+struct KeyedInput { sp::SpArgs A; int32_t* keys; uint32_t* row_of; };
+
+// What tbc_batch_submit_events and tbc_batch_submit_keyed_events END with, on the copy stream: the event arena's input (ev_off, words,
+// process) is on its way -- copied there, or (`keyed`) gathered there by the split's sort, launched here inside the timed section --;
+// the histories are paired, the descriptors come back, the report is filled, and, all or nothing, the input is laid out, its wire
+// columns are emitted into the stage and it is pending.  up: what went to the device; ns_before: kernels already timed.
+tbc_status pair_into_stage(tbc_batch* b, const char* fn, uint32_t slot, const EventSlotView& v, uint32_t n_hist, uint64_t n, uint64_t up, uint64_t ns_before,
+                           tbc_pending_input& P, tbc_events_report* rep, const KeyedInput* keyed) {
+  tbc_batch::EventSlot& sl = b->ev_slots[slot];
+  DevBuf<uint32_t>& stage = b->d_stage[P.stage];
+  const pr::PrArena& L = b->ev_plan.arena;
+  char* base = (char*)b->d_events.p;
+  const pr::PrArgs A = pr::args_stage(b->ev_plan, n_hist, base, stage.p);
+  hipStream_t sc = b->stream_copy;
+  const size_t nh = n_hist;
+  std::string err;
+  tbc_status st;
+  HIP_TRY(hipMemsetAsync(base + L.acc.at, 0, L.acc.bytes, sc));
+  if (n) HIP_TRY(hipMemsetAsync(base + L.comp_of.at, 0xFF, (size_t)n * 4, sc));
+  HIP_TRY(hipEventRecord(b->ev_pair[0], sc));
+  if (keyed) {                                          // the sort and the gather; keys and row_of to the caller, 4 B an event back only if asked for
+    sp::launch_sort(sc, keyed->A);
+    HIP_TRY(hipGetLastError());
+    const char* sbase = (const char*)b->d_split.p;
+    if (keyed->keys) HIP_TRY(hipMemcpyAsync(keyed->keys, sbase + b->sp_plan.arena.keys.at, nh * 4, hipMemcpyDeviceToHost, sc));
+    if (keyed->row_of) HIP_TRY(hipMemcpyAsync(keyed->row_of, sbase + b->sp_plan.arena.row_of.at, (size_t)n * 4, hipMemcpyDeviceToHost, sc));
+  }
+  pr::launch_pair(sc, A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev_pair[1], sc));
+  HIP_TRY(hipMemcpyAsync(v.acc, base + L.acc.at, sizeof(pr::PrAcc), hipMemcpyDeviceToHost, sc));
+  HIP_TRY(hipMemcpyAsync(v.op_off, base + L.op_off.at, (nh + 1) * 8, hipMemcpyDeviceToHost, sc));
+  HIP_TRY(hipMemcpyAsync(v.n_events, base + L.n_events.at, nh * 4, hipMemcpyDeviceToHost, sc));
+  HIP_TRY(hipMemcpyAsync(v.n_process, base + L.n_process.at, nh * 4, hipMemcpyDeviceToHost, sc));
+  HIP_TRY(hipMemcpyAsync(v.status, base + L.status.at, nh * 4, hipMemcpyDeviceToHost, sc));
+  HIP_TRY(hipMemcpyAsync(v.bad_row, base + L.bad_row.at, nh * 4, hipMemcpyDeviceToHost, sc));
+  HIP_TRY(hipEventRecord(b->ev_pair[2], sc));
+  HIP_TRY(hipEventSynchronize(b->ev_pair[2]));          // (that event only: whatever the compute stream is doing goes on)
+  if (rep) {
+    float ms = 0.f;
+    if (rep->status) std::memcpy(rep->status, v.status, nh * 4);
+    if (rep->bad_row) std::memcpy(rep->bad_row, v.bad_row, nh * 4);
+    rep->n_bad = v.acc->n_bad; rep->reserved0 = 0; rep->n_ops = v.acc->total_ops;
+    rep->ns_device = ns_before + (hipEventElapsedTime(&ms, b->ev_pair[0], b->ev_pair[1]) == hipSuccess ? (uint64_t)(ms * 1e6) : 0);
+    rep->bytes_in = up;
+  }
+  // ---- all or nothing: so far nothing is pending, in_seq stands, no stage has been written
+  if ((st = pr::batch_refusal(fn, n_hist, *v.acc, v.status, v.bad_row, b->in_ops_cap, err)) != TBC_OK) { set_error("%s", err.c_str()); return st; }
+  P.total_ops = v.acc->total_ops;
+  P.bytes_copied = up + TBC_EVENTS_DESC_BYTES(n_hist);
+  if ((st = layout_input(b, n_hist, v.op_off, v.n_events, v.n_process, P)) != TBC_OK) return st;
+  // ---- the wire columns into the stage, once its previous occupant has been unpacked
+  if (b->stage_used[P.stage]) HIP_TRY(hipStreamWaitEvent(sc, b->ev_unpacked[P.stage], 0));
+  b->stage_used[P.stage] = true;
+  pr::launch_emit(sc, A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev_stage[P.stage], sc));
+  HIP_TRY(hipEventRecord(sl.copied, sc));
+  sl.busy = true;
+  b->in_seq++;
+  b->pending.push_back(std::move(P));
+  return TBC_OK;
+}
+
+}  // namespace
+}  // namespace tbc
+
+tbc_status tbc_batch_map_events(tbc_batch* b, uint32_t slot, uint64_t events_cap, tbc_batch_events* out) {
+  if (!b || !out) { set_error("tbc_batch_map_events: null argument"); return TBC_ERR_INVALID_ARG; }
+  EventSlotView v{};
+  const tbc_status st = map_event_slot(b, "tbc_batch_map_events", slot, events_cap, false, v);
+  if (st == TBC_OK) *out = v.in;
+  return st;
+}
+
+tbc_status tbc_batch_map_keyed_events(tbc_batch* b, uint32_t slot, uint64_t events_cap, tbc_batch_keyed_events* out) {
+  if (!b || !out) { set_error("tbc_batch_map_keyed_events: null argument"); return TBC_ERR_INVALID_ARG; }
+  EventSlotView v{};
+  const tbc_status st = map_event_slot(b, "tbc_batch_map_keyed_events", slot, events_cap, true, v);
+  if (st == TBC_OK) *out = tbc_batch_keyed_events{v.in.n_hist_cap, 0, v.in.events_cap, v.key, v.in.ev_word, v.in.process};
+  return st;
 }
 
 tbc_status tbc_batch_submit_events(tbc_batch* b, uint32_t slot, uint32_t n_hist, tbc_events_report* rep) {
@@ -521,55 +624,76 @@ tbc_status tbc_batch_submit_events(tbc_batch* b, uint32_t slot, uint32_t n_hist,
     // ---- up, paired, the descriptors back: all on the copy stream
     const pr::PrArena& L = b->ev_plan.arena;
     char* base = (char*)b->d_events.p;
-    const pr::PrArgs A = pr::args_stage(b->ev_plan, n_hist, base, stage.p);
     hipStream_t sc = b->stream_copy;
-    const size_t nh = n_hist;
     HIP_TRY(hipEventRecord(b->ev_copy[P.stage][0], sc));
-    HIP_TRY(hipMemcpyAsync(base + L.ev_off.at, v.in.ev_off, (nh + 1) * 8, hipMemcpyHostToDevice, sc));
+    HIP_TRY(hipMemcpyAsync(base + L.ev_off.at, v.in.ev_off, ((size_t)n_hist + 1) * 8, hipMemcpyHostToDevice, sc));
     if (n) {
       HIP_TRY(hipMemcpyAsync(base + L.ev_word.at, v.in.ev_word, (size_t)n * 4, hipMemcpyHostToDevice, sc));
       HIP_TRY(hipMemcpyAsync(base + L.process.at, v.in.process, (size_t)n * 4, hipMemcpyHostToDevice, sc));
     }
     HIP_TRY(hipEventRecord(b->ev_copy[P.stage][1], sc));
-    HIP_TRY(hipMemsetAsync(base + L.acc.at, 0, L.acc.bytes, sc));
-    if (n) HIP_TRY(hipMemsetAsync(base + L.comp_of.at, 0xFF, (size_t)n * 4, sc));
+    return pair_into_stage(b, fn, slot, v, n_hist, n, (uint64_t)n * 8 + ((uint64_t)n_hist + 1) * 8, 0, P, rep, nullptr);
+  } catch (const std::bad_alloc&) { set_error("host allocation failed"); return TBC_ERR_OOM; }
+  catch (...) { set_error("unexpected exception"); return TBC_ERR_HIP; }
+}
+
+tbc_status tbc_batch_submit_keyed_events(tbc_batch* b, uint32_t slot, uint64_t n_events, tbc_keyed_report* rep) {
+  const char* fn = "tbc_batch_submit_keyed_events";
+  if (!b) { set_error("%s: null batch", fn); return TBC_ERR_INVALID_ARG; }
+  if (b->count_form) { set_error("%s: %s", fn, kCountFormEvents); return TBC_ERR_UNSUPPORTED; }
+  if (!b->stream_copy || slot >= b->ev_slots.size() || !b->ev_slots[slot].mem || !b->d_split.p) { set_error("%s: slot %u was never mapped (tbc_batch_map_keyed_events)", fn, slot); return TBC_ERR_INVALID_ARG; }
+  if (n_events == 0 || n_events > b->events_cap) { set_error("%s: %llu events, a slot holds 1..%llu", fn, (unsigned long long)n_events, (unsigned long long)b->events_cap); return TBC_ERR_INVALID_ARG; }
+  if (b->pending.size() >= 2) { set_error("%s: two inputs are waiting already -- tbc_batch_run consumes one", fn); return TBC_ERR_INVALID_ARG; }
+  try {
+    HIP_TRY(hipSetDevice(b->device));
+    tbc_batch::EventSlot& sl = b->ev_slots[slot];
+    if (sl.busy) { set_error("%s: slot %u is still being copied (map it again before it is re-filled)", fn, slot); return TBC_ERR_INVALID_ARG; }
+    const EventSlotView v = event_slot_view(b, sl.mem);
+    const size_t n = (size_t)n_events;
+    tbc_status st;
+    tbc_pending_input P;
+    P.slot = slot; P.stage = (uint32_t)(b->in_seq & 1u);
+    DevBuf<uint32_t>& stage = b->d_stage[P.stage];
+    if (!stage.p && (st = stage.alloc(3 * b->in_ops_cap)) != TBC_OK) return st;
+    // ---- up (12 B an event), the keys and their ids, the number of keys back: all on the copy stream
+    const sp::SpArena& S = b->sp_plan.arena;
+    char* base = (char*)b->d_split.p;
+    sp::SpArgs A = sp::args_batch(b->sp_plan, (uint32_t)n, base, (char*)b->d_events.p, b->ev_plan.arena);
+    hipStream_t sc = b->stream_copy;
+    HIP_TRY(hipEventRecord(b->ev_copy[P.stage][0], sc));
+    HIP_TRY(hipMemcpyAsync(base + S.key.at, v.key, n * 4, hipMemcpyHostToDevice, sc));
+    HIP_TRY(hipMemcpyAsync(base + S.r_word.at, v.in.ev_word, n * 4, hipMemcpyHostToDevice, sc));
+    HIP_TRY(hipMemcpyAsync(base + S.r_process.at, v.in.process, n * 4, hipMemcpyHostToDevice, sc));
+    HIP_TRY(hipEventRecord(b->ev_copy[P.stage][1], sc));
+    HIP_TRY(hipMemsetAsync(base + S.acc.at, 0, S.acc.bytes, sc));
+    HIP_TRY(hipMemsetAsync(base + S.table.at, 0xFF, (size_t)8 << A.bits, sc));
     HIP_TRY(hipEventRecord(b->ev_pair[0], sc));
-    pr::launch_pair(sc, A);
+    sp::launch_keys(sc, A);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(b->ev_pair[1], sc));
-    HIP_TRY(hipMemcpyAsync(v.acc, base + L.acc.at, sizeof(pr::PrAcc), hipMemcpyDeviceToHost, sc));
-    HIP_TRY(hipMemcpyAsync(v.op_off, base + L.op_off.at, (nh + 1) * 8, hipMemcpyDeviceToHost, sc));
-    HIP_TRY(hipMemcpyAsync(v.n_events, base + L.n_events.at, nh * 4, hipMemcpyDeviceToHost, sc));
-    HIP_TRY(hipMemcpyAsync(v.n_process, base + L.n_process.at, nh * 4, hipMemcpyDeviceToHost, sc));
-    HIP_TRY(hipMemcpyAsync(v.status, base + L.status.at, nh * 4, hipMemcpyDeviceToHost, sc));
-    HIP_TRY(hipMemcpyAsync(v.bad_row, base + L.bad_row.at, nh * 4, hipMemcpyDeviceToHost, sc));
+    HIP_TRY(hipMemcpyAsync(v.sp_acc, base + S.acc.at, sizeof(sp::SpAcc), hipMemcpyDeviceToHost, sc));
     HIP_TRY(hipEventRecord(b->ev_pair[2], sc));
-    HIP_TRY(hipEventSynchronize(b->ev_pair[2]));          // (that event only: whatever the compute stream is doing goes on)
-    const uint64_t up = (uint64_t)n * 8 + (nh + 1) * 8;
-    if (rep) {
-      float ms = 0.f;
-      if (rep->status) std::memcpy(rep->status, v.status, nh * 4);
-      if (rep->bad_row) std::memcpy(rep->bad_row, v.bad_row, nh * 4);
-      rep->n_bad = v.acc->n_bad; rep->reserved0 = 0; rep->n_ops = v.acc->total_ops;
-      rep->ns_device = hipEventElapsedTime(&ms, b->ev_pair[0], b->ev_pair[1]) == hipSuccess ? (uint64_t)(ms * 1e6) : 0;
-      rep->bytes_in = up;
+    HIP_TRY(hipEventSynchronize(b->ev_pair[2]));
+    float ms = 0.f;
+    const uint64_t ns_keys = hipEventElapsedTime(&ms, b->ev_pair[0], b->ev_pair[1]) == hipSuccess ? (uint64_t)(ms * 1e6) : 0;
+    const uint32_t n_keys = v.sp_acc->n_keys;
+    if (rep) {                                          // (a call refused here leaves a whole report: the number of keys, what went up, the kernels so far)
+      rep->n_keys = n_keys; rep->reserved1 = 0;
+      rep->n_bad = 0; rep->reserved0 = 0; rep->n_ops = 0; rep->ns_device = ns_keys; rep->bytes_in = (uint64_t)n * 12;
     }
-    // ---- all or nothing: so far nothing is pending, in_seq stands, no stage has been written
-    if ((st = pr::batch_refusal(fn, n_hist, *v.acc, v.status, v.bad_row, b->in_ops_cap, err)) != TBC_OK) { set_error("%s", err.c_str()); return st; }
-    P.total_ops = v.acc->total_ops;
-    P.bytes_copied = up + TBC_EVENTS_DESC_BYTES(n_hist);
-    if ((st = layout_input(b, n_hist, v.op_off, v.n_events, v.n_process, P)) != TBC_OK) return st;
-    // ---- the wire columns into the stage, once its previous occupant has been unpacked
-    if (b->stage_used[P.stage]) HIP_TRY(hipStreamWaitEvent(sc, b->ev_unpacked[P.stage], 0));
-    b->stage_used[P.stage] = true;
-    pr::launch_emit(sc, A);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(b->ev_stage[P.stage], sc));
-    HIP_TRY(hipEventRecord(sl.copied, sc));
-    sl.busy = true;
-    b->in_seq++;
-    b->pending.push_back(std::move(P));
-    return TBC_OK;
+    if (n_keys > b->in_hist_cap) {                       // (before a row moves: nothing is pending, no stage has been written)
+      set_error("%s: %u distinct keys, the batch holds %u histories", fn, n_keys, b->in_hist_cap);
+      return TBC_ERR_INVALID_ARG;
+    }
+    A.n_keys = n_keys; A.n_pass = sp::sort_passes(n_keys);
+    P.n_hist = n_keys;
+    // ---- the sort and the gather into the event arena's input, then tbc_batch_submit_events' own second half
+    tbc_events_report er{};
+    if (rep) { er.status = rep->status; er.bad_row = rep->bad_row; }
+    const KeyedInput keyed{A, rep ? rep->keys : nullptr, rep ? rep->row_of : nullptr};
+    st = pair_into_stage(b, fn, slot, v, n_keys, n, (uint64_t)n * 12, ns_keys, P, rep ? &er : nullptr, &keyed);
+    if (rep) { rep->n_bad = er.n_bad; rep->reserved0 = 0; rep->n_ops = er.n_ops; rep->ns_device = er.ns_device; rep->bytes_in = er.bytes_in; }
+    return st;
   } catch (const std::bad_alloc&) { set_error("host allocation failed"); return TBC_ERR_OOM; }
   catch (...) { set_error("unexpected exception"); return TBC_ERR_HIP; }
 }

@@ -75,12 +75,18 @@ struct Plan {
 
 // TBC_OK, or TBC_ERR_INVALID_ARG and in `err` the entry point and the rule
 // (the rules of ev_off and of the output arrays: what the two forms of the input share)
+// (the rules of the output arrays alone: tbc_pair_keyed_events, whose ev_off is made on the device, holds its `out` to them; split_plan.h)
+inline tbc_status validate_out(const char* fn, const tbc_pair_out* out, std::string& err) {
+  const auto say = [&](const char* what) { err = std::string(fn) + ": " + what; return TBC_ERR_INVALID_ARG; };
+  if (out && (!out->op_off || !out->n_events || !out->n_process || !out->status || !out->bad_row)) return say("null argument (op_off, n_events, n_process, status, bad_row)");
+  if (out && out->ops_cap && (!out->inv_pos || !out->ret_pos)) return say("null argument (inv_pos, ret_pos)");
+  return TBC_OK;
+}
 inline tbc_status validate_offsets(const char* fn, uint32_t n_hist, const uint64_t* ev_off, const tbc_pair_out* out, std::string& err) {
   char buf[256];
   const auto say = [&](const char* what) { std::snprintf(buf, sizeof buf, "%s: %s", fn, what); err = buf; return TBC_ERR_INVALID_ARG; };
   if (!ev_off) return say("null argument (ev_off)");
-  if (out && (!out->op_off || !out->n_events || !out->n_process || !out->status || !out->bad_row)) return say("null argument (op_off, n_events, n_process, status, bad_row)");
-  if (out && out->ops_cap && (!out->inv_pos || !out->ret_pos)) return say("null argument (inv_pos, ret_pos)");
+  if (validate_out(fn, out, err) != TBC_OK) return TBC_ERR_INVALID_ARG;
   if (ev_off[0] != 0) return say("ev_off[0] is not 0");
   for (uint32_t h = 0; h < n_hist; h++) {
     if (ev_off[h + 1] < ev_off[h]) { std::snprintf(buf, sizeof buf, "%s: history %u: ev_off descends", fn, h); err = buf; return TBC_ERR_INVALID_ARG; }
@@ -212,15 +218,11 @@ void put_events(Frame& C, const PrArena& L, const tbc_event_batch* in) {
 template <class Frame>
 void put_events(Frame& C, const PrArena& L, const tbc_packed_event_batch* in) { C.put(L.ev_word, in->ev_word); C.put(L.process, in->process); }
 
-template <class Frame, class Run, class In>
-tbc_status steps(Frame& C, Run&& run, const char* fn, const In* in, const Plan& P, tbc_pair_out* out) {
-  const PrArena& L = P.arena;
-  const PrArgs A = args(P, out, C.base());
-  C.fill(L.acc, 0, L.acc.bytes);
-  C.put(L.ev_off, in->ev_off);
-  put_events(C, L, in);
-  C.fill(L.comp_of, 0xFF, L.comp_of.bytes);
-  C.timed([&] { run.pair(A); });
+// The second half of the call, from the pairing launched to the filled `out`: what `steps` below and the keyed call (split_plan.h,
+// whose histories are made on the device: A.n_hist of them, P.n_hist at most) both end with.
+template <class Frame, class Run>
+tbc_status finish(Frame& C, Run&& run, const char* fn, const PrArena& L, const PrArgs& A, tbc_pair_out* out) {
+  const size_t nh = A.n_hist;
   PrAcc acc{};
   C.get(&acc, L.acc);
   if (C.sync() != TBC_OK) return C.status;
@@ -232,12 +234,24 @@ tbc_status steps(Frame& C, Run&& run, const char* fn, const In* in, const Plan& 
   C.get(out->process, L.o_process, out->process ? T * 4 : 0);
   C.get(out->inv_pos, L.o_inv, out->inv_pos ? T * 4 : 0); C.get(out->ret_pos, L.o_ret, out->ret_pos ? T * 4 : 0);
   C.get(out->word, L.o_word, out->word ? T * 4 : 0);
-  C.get(out->op_off, L.op_off); C.get(out->n_events, L.n_events); C.get(out->n_process, L.n_process);
-  C.get(out->status, L.status); C.get(out->bad_row, L.bad_row);
+  C.get(out->op_off, L.op_off, (nh + 1) * 8); C.get(out->n_events, L.n_events, nh * 4); C.get(out->n_process, L.n_process, nh * 4);
+  C.get(out->status, L.status, nh * 4); C.get(out->bad_row, L.bad_row, nh * 4);
   if (C.sync() != TBC_OK) return C.status;
   out->n_bad = acc.n_bad; out->reserved0 = 0; out->n_ops = acc.total_ops;
   oneshot::account(C, *out);
   return TBC_OK;
+}
+
+template <class Frame, class Run, class In>
+tbc_status steps(Frame& C, Run&& run, const char* fn, const In* in, const Plan& P, tbc_pair_out* out) {
+  const PrArena& L = P.arena;
+  const PrArgs A = args(P, out, C.base());
+  C.fill(L.acc, 0, L.acc.bytes);
+  C.put(L.ev_off, in->ev_off);
+  put_events(C, L, in);
+  C.fill(L.comp_of, 0xFF, L.comp_of.bytes);
+  C.timed([&] { run.pair(A); });
+  return finish(C, run, fn, L, A, out);
 }
 
 }  // namespace pr

@@ -23,6 +23,7 @@
 #include "tbc_internal.h"
 #include "pool_plan.h"
 #include "pair_plan.h"
+#include "split_plan.h"
 
 namespace tbc {
 
@@ -359,6 +360,11 @@ struct tbc_batch {
   pr::Plan ev_plan;
   tbc::DevBuf<unsigned char> d_events;
   hipEvent_t ev_pair[3] = {};               // the pairing kernels begin / end (timing); the descriptors have arrived
+  // ---- one KEYED history into the batch (tbc_batch_map_keyed_events / tbc_batch_submit_keyed_events): the same slots (a key array
+  // lies behind [process] in every one) and the same event arena, plus the split's regions (split_plan.h plan_batch), made by the
+  // first keyed mapping and kept; the split runs on stream_copy in front of the pairing and gathers into the event arena's input
+  sp::Plan sp_plan;
+  tbc::DevBuf<unsigned char> d_split;
 
   bool borrowed = false;            // stream and events belong to a persistent context (tbc_check)
   ~tbc_batch();

@@ -163,5 +163,73 @@ class IndependentChecker(jc.Checker):
         return out
 
 
+    def check_columns(self, ev, key, opts=None):
+        """check() for a history that is already COLUMNS: `ev` (columns.EventColumns: the client ops of every key, the tuples stripped,
+        register values as the small integers the device takes, N.NIL for nil) and key int32[len(ev)], the key of every row.  For a
+        Linearizable inner over a register or cas-register whose initial value is such an integer (or None).  The history is split by key
+        and paired per key on the device (columns.pair_keyed_events), the keys go to ONE core.Batch, and the result has the shape
+        check() gives: {key: result} as _check_batched makes it, the ops rebuilt from the rows (their :index is the row of `ev`).
+        Rows that belong to every key (nemesis ops) are the caller's to leave out.  The split and the pairing touch no op on the host; the batch is still created from the op columns that
+        come back (core.Batch.stream_keyed_events is the route that keeps them on the device, for a batch that exists already)."""
+        from .. import columns
+        lin = self.inner
+        if not isinstance(lin, jc.Linearizable) or not isinstance(lin.model, (_analysis.M.Register, _analysis.M.CASRegister)):
+            raise ValueError("check_columns: a Linearizable checker over a register or cas-register")
+        device = (opts or {}).get("device", lin.opts.get("device", 0))
+        st, raw = columns.pair_keyed_events_raw(ev, key, device=device)      # (pair_keyed_events, with the device's ev_off kept)
+        N.check_status(st)
+        keys, ops, row_of, offs, results = [int(k) for k in raw["keys"]], columns.keyed_ops(raw), raw["row_of"], raw["ev_off"].astype("int64"), {}
+        good = [k for k in range(len(keys)) if ops[k] is not None]
+        res = []
+        if good:
+            kind = N.MODEL_CAS_REGISTER if isinstance(lin.model, _analysis.M.CASRegister) else N.MODEL_REGISTER
+            init = N.NIL if lin.model.value is None else int(lin.model.value)
+            want_witness = bool(lin.opts.get("witness", lin.algorithm == "wgl"))
+            with core.Batch([ops[k] for k in good], core.make_model(kind, init), _analysis.make_opts_from(lin.algorithm, lin.opts, want_witness)) as b:
+                b.run(tolerate_bad_histories=True)
+                res = b.results()
+        by_key = dict(zip(good, res))
+        for k, name in enumerate(keys):
+            r = by_key.get(k)
+            if r is None or (r["valid"] == N.UNKNOWN and r["cause"] == N.CAUSE_NONE):
+                results[name] = {"valid?": "unknown", "cause": "malformed-history", "analyzer": "wgl", "configs": [], "final-paths": []}
+                continue
+            a = _analysis.result_map(_ColumnsEncoded(lin.model, ops[k], _KeyRows(ev, row_of[offs[k]:offs[k + 1]])), r, lin.algorithm)
+            a["final-paths"] = a["final-paths"][:10]
+            a["configs"] = a["configs"][:10]
+            results[name] = a
+        failures = [k for k in keys if results[k].get("valid?") is False]
+        return {"valid?": jc.merge_valid(r.get("valid?") for r in results.values()), "results": results, "failures": failures}
+
+
+class _KeyRows:
+    """row r of a key's sub-history as the op map it stands for, made when it is asked for"""
+    _TYPE = {N.INVOKE: "invoke", N.OK: "ok", N.FAIL: "fail", N.INFO: "info"}
+    _F = {N.F_READ: "read", N.F_WRITE: "write", N.F_CAS: "cas"}
+
+    def __init__(self, ev, rows):
+        self.ev, self.rows = ev, rows
+
+    def __getitem__(self, r):
+        at = int(self.rows[r])
+        dec = lambda x: None if x == N.NIL else int(x)
+        f = int(self.ev.f[at])
+        a, b = dec(self.ev.a[at]), dec(self.ev.b[at])
+        return {"index": at, "type": self._TYPE.get(int(self.ev.type[at])), "process": int(self.ev.process[at]), "f": self._F.get(f, f),
+                "value": (None if a is None and b is None else (a, b)) if f == N.F_CAS else a}
+
+
+class _ColumnsEncoded(_analysis.Encoded):
+    """what _analysis.result_map reads of an Encoded, over columns: the values are their own encoding"""
+
+    class _Identity:
+        @staticmethod
+        def dec(x):
+            return None if x == N.NIL else int(x)
+
+    def __init__(self, model, ops, rows):
+        self.model, self.ops, self.rows, self.table_info, self.intern = model, ops, rows, None, self._Identity
+
+
 def checker(inner):
     return IndependentChecker(inner)
