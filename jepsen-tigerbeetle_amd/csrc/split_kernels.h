@@ -32,8 +32,9 @@
 // sums, 256 a step with a carried base -- n / 4,096 of them for thist), sp_apply_kernel (every block scanned in place from its base).
 // Ballots, the barriers and index / thread go through wave_env.h / wave_env_wg.h; the 64-bit atomics on the table are plain HIP, which
 // tests/emu/emu_split.cpp states for the host emulator -- these very kernels run there in a permuted order of workgroups.
-// SPLIT_MUTATION (1: ids by key VALUE instead of first appearance; 2: the scatter ranks within the tile only) exists for
-// tests/test_keyed_events_emu.py alone, which must see both.
+// SPLIT_MUTATION (1: ids by key VALUE instead of first appearance; 2: the scatter ranks within the tile only; 3: sp_top_kernel
+// stores a block's base without what its earlier steps of 256 carried; 4: the probe of the table stays in the last slot instead of
+// going on in slot 0) exists for tests/test_keyed_events_emu.py alone, which must see all four.
 #pragma once
 #include "wave_env_wg.h"
 #include "split_plan.h"
@@ -71,6 +72,9 @@ __global__ __launch_bounds__(256) void sp_insert_kernel(SpArgs A) {
     const unsigned long long mine = ((unsigned long long)k << 32) | r;
     unsigned long long idx = sp::table_hash(k, A.bits);
     for (unsigned long long t = 0; t <= mask; t++, idx = (idx + 1ull) & mask) {          // (2n slots or more: an empty one comes)
+#if defined(SPLIT_MUTATION) && SPLIT_MUTATION == 4
+      if (t != 0ull && idx == 0ull) idx = mask;                                        // (the step behind the last slot stays in it)
+#endif
       unsigned long long w = sp_ld64(&A.table[idx]);
       if (w == sp::kEmpty) {
         w = atomicCAS(&A.table[idx], sp::kEmpty, mine);
@@ -88,6 +92,9 @@ __device__ __forceinline__ uint32_t sp_first_row(const SpArgs& A, uint32_t k) {
   const unsigned long long mask = sp_mask(A);
   unsigned long long idx = sp::table_hash(k, A.bits);
   for (unsigned long long t = 0; t <= mask; t++, idx = (idx + 1ull) & mask) {
+#if defined(SPLIT_MUTATION) && SPLIT_MUTATION == 4
+    if (t != 0ull && idx == 0ull) idx = mask;
+#endif
     const unsigned long long w = A.table[idx];
     if ((uint32_t)(w >> 32) == k && w != sp::kEmpty) return (uint32_t)w;
     if (w == sp::kEmpty) break;                                                        // (never)
@@ -247,6 +254,9 @@ __global__ __launch_bounds__(256) void sp_top_kernel(SpScan S) {                
     uint32_t total;
     const uint32_t ex = wg_scan_excl(v, s_scan, t, 0u, total, [](uint32_t a, uint32_t c) { return a + c; });
     if (b < S.n_blocks) S.sums[b] = base + ex;
+#if defined(SPLIT_MUTATION) && SPLIT_MUTATION == 3
+    if (b < S.n_blocks) S.sums[b] = ex;
+#endif
     base += total;
   }
   if (t == 0u) *S.total = base;

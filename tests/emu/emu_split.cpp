@@ -4,7 +4,7 @@
 // THE LAUNCHER IS THIS PROGRAM'S OWN: oneshot_emu.h runs a launch's workgroups one after the other in index order, which a kernel that
 // takes a row's place from the order in which its atomics arrive would pass; here the workgroups of every launch run in a seeded
 // PERMUTED order, so that such a place moves with the seed.  Grids that stride are capped at `grid_cap` workgroups.
-// Built as a shared object by tests/test_keyed_events_emu.py (also with SPLIT_MUTATION 1 and 2, which that test must see).  With
+// Built as a shared object by tests/test_keyed_events_emu.py (also with SPLIT_MUTATION 1 to 4, which that test must see).  With
 // EMU_SPLIT_MAIN it is a program of its own (linked with csrc/tbc_host.cpp, the specification of the pairing): seeded keyed histories
 // through the emulator, against a stable split on the host and tbc_pair_events per key, every array compared -- the form that is built
 // with -fsanitize=address,undefined and run as a plain executable.
@@ -126,12 +126,10 @@ struct Events { std::vector<uint8_t> type, f; std::vector<int32_t> process, a, b
 uint64_t g_rng = 0x243F6A8885A308D3ull;
 uint32_t rnd(uint32_t n) { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17; return (uint32_t)((g_rng >> 11) % n); }
 
-// one interleaved history of about `n` rows over `n_keys` keys (key values spread over the int32 range, INT32_MIN and -1 among them),
-// `procs` processes a key; a key in `spoil` gets one malformed row
-Events history(uint32_t n, uint32_t n_keys, uint32_t procs, uint32_t spoil_every) {
+// one interleaved history of about `n` rows over the keys `kv`, `procs` processes a key; a key in `spoil` gets one malformed row
+Events history_over(uint32_t n, const std::vector<int32_t>& kv, uint32_t procs, uint32_t spoil_every) {
   Events e;
-  std::vector<int32_t> kv(n_keys);
-  for (uint32_t k = 0; k < n_keys; k++) kv[k] = k == 0 ? INT32_MIN : (k == 1 ? -1 : (int32_t)(0x7FFFFFFF - (int32_t)k * 40503));
+  const uint32_t n_keys = (uint32_t)kv.size();
   std::vector<std::vector<int>> open(n_keys, std::vector<int>(procs, 0));
   std::vector<std::vector<int32_t>> id(n_keys, std::vector<int32_t>(procs));
   for (uint32_t k = 0; k < n_keys; k++) for (uint32_t p = 0; p < procs; p++) id[k][p] = (int32_t)p;
@@ -149,8 +147,32 @@ Events history(uint32_t n, uint32_t n_keys, uint32_t procs, uint32_t spoil_every
   }
   return e;
 }
+// ... over `n_keys` keys, their values spread over the int32 range, INT32_MIN and -1 among them
+Events history(uint32_t n, uint32_t n_keys, uint32_t procs, uint32_t spoil_every) {
+  std::vector<int32_t> kv(n_keys);
+  for (uint32_t k = 0; k < n_keys; k++) kv[k] = k == 0 ? INT32_MIN : (k == 1 ? -1 : (int32_t)(0x7FFFFFFF - (int32_t)k * 40503));
+  return history_over(n, kv, procs, spoil_every);
+}
+// keys whose probe run crosses the END of the table a history of n rows gets: 8 whose home is the last slot, 8 in the slot before it, 4
+// in slot 0, a key of each in turn (the first three are the hot keys)
+std::vector<int32_t> wrapping_keys(uint32_t n) {
+  const uint32_t bits = sp::table_bits(n);
+  const uint64_t last = (1ull << bits) - 1ull;
+  std::vector<std::vector<int32_t>> g(3);
+  const uint64_t home[3] = {last, last - 1ull, 0ull};
+  const size_t count[3] = {8, 8, 4};
+  for (uint32_t k = 1; k < 200000u; k++)
+    for (int i = 0; i < 3; i++)
+      if (sp::table_hash(k, bits) == home[i] && g[i].size() < count[i]) g[i].push_back((int32_t)k);
+  std::vector<int32_t> kv;
+  for (size_t j = 0; j < 8; j++)
+    for (int i = 0; i < 3; i++)
+      if (j < g[i].size()) kv.push_back(g[i][j]);
+  return kv;
+}
 
-int check(const Events& e0, bool packed, uint32_t grid_cap, uint64_t seed, uint32_t cap = 0) {
+// want_keys: the distinct keys the history is there to have (0: any)
+int check(const Events& e0, bool packed, uint32_t grid_cap, uint64_t seed, uint32_t cap = 0, size_t want_keys = 0) {
   const uint32_t n = (uint32_t)e0.type.size();
   Events e = e0;                                                              // (cap: the arrays hold `cap` rows, the first n count)
   if (cap) { e.type.resize(cap); e.f.resize(cap); e.process.resize(cap); e.a.resize(cap); e.b.resize(cap); e.key.resize(cap); }
@@ -164,6 +186,7 @@ int check(const Events& e0, bool packed, uint32_t grid_cap, uint64_t seed, uint3
     rows[it->second].push_back(r);
   }
   const size_t nk = wkeys.size();
+  if (want_keys && nk != want_keys) { std::printf("seed %llu: the history has %zu keys, it is there for %zu\n", (unsigned long long)seed, nk, want_keys); return 1; }
   std::vector<uint64_t> wev_off{0}, woff{0};
   std::vector<uint32_t> wrow_of, wi, wr, wproc(nk);
   std::vector<uint8_t> wf; std::vector<int32_t> wa, wb, wp, wst(nk);
@@ -225,6 +248,16 @@ int main() {
   // the batch form: regions for a capacity, a call of fewer rows (a tile more, and ten times the rows)
   wrong += check(small, true, 3u, 3, (uint32_t)small.type.size() + sp::kTile + 5u);
   wrong += check(wide, true, 1u, 4, 10u * (uint32_t)wide.type.size());
+  // a probe run across the table's end (20 keys around the last slot of the 1,024 that 300 rows get), and several rows a key over two
+  // passes of the sort (257 keys, each key's rows over the five tiles)
+  const std::vector<int32_t> around_the_end = wrapping_keys(300);
+  if (around_the_end.size() != 20u) { std::printf("WRONG: %zu keys around the table's end\n", around_the_end.size()); return 1; }
+  const Events wraps = history_over(300, around_the_end, 2, 0), two_passes = history(4 * sp::kTile + 3, 257, 2, 0);
+  for (uint64_t seed = 5; seed <= 6; seed++) {
+    wrong += check(wraps, seed == 6, seed == 5 ? 3u : 1u, seed, 0, 20);
+    wrong += check(two_passes, seed == 5, seed == 5 ? 3u : 1u, seed, 0, 257);
+    rows += wraps.type.size() + two_passes.type.size();
+  }
   std::printf("%s: %zu rows\n", wrong ? "WRONG" : "ok", rows);
   return wrong ? 1 : 0;
 }

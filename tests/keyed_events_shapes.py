@@ -2,7 +2,18 @@
 GPU test (tests/test_keyed_events_gpu.py): the smallest shapes at which each mechanism of csrc/split_kernels.h can go wrong -- chunks
 of 64 rows and tiles of T = 1,024, the digits of the sort (n_keys around 2^8 and 2^16), the key table (sp::table_hash, stated below),
 the order of the keys -- and the reference: columns.split_events in numpy, then tbc_pair_events key by key (pair_events_shapes.reference).
-A case is a list of keyed histories (EventColumns, key int32[n]); each goes into one call."""
+A case is a list of keyed histories (EventColumns, key int32[n]); each goes into one call.
+
+THREE THRESHOLDS of the kernels lie above those shapes, and large_cases() / large_case() hold one history each side of none of
+them but just past each: 2^20 rows (the scan's one workgroup over the block sums takes its SECOND step of 256 once thist has more
+than 256 blocks of 1,024 words, n_tiles > 1,024; the row kernels' grid of 4,096 workgroups of 256 threads begins to stride), 8,192
+tiles (8,388,608 rows: the tile kernels' grid begins to stride) -- and, at any size, THE TABLE'S END: a probe run that starts in
+the last slots goes on in slot 0 (probe_run_wraps, a small case).  The large histories are built in numpy and go through the split
+alone, once each; they are not in cases(), whose every entry the tests run three to nine times.  The scan's own block stride
+(sp_sum_kernel / sp_apply_kernel above 4,096 blocks) would need 16.8 M rows and a 512 MB key table: left out on purpose, the
+emulator's capped grids run that loop and the library's cap is one min."""
+import functools
+
 import numpy as np
 
 import packed_events_shapes as PK
@@ -63,6 +74,20 @@ def colliding_keys(n, count):
     return [int(k) for pair in zip(same, behind) for k in pair]
 
 
+def wrapping_keys(n):
+    """keys whose probe run crosses the END of the table a history of n rows gets: 8 whose home is the last slot, 8 in the slot before
+    it, 4 in slot 0 -- a key of each in turn, so that the run that begins in slot 2^bits - 2 goes on through slots 0, 1, ... past the
+    keys whose home slot 0 is"""
+    bits = table_bits(n)
+    last = (1 << bits) - 1
+    at = lambda slot, count: [k for k in range(1, 200000) if table_hash(k, bits) == slot][:count]
+    groups = [at(last, 8), at(last - 1, 8), at(0, 4)]
+    assert [len(g) for g in groups] == [8, 8, 4]
+    keys = [g[i] for i in range(8) for g in groups if i < len(g)]
+    assert len(keys) == 20 and sum(table_hash(k, bits) == last for k in keys) >= 2
+    return keys
+
+
 def _cases():
     c = {}
     c["sizes"] = [spread(n, 3) for n in (0, 1, 63, 64, 65, T - 1, T, T + 1, 2 * T + 1)]
@@ -80,6 +105,11 @@ def _cases():
     c["first_appearance_descending"] = [(ev, key), (H(pairs(8)), np.array([3, 2, 1, 1, 2, 3, 0, 0], np.int32))]
     c["key_values"] = [spread(200, 4, keys=[INT32_MAX, -1, INT32_MIN, 0]), spread(9, 4, keys=[-1, INT32_MIN, INT32_MAX, 0])]
     c["colliding_keys"] = [spread(300, 24, keys=colliding_keys(300, 12))]
+    # a probe run across the table's end: the `& mask` step from the last slot to slot 0, in the insert and in the lookup
+    c["probe_run_wraps"] = [spread(300, 20, keys=wrapping_keys(300))]
+    # two passes of the sort with up to 16 rows a key, every key's rows in four or five tiles: the order of a key's OWN rows through a second
+    # stable pass; key values scattered, not in the order of first appearance
+    c["many_rows_over_passes"] = [spread(4 * T + 3, 257, keys=[(i * 7919) % 65521 - 30000 for i in range(257)])]
     # an invocation in the last row of a chunk / of a tile of the ONE history, its completion in the first row of the next -- and the same
     # at row 63 / 64 of the key's own rows (the pairing's chunk)
     rows, key = [], []
@@ -110,6 +140,66 @@ def _cases():
 WORD_CASES = ("wire", "sizes", "semantics", "refusal_per_key")
 BIG_CASES = ("digit_edges_16",)          # ~200k rows, a key each: the emulator test runs the SPLIT of these alone, at grids 3 and 1 with a seed each (a
                                          # wavefront of the pairing clears a 4,096-entry table per key: most of a minute on the CPU); the GPU test pairs them
+
+
+# ---- the large shapes: past 2^20 rows and past 8,192 tiles
+LARGE_CASES = ("top_scan_second_step", "top_scan_three_passes", "three_passes_many_rows")     # the emulator and the GPU
+LARGE_GPU_CASES = LARGE_CASES + ("tiles_stride",)                                             # (8.4 M rows: the GPU alone)
+_LARGE = {"top_scan_second_step": (T * T + 1, 300, 11), "top_scan_three_passes": (T * T + T + 1, 70000, 12),
+          "three_passes_many_rows": (3 * 65537 + 5, 65537, 13), "tiles_stride": (8192 * T + T + 1, 1000, 14)}
+
+
+def _large(n, n_keys, seed):
+    """n rows over n_keys keys, in numpy: every key once in the order of its id (an invocation of process 0 that never completes),
+    then invocation and :ok of a process 1..3 in ADJACENT rows under one key drawn at random, and an invocation of process 4 in the
+    last row where rows are left over -- every key's rows a well-formed history.  The key VALUES are a seeded permutation, spread out:
+    not in the order of first appearance."""
+    rng = np.random.default_rng(seed)
+    m = (n - n_keys) // 2
+    drawn = rng.integers(0, n_keys, m)
+    ids = np.concatenate([np.arange(n_keys), np.repeat(drawn, 2), rng.integers(0, n_keys, (n - n_keys) % 2)])
+    k = np.arange(m)
+    typ = np.concatenate([np.full(n_keys, I), np.tile([I, OK], m), np.full((n - n_keys) % 2, I)]).astype(np.uint8)
+    proc = np.concatenate([np.zeros(n_keys, np.int64), np.repeat(1 + k % 3, 2), np.full((n - n_keys) % 2, 4)]).astype(np.int32)
+    a = np.concatenate([np.arange(n_keys) % 5, np.repeat(k % 5, 2), np.zeros((n - n_keys) % 2, np.int64)]).astype(np.int32)
+    value = (rng.permutation(n_keys) * 29 - 1000000).astype(np.int32)
+    ev = columns.EventColumns(typ, proc, np.full(n, W, np.uint8), a, np.zeros(n, np.int32))
+    assert len(ev) == len(ids) == n
+    return ev, np.ascontiguousarray(value[ids])
+
+
+@functools.lru_cache(maxsize=None)
+def large_case(name):
+    """(EventColumns, key int32[n]) of one large shape, built once; each holds in Python what it is named for"""
+    n, n_keys, seed = _LARGE[name]
+    ev, key = _large(n, n_keys, seed)
+    n_tiles, per_key = (n + T - 1) // T, np.bincount(np.unique(key, return_inverse=True)[1].reshape(-1))
+    blocks = (256 * n_tiles + 1023) // 1024                      # of the scan over thist
+    assert len(per_key) == n_keys and per_key.min() >= 1 and per_key.max() >= 3
+    if name == "top_scan_second_step":                           # 257 blocks: ONE into the second step; the row kernels stride
+        # (block 256 is the last tiles of digit 255: the key of id 255 has rows there, so the step's carried base places rows)
+        assert (n, n_tiles, blocks, sort_passes(n_keys)) == (T * T + 1, T + 1, 257, 2) and n > 4096 * 256
+        assert (key[(n_tiles - 200) * T:] == key[255]).any() and not (key[:255] == key[255]).any()
+    elif name == "top_scan_three_passes":                        # the same with a third pass: the final buffers are id_b / row_b
+        assert n == T * T + T + 1 and blocks > 256 and sort_passes(n_keys) == 3 and len(set(key[:2 * 65537].tolist())) >= 65537
+    elif name == "three_passes_many_rows":                       # a key's own rows through three stable passes
+        assert (n, n_keys, sort_passes(n_keys)) == (3 * 65537 + 5, 65537, 3) and np.array_equal(np.unique(key[:n_keys]), np.unique(key))
+    else:                                                        # tiles_stride: more tiles than the tile kernels' grid of 8,192
+        assert n_tiles == 8194 > 8192 and blocks > 256 and sort_passes(n_keys) == 2
+    return ev, key
+
+
+def large_cases():
+    """name -> (EventColumns, key) of the large shapes the emulator runs (tiles_stride: large_case, the GPU test alone)"""
+    return {name: large_case(name) for name in LARGE_CASES}
+
+
+@functools.lru_cache(maxsize=None)
+def large_reference(name):
+    """columns.split_events of a large shape, computed once and shared: keys, ev_off, row_of, n_keys"""
+    ev, key = large_case(name)
+    keys, ev_off, row_of = columns.split_events(ev, key)
+    return {"keys": keys, "ev_off": ev_off, "row_of": row_of, "n_keys": len(keys)}
 
 
 def forms(name):

@@ -3,7 +3,9 @@ those of csrc/pair_kernels.h -- the files hipcc compiles into libtbcheck.so -- u
 (tests/emu/emu_split.cpp), against columns.split_events in numpy and tbc_pair_events key by key: every output array bit for bit on
 the shapes of tests/keyed_events_shapes.py, with the grids capped at 3 and at 1 workgroups.  The program's own launcher runs the
 workgroups of every launch in a seeded PERMUTED order, two seeds at least, so that a row's place taken from the order in which atomics
-arrive would show on the CPU.  Two planted mutations of the kernels (SPLIT_MUTATION) must each be seen by a shape.  The same program
+arrive would show on the CPU.  Four planted mutations of the kernels (SPLIT_MUTATION) must each be seen by a shape -- the third
+only past 2^20 rows (keyed_events_shapes.large_cases, the split alone and once each), the fourth only where a probe run crosses
+the table's end.  The same program
 with its own main (EMU_SPLIT_MAIN, linked with csrc/tbc_host.cpp) is built with -fsanitize=address,undefined and run as a plain
 executable, outside Python.  Test infrastructure only: the product has no CPU path."""
 import ctypes as C
@@ -27,7 +29,7 @@ CASES = sorted(S.cases())
 def emus(tmp_path_factory, native):
     d = tmp_path_factory.mktemp("emu_sp")
     procs, libs = [], {}
-    for m in (0, 1, 2):
+    for m in (0, 1, 2, 3, 4):
         so = str(d / f"libemu_sp{m}.so")
         procs.append((m, so, subprocess.Popen(FLAGS + ["-shared", "-fPIC"] + ([f"-DSPLIT_MUTATION={m}"] if m else []) + [SRC, "-o", so])))
     for m, so, p in procs:
@@ -147,6 +149,51 @@ def test_planted_mutations_are_seen(emus, mutation, seen_by):
         S.assert_same(got, want, seen_by)
     st, good, err = run(emus[0], ev, key)
     S.assert_same(good, want, seen_by)
+
+
+def split_alone(lib, ev, key, grid, seed):
+    st, got, err = run(lib, ev, key, grid=grid, seed=seed, pair=False)
+    assert st == 0, err
+    return got
+
+
+@pytest.mark.parametrize("name, grid, seed", [("top_scan_second_step", 3, 21), ("top_scan_three_passes", 3, 22), ("three_passes_many_rows", 1, 23)])
+def test_past_2_to_the_20_rows(emus, name, grid, seed):
+    """the large shapes (keyed_events_shapes.large_cases), the split alone, once each: sp_top_kernel's second step of 256 block sums,
+    with two and with three passes of the sort, and several rows a key through three passes -- keys, ev_off and row_of bit for bit
+    against columns.split_events"""
+    ev, key = S.large_cases()[name]
+    S.assert_same(split_alone(emus[0], ev, key, grid, seed), S.large_reference(name), (name, grid, seed), paired=False)
+
+
+def test_the_second_step_of_the_top_scan_is_seen_past_2_to_the_20_rows_alone(emus):
+    """mutation 3: sp_top_kernel stores a block's base without what the steps before carried.  The largest history of cases(),
+    digit_edges_16[2] (65,537 rows: 17 blocks), PASSES under it -- the gap these shapes close; 2^20 + 1 rows (257 blocks) see it."""
+    ev, key = S.cases()["digit_edges_16"][2]
+    want = dict(zip(("keys", "ev_off", "row_of"), columns.split_events(ev, key)))
+    want["n_keys"] = len(want["keys"])
+    S.assert_same(split_alone(emus[3], ev, key, 3, 1), want, "digit_edges_16[2] under mutation 3", paired=False)
+    ev, key = S.large_cases()["top_scan_second_step"]
+    got = split_alone(emus[3], ev, key, 3, 21)
+    with pytest.raises(AssertionError):
+        S.assert_same(got, S.large_reference("top_scan_second_step"), "top_scan_second_step under mutation 3", paired=False)
+
+
+def test_a_probe_that_does_not_wrap_is_seen_by_the_wrapping_case_alone(emus):
+    """mutation 4: behind the last slot of the table the probe stays there (in bounds; `t <= mask` ends it) in sp_insert_kernel and
+    sp_first_row.  colliding_keys, whose probe runs lie in the middle of the table, passes under it; probe_run_wraps does not.  The
+    split alone: the mutated table loses keys, and the pairing is not to run over what is left."""
+    for name, seen in (("colliding_keys", False), ("probe_run_wraps", True)):
+        ev, key = S.cases()[name][0]
+        want = S.reference(name, 0, ev, key, False)
+        for grid, seed in ((3, 1), (1, 2)):
+            S.assert_same(split_alone(emus[0], ev, key, grid, seed), want, (name, grid, seed), paired=False)
+            got = split_alone(emus[4], ev, key, grid, seed)
+            if seen:
+                with pytest.raises(AssertionError):
+                    S.assert_same(got, want, (name, "mutation 4", grid, seed), paired=False)
+            else:
+                S.assert_same(got, want, (name, "mutation 4", grid, seed), paired=False)
 
 
 def test_stand_alone_program_under_the_sanitizers(tmp_path):

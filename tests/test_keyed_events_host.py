@@ -83,6 +83,38 @@ def test_the_shapes_hold_what_they_are_there_for():
         assert np.array_equal(ref[k], flat[k]), k
 
 
+def test_the_table_end_and_many_rows_shapes_hold_what_they_are_there_for():
+    c, T = S.cases(), S.T
+    (ev, key), = c["probe_run_wraps"]
+    bits = S.table_bits(len(key))
+    assert (len(key), bits) == (300, 10)
+    keys, _, _ = columns.split_events(ev, key)
+    home = [S.table_hash(int(k), bits) for k in keys]
+    assert (home.count(1023), home.count(1022), home.count(0), len(home)) == (8, 8, 4, 20)
+    assert home[:6] == [1023, 1022, 0, 1023, 1022, 0]                      # a key of each group in turn
+    (ev, key), = c["many_rows_over_passes"]
+    keys, ev_off, row_of = columns.split_events(ev, key)
+    per_key = np.diff(ev_off.astype(np.int64))
+    assert len(key) == 4 * T + 3 and len(keys) == 257 and S.sort_passes(257) == 2 and (per_key.min(), per_key.max()) == (15, 16)
+    tiles = [len(set(row_of[int(ev_off[h]):int(ev_off[h + 1])] // T)) for h in range(257)]      # (a key's rows are 257 apart)
+    assert min(tiles) == 4 and max(tiles) == 5
+    assert list(keys) != sorted(keys) and list(keys) != sorted(keys, reverse=True)
+    ref = S.reference("many_rows_over_passes", 0, ev, key, False)
+    assert not ref["status"].any() and ref["n_ops"] > 2 * T
+
+
+def test_the_large_shapes_hold_what_they_are_there_for():
+    """(large_case asserts the thresholds itself: the tiles, the scan's blocks, the passes, the rows a key)"""
+    assert S.LARGE_GPU_CASES == S.LARGE_CASES + ("tiles_stride",) and set(S.large_cases()) == set(S.LARGE_CASES)
+    for name, (ev, key) in S.large_cases().items():
+        assert len(ev) == len(key) > (S.T * S.T if name.startswith("top_scan") else 3 * 65537) and key.dtype == np.int32
+    # an invocation and its completion in adjacent rows under one key, behind the keys' first rows
+    ev, key = S.large_case("top_scan_second_step")
+    body = slice(300, len(key) - 1)
+    assert np.array_equal(key[body][0::2], key[body][1::2]) and set(ev.type[body][0::2]) == {PS.I} and set(ev.type[body][1::2]) == {PS.OK}
+    assert np.array_equal(ev.process[body][0::2], ev.process[body][1::2])
+
+
 def test_the_quick_reference_is_the_reference():
     """keyed_events_shapes._all_keys_fine (tbc_pair_events key by key without an array per key) gives what pair_events_shapes.reference gives"""
     for name, i in (("sizes", 8), ("semantics", 0), ("key_values", 0)):
