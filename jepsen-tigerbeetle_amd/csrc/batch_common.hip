@@ -40,6 +40,13 @@ void guard_remove(const void* arena_end) {
   std::lock_guard<std::mutex> lk(g_guard_mu);
   for (size_t i = 0; i < g_guards.size(); i++) if (g_guards[i].at == (const char*)arena_end) { g_guards.erase(g_guards.begin() + (long)i); return; }
 }
+size_t guard_live(const void* owner, size_t* all) {
+  std::lock_guard<std::mutex> lk(g_guard_mu);
+  size_t own = 0;
+  for (const GuardRec& g : g_guards) own += g.owner == owner;
+  *all = g_guards.size();
+  return own;
+}
 // returns the number of arenas whose guard bytes were overwritten (after the caller's stream is idle)
 size_t guard_check(const char* when, const void* owner) {
   std::vector<GuardRec> live;

@@ -5,11 +5,11 @@
 //   plan_engines                  sequential / wide / several histories per wavefront / level sweep / relaxed sweep, rules, lookahead
 //   plan_sweep_segments           the sweep's windows and cuts
 //   layout_histories              per-history descriptors and the arenas' element counts (shared with batch_stream.hip)
-//   alloc_arenas                  every device arena, in the order tbc_check's one-block upload and one-block memset rely on
+//   alloc_arenas                  every device arena (the input-sized ones: batch_arenas.h), in the order tbc_check's one-block upload and one-block memset rely on
 //   upload_inputs                 columns, descriptors, work list (one pinned block for tbc_check)
 //   size_lists_on_device          a big batch: pack + counts once over the resident inputs say how long the per-front lists are
 // There is no CPU path in here by design: every compute entry point needs a gfx950 device and says TBC_ERR_NO_DEVICE otherwise.
-#include "tbc_batch.h"
+#include "batch_arenas.h"
 #include "reach_table.h"
 
 using namespace tbc;
@@ -464,19 +464,18 @@ void tbc_batch::count_device_bytes() {
   if (B->d_split.p) B->device_bytes += B->d_split.bytes();
 }
 
+// What is not a DevBuf.  The arenas are members and free themselves AFTER this body (a borrowed batch's are pieces of its context's
+// slab: they only un-register their guard bytes), so the streams destroyed here are idle first: a batch given up in mid-create
+// may have copies queued, and they read and write what goes next.
 tbc_batch::~tbc_batch() {
+  if (!borrowed) {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (stream2) (void)hipStreamSynchronize(stream2);
+  }
   tbc::stream_release(this);
-  d_f.release(); d_a.release(); d_b.release(); d_proc.release(); d_inv.release(); d_ret.release();
-  d_hist.release(); d_rec.release(); d_seg.release(); d_ret_slot.release(); d_ret_op.release();
-  d_bitmap.release(); d_wpre.release(); d_frames.release(); d_witness.release(); d_work.release();
-  d_queue.release(); d_tab.release(); d_results.release(); d_table.release(); d_pool_vals.release(); d_cfg.release();
-  d_bh.release(); d_off.release(); d_ncr.release(); d_lst.release(); d_crashed.release(); d_stack.release();
-  d_zncr.release(); d_reach.release(); d_reach_hdr.release(); d_abort.release(); d_order.release(); d_park.release();
   if (abort_one) (void)hipHostFree(abort_one);
   if (progress) (void)hipHostFree(progress);
-  d_progress.release();
   if (!borrowed) { for (auto& e : ev2) if (e) (void)hipEventDestroy(e); if (stream2) (void)hipStreamDestroy(stream2); }
-  d_cmem.release(); d_occ.release(); d_btab.release(); d_slot8.release(); d_rk8.release(); d_look.release(); d_looktmp.release(); d_twn.release(); d_rdm.release(); d_cuts.release(); d_seglist.release(); d_sres.release(); d_dstack.release(); d_pool.release(); d_pool_cursor.release();
   if (ev_turn) (void)hipEventDestroy(ev_turn);
   if (!borrowed) {
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
@@ -487,18 +486,18 @@ tbc_batch::~tbc_batch() {
 namespace tbc {
 namespace {
 
-// Every device arena of the batch, sized from the layout's totals -- in the order tbc_check relies on (its arenas are consecutive pieces
-// of its context's slab: what is uploaded -- the six columns, the descriptors, the work list -- first, as one block (upload_inputs);
-// then what every run zeroes, as one memset (batch_run.hip, zero_block)).  The lists (d_lst, d_twn) of a big batch come later
-// (size_lists_on_device).
+// Every device arena of the batch: those whose size follows the input as batch_arenas.h states them, the others here -- in the order
+// tbc_check relies on (its arenas are consecutive pieces of its context's slab: what is uploaded -- the six columns, the descriptors,
+// the work list -- first, as one block (upload_inputs); then what every run zeroes, as one memset (batch_run.hip, zero_block)).  The
+// lists (d_lst, d_twn) of a big batch come later (size_lists_on_device).
 tbc_status alloc_arenas(CreatePlan& P) {
-  tbc_batch* B = P.B; const tbc_opts* opts = P.opts; const tbc_model* model = P.model;
+  tbc_batch* B = P.B; const tbc_model* model = P.model;
   const uint32_t nh = P.nh;
   const bool beam = P.beam, device_sizing = P.device_sizing;
   const LayoutTotals& t = P.tot;
   const uint32_t EW = B->entry_words();
+  const auto allocate = [](auto& buf, uint64_t count) { return buf.alloc((size_t)count); };
   tbc_status s;
-  const uint64_t T = B->total_ops;
   // (progress words: host memory the kernels write and another host thread reads, coherent like the debug words of batch_common.hip.
   // tbc_check's one-shot batches, which borrow a context and hand out no handle, have none: nobody could ask)
   if (!t_ctx) {
@@ -506,19 +505,12 @@ tbc_status alloc_arenas(CreatePlan& P) {
     std::memset(B->progress, 0, 16 * sizeof(uint32_t));
     if ((s = B->d_progress.alloc(1))) return s;
   }
-  if ((s = B->d_f.alloc(T)) || (s = B->d_a.alloc(T)) || (s = B->d_b.alloc(T)) || (s = B->d_proc.alloc(T)) ||
-      (s = B->d_inv.alloc(T)) || (s = B->d_ret.alloc(T)) || (s = B->d_hist.alloc(nh)) || (s = B->d_bh.alloc(beam ? nh : 0)) || (s = B->d_work.alloc(nh)) ||
-      (s = B->d_bitmap.alloc(t.bm_n)) || (s = B->d_off.alloc(beam ? t.boff_n : 0)) || (s = B->d_ncr.alloc(beam ? t.boff_n : 0)) || (s = B->d_pool_cursor.alloc(1)) ||
-      (s = B->d_rec.alloc(t.rec_n)) ||
-      (s = B->d_seg.alloc(t.seg_n)) || (s = B->d_ret_slot.alloc(T)) || (s = B->d_ret_op.alloc(T)) ||
-      (s = B->d_wpre.alloc(t.bm_n)) || (s = B->d_frames.alloc(t.frame_n)) ||
-      (s = B->d_tab.alloc(t.tab_n)) || (s = B->d_results.alloc(nh)) ||
-      (s = B->d_queue.alloc(4)) || (s = B->d_witness.alloc(opts->want_witness ? T : 0)))
+  if ((s = visit_column_arenas(B, t, allocate)) || (s = B->d_hist.alloc(nh)) || (s = B->d_bh.alloc(beam ? nh : 0)) || (s = B->d_work.alloc(nh)) ||
+      (s = visit_zeroed_arenas(B, t, allocate)) || (s = B->d_pool_cursor.alloc(1)) ||
+      (s = visit_other_arenas(B, t, nh, allocate)) || (s = B->d_results.alloc(nh)) || (s = B->d_queue.alloc(4)))
     return s;
   if (beam) {
-    if ((!device_sizing && (s = B->d_lst.alloc(t.blst_n))) || (s = B->d_crashed.alloc((B->count_form || !B->any_crashed) ? 0 : T)) || (s = B->d_cmem.alloc(B->count_form ? t.bocc_n : 0)) ||
-        (s = B->d_slot8.alloc(slot8_bytes(T, nh))) || (s = B->d_stack.alloc(t.bstack_n)) || (s = B->d_btab.alloc(t.btab_n * B->tab_stride())))
-      return s;
+    if (!device_sizing && (s = size_lists(B, t.blst_n))) return s;
     if ((B->sweep || B->rsweep) && ((s = B->d_cuts.alloc((uint64_t)nh * B->max_segs)) || (s = B->d_sres.alloc((uint64_t)nh * B->max_segs * kSweepSlices)) || (s = B->d_seglist.alloc((uint64_t)nh * B->max_segs * kSweepSlices * 3)))) return s;
     if (B->sweep || B->rsweep) B->seg_host.resize((size_t)nh * B->max_segs * kSweepSlices);
     if (B->rsweep) {          // no crashed call is a candidate of its own (a zero ncr[]); the classes' reach tables (reach_table.h)
@@ -536,21 +528,12 @@ tbc_status alloc_arenas(CreatePlan& P) {
       HIP_TRY(hipHostMalloc((void**)&B->abort_one, sizeof(uint32_t), hipHostMallocDefault));
       *B->abort_one = 1u;
     }
-    if (B->lanes && (s = B->d_rk8.alloc(slot8_bytes(T, nh)))) return s;
-    if (B->reg_rules() && ((!device_sizing && (s = B->d_twn.alloc(t.blst_n * B->mask_words))) || (s = B->d_rdm.alloc(B->lanes ? 1 : T * B->vpad * B->mask_words)))) return s;
-    // several histories per wavefront: front records (tbc_internal.h) instead of plain rows, with or without the rules
-    if (B->lanes) { B->d_rdm.release(); if ((s = B->d_rdm.alloc(T * B->front_words()))) return s; }
-    // (d_looktmp: scratch of the walk with lane = process slot only -- launch_pack_open's choice, repeated here)
-    const bool by_front = B->mask_words == 1 && B->vpad <= 32;
-    if (B->lookahead && ((s = B->d_look.alloc(look_words(T, nh, B->mask_words))) || (s = B->d_looktmp.alloc(by_front ? 0 : T)) ||
-                         (s = B->d_dstack.alloc(t.bstack_n)))) return s;
-    // growth pool: 30 % of the visited-set arena -- 10 % for the big quiet batches that run several histories per wavefront, whose sets
-    // rarely grow (a history that outgrows its table and finds the pool empty is run again from a scratch arena: at 32 calls in
-    // flight a 10 % pool cost 22 s of such retries per 2,048 histories) --, at least room for one history to grow twice (4x, then 16x: keys, parents, two stacks, slot translation), at most 32 GiB
+    // growth pool: its share of the visited-set arena (batch_arenas.h), at least room for one history to grow twice (4x, then 16x: keys,
+    // parents, two stacks, slot translation), at most 32 GiB
     {
       uint64_t biggest = 0;
       for (uint32_t h = 0; h < nh; h++) biggest = std::max<uint64_t>(biggest, 1ull << B->bh[h].tab_log2);
-      uint64_t words = std::max<uint64_t>(t.btab_n * B->tab_stride() * (B->lanes ? 1u : 3u) / 10, biggest * (4 + 16 + 4) * (EW + 1));
+      uint64_t words = std::max<uint64_t>(pool_share_words(B, t), biggest * (4 + 16 + 4) * (EW + 1));
       words = std::min<uint64_t>(words, (32ull << 30) / 8);
       if (B->sweep) words = 1;
       if ((s = B->d_pool.alloc(words))) return s;
@@ -660,7 +643,7 @@ tbc_status upload_inputs(CreatePlan& P, bool* done) {
 }
 
 // the narrow kernel addresses lists and fronts with 32-bit element offsets (wgl_narrow_impl.h): a batch past that keeps a wavefront per history
-bool lists_too_long(const tbc_batch* B, const LayoutTotals& t) { return B->lanes && (t.blst_n >= (1ull << 32) || t.boff_n >= (1ull << 32)); }
+bool lists_too_long(const tbc_batch* B, const LayoutTotals& t) { return lists_past_lanes(B, t.blst_n) || (B->lanes && t.boff_n >= (1ull << 32)); }
 
 // A big batch: the pack and counts kernels over the resident inputs say how many entries each history's per-front lists hold
 // (BeamHist.lst_need); the list arenas are allocated after that.  (A pass over every history's events on the host was 1.5 of
@@ -694,13 +677,12 @@ tbc_status size_lists_on_device(CreatePlan& P) {
     const bool had_branch = (B->rules & kRuleBranch) != 0;
     B->lanes = 0; B->rules &= ~kRuleBranch;
     if (!opts->want_witness) {                   // (a wavefront per history keeps parent links whatever the caller wants: the arena grows by them)
-      B->d_btab.release();
-      if ((s = B->d_btab.alloc(P.tot.btab_n * B->tab_stride()))) return s;
+      if ((s = B->d_btab.regrow(btab_words(B, P.tot)))) return s;
     }
     if (!had_branch) break;                      // (else the lists hold the reads again: counted once more)
     for (uint32_t h = 0; h < nh; h++) { B->bh[h].lst_cap = 0xFFFFFFF0u; B->bh[h].lst_off = 0; }
   }
-  if ((s = B->d_lst.alloc(P.tot.blst_n)) || (B->reg_rules() && (s = B->d_twn.alloc(P.tot.blst_n * B->mask_words)))) return s;
+  if ((s = size_lists(B, P.tot.blst_n))) return s;
   B->count_device_bytes();
   TRACE("create: lists sized on the device");
   return TBC_OK;

@@ -123,7 +123,7 @@ static tbc_status scratch_pass(tbc_batch* B, const std::vector<uint32_t>& grp, c
     }
     entries += 1ull << lg[i];
   }
-  DevBuf<uint64_t> big;
+  DevBuf<uint64_t> big;          // (the scratch arenas go when the pass is left, whichever way)
   DevBuf<uint32_t> bstack, bdstack, bframes;
   tbc_status st = big.alloc(entries * words_per_entry);
   if (st != TBC_OK) return st;
@@ -131,38 +131,35 @@ static tbc_status scratch_pass(tbc_batch* B, const std::vector<uint32_t>& grp, c
   if (!beam && B->frame_words < seq_fw) {          // the batch's frames arena is sized for the pack kernels only: the sequential kernel's stack is taken here
     uint64_t fn = 0;
     for (size_t i = 0; i < grp.size(); i++) { ph[i].frame_off = fn; fn += std::max<uint64_t>(ph[i].n_ops, 1) * seq_fw; }
-    if ((st = bframes.alloc(fn)) != TBC_OK) { big.release(); return st; }
+    if ((st = bframes.alloc(fn)) != TBC_OK) return st;
   }
-  if (beam && (st = bstack.alloc(entries)) != TBC_OK) { big.release(); return st; }
-  if (beam && B->lookahead && (st = bdstack.alloc(entries)) != TBC_OK) { big.release(); bstack.release(); return st; }
-  hipError_t e = hipMemsetAsync(big.p, 0, entries * words_per_entry * 8, s);
-  for (size_t i = 0; i < grp.size() && e == hipSuccess; i++) {
-    e = hipMemcpyAsync(B->d_hist.p + grp[i], &ph[i], sizeof(Hist), hipMemcpyHostToDevice, s);
-    if (beam && e == hipSuccess) e = hipMemcpyAsync(B->d_bh.p + grp[i], &pb[i], sizeof(BeamHist), hipMemcpyHostToDevice, s);
+  if (beam && (st = bstack.alloc(entries)) != TBC_OK) return st;
+  if (beam && B->lookahead && (st = bdstack.alloc(entries)) != TBC_OK) return st;
+  // (the first call that fails ends the pass: nothing after it is queued, the descriptors are put back only after a pass that ran)
+  HIP_TRY(hipMemsetAsync(big.p, 0, entries * words_per_entry * 8, s));
+  for (size_t i = 0; i < grp.size(); i++) {
+    HIP_TRY(hipMemcpyAsync(B->d_hist.p + grp[i], &ph[i], sizeof(Hist), hipMemcpyHostToDevice, s));
+    if (beam) HIP_TRY(hipMemcpyAsync(B->d_bh.p + grp[i], &pb[i], sizeof(BeamHist), hipMemcpyHostToDevice, s));
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(B->d_work.p, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    const uint32_t nw = (uint32_t)grp.size();
-    if (beam) { BeamArgs ba = make_beam_args(B, big.p, bstack.p, bdstack.p, nw); ba.pool = nullptr; ba.pool_words = 0;
-      if (width_override) ba.width = width_override;
-      ba.count_mode = count_mode;
-      if (steps_override >= 0) ba.max_steps = (uint64_t)steps_override;
-      // (a retry runs the schedule of the first pass: several histories per wavefront stay so)
-      if (B->lanes && (!width_override || width_override == B->width)) launch_narrow(ba, B->mask_words, B->lanes, s); else launch_beam(ba, B->mask_words, search_blocks(nw), s); }
-    else { SearchArgs ra = make_search_args(B, big.p, nw); if (bframes.p) ra.frames = bframes.p; launch_search(ra, B->mask_words, search_blocks(nw), s); }
-    e = hipGetLastError();
-  }
-  for (size_t i = 0; i < grp.size() && e == hipSuccess; i++)
-    e = hipMemcpyAsync(&B->res_host[grp[i]], B->d_results.p + grp[i], sizeof(DevResult), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  HIP_TRY(hipMemcpyAsync(B->d_work.p, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, s));
+  const uint32_t nw = (uint32_t)grp.size();
+  if (beam) { BeamArgs ba = make_beam_args(B, big.p, bstack.p, bdstack.p, nw); ba.pool = nullptr; ba.pool_words = 0;
+    if (width_override) ba.width = width_override;
+    ba.count_mode = count_mode;
+    if (steps_override >= 0) ba.max_steps = (uint64_t)steps_override;
+    // (a retry runs the schedule of the first pass: several histories per wavefront stay so)
+    if (B->lanes && (!width_override || width_override == B->width)) launch_narrow(ba, B->mask_words, B->lanes, s); else launch_beam(ba, B->mask_words, search_blocks(nw), s); }
+  else { SearchArgs ra = make_search_args(B, big.p, nw); if (bframes.p) ra.frames = bframes.p; launch_search(ra, B->mask_words, search_blocks(nw), s); }
+  HIP_TRY(hipGetLastError());
+  for (size_t i = 0; i < grp.size(); i++)
+    HIP_TRY(hipMemcpyAsync(&B->res_host[grp[i]], B->d_results.p + grp[i], sizeof(DevResult), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   // put the descriptors back so the next run starts from the resident layout
-  for (size_t i = 0; i < grp.size() && e == hipSuccess; i++) {
-    e = hipMemcpyAsync(B->d_hist.p + grp[i], &hist_back[grp[i]], sizeof(Hist), hipMemcpyHostToDevice, s);
-    if (beam && e == hipSuccess) e = hipMemcpyAsync(B->d_bh.p + grp[i], &bh_back[grp[i]], sizeof(BeamHist), hipMemcpyHostToDevice, s);
+  for (size_t i = 0; i < grp.size(); i++) {
+    HIP_TRY(hipMemcpyAsync(B->d_hist.p + grp[i], &hist_back[grp[i]], sizeof(Hist), hipMemcpyHostToDevice, s));
+    if (beam) HIP_TRY(hipMemcpyAsync(B->d_bh.p + grp[i], &bh_back[grp[i]], sizeof(BeamHist), hipMemcpyHostToDevice, s));
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  big.release(); bstack.release(); bdstack.release(); bframes.release();
-  if (e != hipSuccess) { set_error("scratch pass failed: %s", hipGetErrorString(e)); return TBC_ERR_HIP; }
+  HIP_TRY(hipStreamSynchronize(s));
   return TBC_OK;
 }
 
@@ -560,7 +557,7 @@ tbc_status first_pass(RunState& R) {
   SYNC_TRACE("memsets");
 
   if (!B->hist_order.empty()) {          // (a race's batch: every history's own list order goes up before the walk)
-    if (B->d_order.n < nh) { B->d_order.release(); const tbc_status os = B->d_order.alloc(nh); if (os != TBC_OK) return os; }
+    if (B->d_order.n < nh) { const tbc_status os = B->d_order.regrow(nh); if (os != TBC_OK) return os; }
     HIP_TRY(hipMemcpyAsync(B->d_order.p, B->hist_order.data(), (size_t)nh * 4, hipMemcpyHostToDevice, s));
   }
   tbc_status ps = queue_pack(R);
@@ -1002,11 +999,10 @@ tbc_status race_orders(RunState& R, const std::vector<uint32_t>& pend_all) {
     if (inner) tbc_batch_destroy(inner);
     HIP_TRY(hipSetDevice(B->device));
     const bool inner_ok = nr != 0 && (st == TBC_OK || st == TBC_ERR_BAD_HISTORY || st == TBC_ERR_MODEL);
-    if (!inner_ok && n_res == 0) { decided.release(); d_outer_map.release(); d_inner_map.release(); return st == TBC_OK ? TBC_ERR_HIP : st; }
+    if (!inner_ok && n_res == 0) return st == TBC_OK ? TBC_ERR_HIP : st;
     if (n_res) HIP_TRY(hipMemcpyAsync(outer_res.data(), B->d_results.p, (size_t)nh * sizeof(DevResult), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));          // the resumed default order: decided, or told to stop by a replica that was
     TRACE("race: the resumed default order is done");
-    decided.release(); d_outer_map.release(); d_inner_map.release();
     // ---- who answered: the default order if it decided (its counters are then the whole single search's -- nothing was done twice);
     // else the first replica, in the orders' sequence, that did.  What the others did before they stopped is work done: it is counted.
     std::vector<uint32_t> first_rep(k, 0xFFFFFFFFu);

@@ -38,7 +38,7 @@
 //     there the call ends as tbc_batch_submit_events ends: pair_into_stage, one function for both.
 // What it does not take (TBC_ERR_UNSUPPORTED: destroy and create): batches of the level sweep (a count-form batch of <= 8 histories has
 // the relaxed sweep beside it), set / bank / multi-register / table models, batches of tbc_check's persistent contexts.
-#include "tbc_batch.h"
+#include "batch_arenas.h"
 
 using namespace tbc;
 
@@ -166,44 +166,20 @@ void slot_pointers(const tbc_batch* B, char* mem, tbc_batch_input* out) {
   out->ret_pos = out->inv_pos + B->in_ops_cap;
 }
 
-template <typename T>
-tbc_status ensure(DevBuf<T>& buf, uint64_t need, bool* grew) {
-  if (buf.p && buf.n >= need) return TBC_OK;
-  *grew = true;
-  return buf.regrow((size_t)(need + need / 16));
-}
-
-// every per-history arena holds the input laid out as `tot` (the allocation list of batch_create.hip's alloc_arenas, for the batches
-// streamable() lets through); an arena that is too small is replaced by one 6 % larger than asked
+// every input-sized arena (batch_arenas.h) holds the input laid out as `t`; one that is too small is replaced by one 6 % larger than asked
 tbc_status ensure_arenas(tbc_batch* B, const LayoutTotals& t) {
-  const uint64_t T = t.total_ops;
-  const uint32_t nhc = B->in_hist_cap, MW = B->mask_words;
-  bool grew = false, grew_tab = false;
-  tbc_status s;
-  if ((s = ensure(B->d_f, T, &grew)) || (s = ensure(B->d_a, T, &grew)) || (s = ensure(B->d_b, T, &grew)) || (s = ensure(B->d_proc, T, &grew)) ||
-      (s = ensure(B->d_inv, T, &grew)) || (s = ensure(B->d_ret, T, &grew)) || (s = ensure(B->d_ret_slot, T, &grew)) || (s = ensure(B->d_ret_op, T, &grew)) ||
-      (s = ensure(B->d_bitmap, t.bm_n, &grew)) || (s = ensure(B->d_wpre, t.bm_n, &grew)) || (s = ensure(B->d_off, t.boff_n, &grew)) || (s = ensure(B->d_ncr, t.boff_n, &grew)) ||
-      (s = ensure(B->d_rec, t.rec_n, &grew)) || (s = ensure(B->d_seg, t.seg_n, &grew)) || (s = ensure(B->d_frames, t.frame_n, &grew)) ||
-      (s = ensure(B->d_slot8, slot8_bytes(T, nhc), &grew)) || (s = ensure(B->d_stack, t.bstack_n, &grew)))
-    return s;
-  if (B->opts.want_witness && (s = ensure(B->d_witness, T, &grew))) return s;
-  if (B->any_crashed && !B->count_form && (s = ensure(B->d_crashed, T, &grew))) return s;
-  if (B->count_form && (s = ensure(B->d_cmem, t.bocc_n, &grew))) return s;
-  if (B->lanes && (s = ensure(B->d_rk8, slot8_bytes(T, nhc), &grew))) return s;
-  if (B->lanes) { if ((s = ensure(B->d_rdm, T * B->front_words(), &grew))) return s; }
-  else if (B->reg_rules() && (s = ensure(B->d_rdm, T * B->vpad * MW, &grew))) return s;
-  if (B->lookahead) {
-    const bool by_front = MW == 1 && B->vpad <= 32;
-    if ((s = ensure(B->d_look, look_words(T, nhc, MW), &grew)) || (!by_front && (s = ensure(B->d_looktmp, T, &grew))) || (s = ensure(B->d_dstack, t.bstack_n, &grew))) return s;
-  }
-  if ((s = ensure(B->d_btab, t.btab_n * B->tab_stride(), &grew_tab))) return s;
-  if (grew_tab) {
-    B->epoch = 0;          // (a new visited-set arena: zeroed by the run before its first pass, as a batch's first arena is)
-    // ... and the growth pool keeps its share of it (alloc_arenas' rule)
-    const uint64_t words = std::min<uint64_t>(t.btab_n * B->tab_stride() * (B->lanes ? 1u : 3u) / 10, (32ull << 30) / 8);
-    if (words > B->d_pool.n) { B->pool_state.replaced(); if ((s = B->d_pool.regrow(words))) return s; }
-  }
-  (void)grew;
+  const auto ensure = [](auto& buf, uint64_t need) -> tbc_status {
+    if (buf.p && buf.n >= need) return TBC_OK;
+    return buf.regrow((size_t)(need + need / 16));
+  };
+  const size_t tab_had = B->d_btab.n;
+  tbc_status s = visit_input_arenas(B, t, B->in_hist_cap, ensure);
+  if (B->d_btab.n == tab_had) return s;
+  B->epoch = 0;          // (a new visited-set arena: zeroed by the run before its first pass, as a batch's first arena is)
+  if (s != TBC_OK) return s;
+  // ... and the growth pool keeps its share of it
+  const uint64_t words = pool_share_words(B, t);
+  if (words > B->d_pool.n) { B->pool_state.replaced(); if ((s = B->d_pool.regrow(words))) return s; }
   return TBC_OK;
 }
 
@@ -275,12 +251,8 @@ void stream_release(tbc_batch* B) {
     if (B->ev_unpacked[i]) (void)hipEventDestroy(B->ev_unpacked[i]);
     if (B->ev_copy[i][0]) (void)hipEventDestroy(B->ev_copy[i][0]);
     if (B->ev_copy[i][1]) (void)hipEventDestroy(B->ev_copy[i][1]);
-    B->d_stage[i].release();
   }
   for (hipEvent_t& e : B->ev_pair) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  B->d_events.release();
-  B->d_split.release();
-  B->d_in_flags.release(); B->d_list_over.release();
   if (B->in_flags_host) { (void)hipHostFree(B->in_flags_host); B->in_flags_host = nullptr; }
 }
 
@@ -301,18 +273,14 @@ tbc_status stream_consume(tbc_batch* B, bool* consumed) {
     want.bm_n = more(want.bm_n, B->cap.bm_n); want.frame_n = more(want.frame_n, B->cap.frame_n); want.boff_n = more(want.boff_n, B->cap.boff_n);
     want.bstack_n = more(want.bstack_n, B->cap.bstack_n); want.btab_n = more(want.btab_n, B->cap.btab_n);
     B->lists_headroom = true;
-    const uint64_t want = B->d_lst.n + B->d_lst.n / 16 + 4096;
-    if (!(B->lanes && want >= (1ull << 32))) {
-      if ((st = B->d_lst.regrow(want))) return st;
-      if (B->reg_rules() && (st = B->d_twn.regrow(want * B->mask_words))) return st;
-    }
+    const uint64_t roomy = B->d_lst.n + B->d_lst.n / 16 + 4096;
+    if (!lists_past_lanes(B, roomy) && (st = size_lists(B, roomy))) return st;
   }
   if ((st = ensure_arenas(B, want))) return st;
   if (B->count_form && P.lst_total > B->d_lst.n) {          // (no fallback for lists that do not fit: the arena grows BEFORE the run)
     const uint64_t need = P.lst_total + P.lst_total / 16;
-    if (B->lanes && need >= (1ull << 32)) { set_error("the input's per-front lists exceed what several histories per wavefront address: destroy and create"); return TBC_ERR_UNSUPPORTED; }
-    if ((st = B->d_lst.regrow(need))) return st;
-    if (B->reg_rules() && (st = B->d_twn.regrow(need * B->mask_words))) return st;
+    if (lists_past_lanes(B, need)) { set_error("the input's per-front lists exceed what several histories per wavefront address: destroy and create"); return TBC_ERR_UNSUPPORTED; }
+    if ((st = size_lists(B, need))) return st;
     B->lists_regrown++;
   }
   B->count_device_bytes();
@@ -374,10 +342,9 @@ tbc_status stream_after_run(tbc_batch* B, const HostBuf<BeamHist>& bh_back) {
   for (uint32_t h = 0; h < B->n_hist; h++) { need += std::max(1u, bh_back[h].lst_need); over = over || bh_back[h].status == 1u; }
   if (!over || need <= B->d_lst.n) return TBC_OK;
   const uint64_t want = need + need / 16;
-  if (B->lanes && want >= (1ull << 32)) return TBC_OK;          // (the narrow kernel's 32-bit list offsets: such an input keeps its fallback)
+  if (lists_past_lanes(B, want)) return TBC_OK;          // (such an input keeps its fallback)
   tbc_status st;
-  if ((st = B->d_lst.regrow(want))) return st;
-  if (B->reg_rules() && (st = B->d_twn.regrow(want * B->mask_words))) return st;
+  if ((st = size_lists(B, want))) return st;
   B->lists_regrown++;
   B->count_device_bytes();
   return TBC_OK;

@@ -70,6 +70,11 @@ void tbc_batch_destroy(tbc_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   delete b;
+  if (guard_on()) {          // every arena has released itself: none of the batch's is registered any more
+    size_t all = 0;
+    const size_t own = guard_live(b, &all);
+    std::fprintf(stderr, "[tbc guard] batch %p destroyed: %zu of its arenas still registered (%zu of all batches)\n", (const void*)b, own, all);
+  }
 }
 
 tbc_status tbc_check(const tbc_ops* ops, const tbc_model* model, const tbc_opts* opts, tbc_result* out) {

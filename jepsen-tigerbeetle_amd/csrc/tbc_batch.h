@@ -6,6 +6,7 @@
 //   batch_shard.hip    one history over several GPUs (tbc_batch_set_shard ... tbc_batch_sweep_merge)
 //   batch_stream.hip   fresh inputs into a batch's arenas (tbc_batch_map_input / tbc_batch_submit_input / tbc_batch_reload)
 //   tbc_api.hip        tbc_check and the small getters
+// and batch_arenas.h (create and stream include it): what each input-sized arena holds, and the lists' sizing, stated once.
 // Nothing here crosses the C-ABI (include/tbcheck.h does); nothing here runs on the device (tbc_internal.h is what the kernels share).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -92,6 +93,7 @@ extern thread_local const void* t_guard_owner;
 extern thread_local size_t t_guard_nth;          // the arena's number within its batch (allocation order of tbc_batch_create: names it)
 void guard_add(const void* arena_end);
 void guard_remove(const void* arena_end);
+size_t guard_live(const void* owner, size_t* all);         // arenas still registered: the owner's (returned) and everybody's
 size_t guard_check(const char* when, const void* owner);   // arenas of `owner` whose guard bytes were overwritten (after the caller's stream is idle)
 
 template <typename T>
@@ -100,6 +102,10 @@ struct DevBuf {
   size_t n = 0;
   bool owned = false;
   bool guarded = false;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }          // (a piece of a context's slab only un-registers its guard bytes; hipFree waits for the device)
   tbc_status alloc(size_t count) {
     n = count;
     if (count == 0) count = 1;
@@ -233,7 +239,7 @@ struct tbc_batch {
   // counts say slot order), no round budget.  A witness's absorbed reads are replayed in the same order (witness_expand.h).
   static constexpr uint32_t kDefaultListOrder = 16u + 24u;
   bool list_order_applies() const {
-    return width > 1 && mask_words == 1 && vpad <= 32 && !(rules & tbc::kRuleCount) && !sweep && opts.round_budget == 0 &&
+    return width > 1 && tbc::walk_by_front(mask_words, vpad) && !(rules & tbc::kRuleCount) && !sweep && opts.round_budget == 0 &&
            (model.kind == TBC_MODEL_REGISTER || model.kind == TBC_MODEL_CAS_REGISTER);
   }
   // PackOpenArgs.list_order: 0 = slot order, 1 = completion, 2 = completion with the :write calls last, 16 + W
@@ -367,7 +373,7 @@ struct tbc_batch {
   tbc::DevBuf<unsigned char> d_split;
 
   bool borrowed = false;            // stream and events belong to a persistent context (tbc_check)
-  ~tbc_batch();
+  ~tbc_batch();                     // streams, events, pinned memory; the arenas above free themselves after it
 };
 
 namespace tbc {
@@ -402,6 +408,7 @@ tbc_status stream_consume(tbc_batch* B, bool* consumed);
 tbc_status stream_assign_lists(tbc_batch* B);
 // after the run: did the lists fit?  (grows the list arenas for the next input when they did not)
 tbc_status stream_after_run(tbc_batch* B, const HostBuf<BeamHist>& bh_back);
+// the slots' pinned memory and events, the copy stream (idle when it goes)
 void stream_release(tbc_batch* B);
 
 }  // namespace tbc

@@ -68,7 +68,7 @@ struct tbc_comm {
   ncclComm_t nccl = nullptr;                 // RCCL transport ...
   tbc_allgather_fn host_fn = nullptr;        // ... or the caller's, over host memory
   void* host_user = nullptr;
-  DevBuf<uint8_t> gathered;                  // RCCL: world tables back to back, in HBM
+  DevBuf<uint8_t> gathered;                  // RCCL: world tables back to back, in HBM (freed with the communicator)
   std::vector<uint8_t> host_send, host_recv;
 };
 
@@ -116,7 +116,6 @@ uint32_t tbc_comm_world(const tbc_comm* c) { return c ? c->world : 0; }
 void tbc_comm_destroy(tbc_comm* c) {
   if (!c) return;
   if (c->nccl) { (void)hipSetDevice(c->device); (void)rccl().CommDestroy(c->nccl); }
-  c->gathered.release();
   delete c;
 }
 
@@ -134,7 +133,7 @@ tbc_status tbc_batch_sweep_allgather(tbc_batch* b, tbc_comm* c, tbc_result* resu
     if (c->nccl) {
       if (c->device != b->device) { set_error("tbc_batch_sweep_allgather: the communicator lives on device %d, the batch on %d", c->device, b->device); return TBC_ERR_INVALID_ARG; }
       HIP_TRY(hipSetDevice(b->device));
-      if (c->gathered.n < bytes * c->world) { c->gathered.release(); if ((s = c->gathered.alloc((size_t)(bytes * c->world))) != TBC_OK) return s; }
+      if (c->gathered.n < bytes * c->world) { if ((s = c->gathered.regrow((size_t)(bytes * c->world))) != TBC_OK) return s; }
       // (tbc_batch_sweep_partial has synchronised the batch's stream: the table is complete; the collective runs on that stream and
       // tbc_batch_sweep_merge's OR kernel follows it there)
       NCCL_TRY(rccl().AllGather(table, c->gathered.p, (size_t)bytes, ncclUint8, c->nccl, b->stream));

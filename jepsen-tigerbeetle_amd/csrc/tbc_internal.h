@@ -241,7 +241,11 @@ __host__ __device__ inline bool front_compact_ok(uint32_t n_dom, uint32_t mask_w
 // width when there are no rule tables (vpad 0: a mutex, register values past 30) -- at two or four mask words that is the plain record.
 // (At one mask word a record of 8 words is packed and read as the compact one whichever way it came to 8: both sides ask this function.)
 __host__ __device__ inline bool front_is_compact(uint32_t front_words, uint32_t mask_words) { return mask_words == 1 && front_words == kFrontCompactWords; }
-constexpr uint64_t kNarrowMaxOps = 0xFFFFF0ull;          // several histories per wavefront: front + 1 must fit 24 bits of a visited-set key
+// Does the walk over the fronts run with lane = front (one mask word, rows of at most 32 entries), not lane = process slot?  What the
+// host sizes by it: d_looktmp, the scratch of the walk by process slot alone (batch_arenas.h), and whether a list order applies
+// (tbc_batch.h).  launch_pack_open (pack_open.hip) chooses its kernels by the same expression, written out there.
+inline bool walk_by_front(uint32_t mask_words, uint32_t vpad) { return mask_words == 1 && vpad <= 32; }
+constexpr uint64_t kNarrowMaxOps = 0xFFFFF0ull;         // several histories per wavefront: front + 1 must fit 24 bits of a visited-set key
 constexpr int32_t kMaxRuleValue = 30;       // register values 0..30 (vpad <= 32); anything else switches the rules off
 __host__ __device__ inline uint32_t rdm_index(int32_t v, uint32_t vpad) {   // row entry of state / read value v
   return (v == TBC_NIL || (uint32_t)(v + 1) >= vpad) ? 0u : (uint32_t)(v + 1);

@@ -6,6 +6,7 @@ verdict, failing op, every counter -- which in turn is the oracle's schedule bit
 import numpy as np
 import pytest
 
+import batch_size_shapes as S
 from jepsen_tigerbeetle_amd import _native as N, columns, core, synth
 
 pytestmark = pytest.mark.gpu
@@ -193,3 +194,80 @@ def test_a_count_form_batch_takes_fresh_inputs(native, oracle, lanes):
         calm = hists_of(7900, 40, n_ops=500, info=0.0)
         b.reload(calm)
         assert [key(r)[:3] for r in b.run().results()] == [k[:3] for k in fresh(calm, opts)]
+
+
+# ---- a second growth in mid-stream (csrc/batch_arenas.h: the input-sized arenas as tbc_batch_create and ensure_arenas both visit them)
+SHAPE_KEYS = KEYS + ("search_width",)
+# (family of tests/batch_size_shapes.py, histories, witness): several histories per wavefront at two mask words; the wide schedule with
+# the lookahead at two mask words (the walk with lane = process slot: its scratch arena exists) and parent links read back; crashed
+# calls as mask bits (their own arena, an entry per op); the count form (crashed calls as classes)
+# (as many histories as make T0 a little over 2,000 ops while the family's longest are still a fifth longer than its shortest)
+GROWTH_CASES = [("narrow-2w", 12, False), ("wide-2w", 12, True), ("crashed-mask-wide", 20, False), ("count-wide", 20, False)]
+
+
+def as_the_oracle(name, res, exp, tag):
+    """every history against the reference of its family's schedule (tests/batch_size_shapes.py, reference): the verdict, the failing
+    op, the state a valid history ends in, the counters"""
+    count = S.FAMILIES[name].kind == "count"
+    assert len(res) == len(exp), tag
+    for i, (g, e) in enumerate(zip(res, exp)):
+        assert g["valid"] == e["valid"] != N.UNKNOWN, (tag, i, g["valid"], e["valid"], g["cause"])
+        assert g["fail_op"] == e["fail_op"] if e["valid"] == 0 else g["final_state"] == e["final_state"], (tag, i)
+        for k in ("probes", "visited", "backtracks") + (() if count else ("max_depth",)):
+            assert g[k] == e[k], (tag, i, k, g[k], e[k])
+
+
+def _growth_inputs(name, n):
+    """-> three inputs of n histories as (histories, base indices, from other seeds?): the family's n shortest, the same places from
+    other seeds (about as many ops), its n longest (a third more)"""
+    b, o = S.base(name), S.other_base(name)
+    by_len = sorted(range(S.N_BASE), key=lambda j: (len(b[j]), j))
+    short, long_ = by_len[:n], by_len[-n:]
+    return ([b[j] for j in short], short, [False] * n), ([o[j] for j in short], short, [True] * n), ([b[j] for j in long_], long_, [False] * n)
+
+
+@pytest.mark.parametrize("name,n,witness", GROWTH_CASES, ids=lambda v: str(v))
+def test_the_arenas_grow_a_second_time_in_mid_stream(native, oracle, name, n, witness):
+    """Every other fresh-input test grows the arenas once, at the first consumed input (stream_consume asks for 1/64 more than the batch
+    was created for, ensure_arenas gives 1/16 on top: about 1.08 T0 ops).  Here a second input of about T0 ops is followed by a third
+    of at least 1.2 T0: it fits the slot (T0 * 1.125 rounded up to 1,024, plus 1,024) and outgrows every per-op arena in mid-stream.
+    Both fresh inputs answer as the oracle and as batches created from them; device_bytes() says that the arenas grew."""
+    (first, idx0, w0), (same, idx1, w1), (more, idx2, w2) = _growth_inputs(name, n)
+    t0, t1, t2 = (sum(len(h) for h in x) for x in (first, same, more))
+    opts = core.make_opts(time_limit_ms=120000, algorithm=N.ALG_COMPETITION, **dict(S.FAMILIES[name].opts, want_witness=witness))
+
+    def created(hists):
+        with core.Batch(hists, gm(), opts) as c:
+            return c.run().results()
+
+    def same_answers(got, exp):
+        assert [tuple(r[k] for k in SHAPE_KEYS) for r in got] == [tuple(r[k] for k in SHAPE_KEYS) for r in exp]
+        if witness:
+            assert any(r["witness"] is not None for r in exp)
+            for g, e in zip(got, exp):
+                assert (g["witness"] is None) == (e["witness"] is None) and (e["witness"] is None or np.array_equal(g["witness"], e["witness"]))
+
+    with core.Batch(first, gm(), opts) as b:
+        as_the_oracle(name, b.run().results(), S.expected(oracle, name, first, idx0, w0), (name, "created"))
+        d0 = b.device_bytes()
+        b.reload(same)
+        res1 = b.run().results()
+        d1 = b.device_bytes()
+        # the totals: the second input left the per-op arenas at the first growth's size, the third is beyond it and within a slot
+        ops_cap = b.input_info()["ops_cap"]
+        asked = max(t1, t0 + t0 // 64 + 1)
+        held = asked + asked // 16
+        assert ops_cap == ((t0 + t0 // 8 + 1023) & ~1023) + 1024
+        assert 2000 <= t0 and abs(t1 - t0) <= t0 // 16 and 1.2 * t0 <= t2 <= ops_cap and held < t2, (t0, t1, t2, held, ops_cap)
+        as_the_oracle(name, res1, S.expected(oracle, name, same, idx1, w1), (name, "about T0"))
+        same_answers(res1, created(same))
+        b.reload(more)
+        res2 = b.run().results()
+        d2 = b.device_bytes()
+        as_the_oracle(name, res2, S.expected(oracle, name, more, idx2, w2), (name, "1.2 T0"))
+        same_answers(res2, created(more))
+        info = b.input_info()
+        assert d0 < d1 < d2, (d0, d1, d2)
+        assert (info["inputs_consumed"], info["n_hist"], info["pending"], info["ops_cap"]) == (2, n, 0, ops_cap)
+        if S.FAMILIES[name].kind != "count":          # (nobody fell back to the sequential kernel: the lists fitted what the first growth left)
+            assert info["lists_regrown"] == 0
